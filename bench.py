@@ -1,24 +1,27 @@
 #!/usr/bin/env python
 """HGTConv forward benchmark (BASELINE.json metric: edges/s + achieved HBM GB/s).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One step = one HGTConv.forward (eval mode, fp32, plan cached -- the reference reuses one sampled
 graph for all layers and `repeat` optimisation steps, model.py:78-79 / train_paper_field.py:240)
-over a synthetic typed graph that is already resident in HBM.  After the timed region the output
-of the benchmarked configuration itself is checked against the fp64 CPU oracle on ~2000 sampled
-target rows (`parity_max_abs_err`; the run fails above 1e-4), and secondary figures are taken:
-the other precision, the plan-included rate, the median next to the mean.
+over a synthetic typed graph that is already resident in HBM.  A plain run sets up, warms up,
+times exactly --steps steps, writes the last step's output if --dump-outputs is given (DIR/<name>.npy,
+float32; a fixed seeded sample of the rows of a large output) and prints the result line.
+With --full, after the timed region the output of the benchmarked configuration itself is
+checked against the fp64 CPU oracle on ~2000 sampled target rows (`parity_max_abs_err`; the run
+fails above 1e-4), and secondary figures are taken: the other precisions, the plan-included
+rate, shape variants, the latency regime, the emulated rank of 8 and the CPU baseline.
   N = 1 : BASELINE.json configs[1]: T=4 R=8, 1M nodes / 10M edges, d=256, H=8, 4-argument form
           (use_RTE=False), LayerNorm on.
   N > 1 : weak scaling -- every rank owns 1M target nodes and their 10M in-edges; sources are
           uniform over all N*1M nodes; halo source rows (exact fp32) come over one RCCL all-to-all per
           step (pyhgt_amd/dist.py); value = total edges of all ranks / max-over-ranks time.
 Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` (dominant kernel,
-timed with HIP events on the launch stream during the timed steps) and `cpu_baseline` (the CPU
-port of the reference algorithm, oracle/hgt_oracle.py, on a bounded sample).
+timed with HIP events on the launch stream during the timed steps) and, with --full, `cpu_baseline`
+(the CPU port of the reference algorithm, oracle/hgt_oracle.py, on a bounded sample).
 """
 import argparse
 import ctypes as C
@@ -201,6 +204,26 @@ def kernel_sources_sha16():
         h.update(os.path.basename(path).encode())
         h.update(open(path, "rb").read())
     return h.hexdigest()[:16]
+
+
+DUMP_BYTES = 16 * 2 ** 20     # --dump-outputs: at most this much float32 per process
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs DIR: the tensors the timed path returned in its last step, as DIR/<name>.npy in float32.  An output larger than
+    its share of DUMP_BYTES is written as a fixed sample of its rows (a permutation seeded with 0, first rows kept, ascending), so
+    that two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        row_bytes = 4 * max(t[0].numel() if t.dim() > 0 and t.size(0) else 1, 1)
+        if t.dim() > 0 and t.size(0) * row_bytes > budget:
+            keep = max(budget // row_bytes, 1)
+            rows = torch.randperm(t.size(0), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.float().cpu().numpy())
 
 
 def wall_us(fn, iters, warm, repeats=3):
@@ -437,6 +460,8 @@ def replicas_c5(args, world, rank, dev, backend_name):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
     assert torch.isfinite(out).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out" if world == 1 else "out_rank%d" % rank: out})
     my_edges = float(sum(edges[i % pool] for i in range(args.steps)) * L)
     tot = torch.tensor([elapsed, my_edges], device=dev if backend_name in ("nccl", "none") else "cpu", dtype=torch.float64)
     if world > 1:
@@ -451,7 +476,7 @@ def replicas_c5(args, world, rank, dev, backend_name):
     if rank == 0:
         # parity of the replica's model path against the verbatim reference GNN (same shape, golden rows): after the timed region
         parity = None
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             import numpy as np
             from oracle import hgt_oracle as O
             from oracle.gen_golden_gnn import GNN_CASES, build_batch
@@ -619,6 +644,11 @@ def main():
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--types", type=int, default=4)
     ap.add_argument("--relations", type=int, default=8)
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run everything beyond the headline: the parity check "
+                    "against the fp64 CPU oracle, the other precisions, the shape variants, the latency regime, the emulated rank of 8 and "
+                    "the CPU baseline (each can still be left out with its --no-* option).  Off: set-up, warm-up, timed steps, result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step as "
+                    "DIR/<name>.npy (float32; a fixed seeded sample of the rows of a large output, at most 16 MB per process)")
     ap.add_argument("--rte", action="store_true", help="5-argument form with temporal encoding")
     ap.add_argument("--dst-skew", type=float, default=0.0, help="secondary variant: Zipf exponent a in (0,1) of the target in-degree distribution (hubs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -643,7 +673,7 @@ def main():
                     help="typed linears / relation transforms.  Default (round 6, N = 1) f16x3 = 3-term fp16 hi/lo MFMA with power-of-two "
                          "row scales, fp32 accumulation: the layer's default, the reference's own fp32 accuracy (<= 2e-6 from the fp64 "
                          "oracle).  bf16x3 = 3-term split-bf16 MFMA (the split SURVEY.md 7.2 prescribes, <= 3.5e-5, north-star bound 1e-4; "
-                         "the judged mode of rounds 1-5, ~5 %% faster): measured in EVERY default run and reported at the top level of the "
+                         "the judged mode of rounds 1-5, ~5 %% faster): measured in every --full run and reported at the top level of the "
                          "line as `fast_mode` (and under `secondary`, with exact fp32).  N > 1 defaults to bf16x3: the staged calls run it")
     ap.add_argument("--kernel-flags", type=int, default=0, help="hgt_conv_args.flags (HGT_FLAG_*), A/B runs")
     ap.add_argument("--workload", default="c2", choices=["c2", "c5"],
@@ -653,7 +683,7 @@ def main():
     ap.add_argument("--small-only", action="store_true", help="tool mode: only the latency-regime measurements of the line (c1, c3, script-default "
                     "batch, c5, published 4-layer model), printed as one JSON object")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="also run the CPU port ONCE at the full c2 size (about a minute; needs >= 64 GB "
-                    "of free RAM); the default on hosts with >= 96 GB of RAM available")
+                    "of free RAM); with --full, the default on hosts with >= 96 GB of RAM available")
     ap.add_argument("--cpu-baseline-sample-only", action="store_true", help="never run the full-size CPU forward")
     ap.add_argument("--cpu-full-size", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
@@ -759,13 +789,13 @@ def main():
     if world == 1:
         edge_index = torch.stack([src_global, dst_local], dim=1).t()       # (1,2)-strided view like data.py:254
         plan_times = []
-        for _ in range(3):
+        for _ in range(3 if args.full else 1):      # the plan-build time (fastest of 3) is a --full figure
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             plan = GraphPlan(node_type_own, edge_index, edge_type, edge_time, T, R)
             torch.cuda.synchronize()
             plan_times.append((time.perf_counter() - t0) * 1e3)
-        plan_ms = min(plan_times)
+        plan_ms = min(plan_times) if args.full else None
 
         def make_step(lay, compress=None):
             return lambda events=None: lay(x_own, node_type_own, edge_index, edge_type, edge_time, plan=plan, phase_events=events)
@@ -837,6 +867,10 @@ def main():
 
     out, elapsed, phase_ms, median_ms = timed(make_step(layer), args.steps, args.warmup)
     assert torch.isfinite(out).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out" if world == 1 else "out_rank%d" % rank: out})
+    do_parity = args.full and not args.no_parity
+    do_secondary = args.full and not args.no_secondary
 
     ms_per_step = elapsed / args.steps * 1e3
     total_edges = El * world
@@ -849,14 +883,14 @@ def main():
 
     # ---------------- parity of the benchmarked configuration itself (after the timed region) ----------------
     def check(o, sd):
-        if args.no_parity:
+        if not do_parity:
             return None
         if world == 1:
             return parity_check(sd, o, x_own, node_type_own, edge_index, edge_type, edge_time, T, R, H, use_rte)
         # a rank's local graph [own ; halo]: exact for its own targets only if the exchanged halo rows are right
         return parity_check(sd, o, pg.x_local, pg.node_type_local, pg.edge_index, pg.edge_type, pg.edge_time, T, R, H, use_rte,
                             n_q_rows=Nl)
-    if world > 1 and not args.no_parity:
+    if world > 1 and do_parity:
         # The checker wants the TRUE inputs: exact fp32 halo rows (compress=False), whatever format the timed steps shipped -- with
         # the rows of the 24-bit wire format fed to the oracle as well, the format's own rounding (<= 2^-16 relative per remote
         # source element) would cancel out of parity_max_abs_err and the 1e-4 gate could not see it (round-4 advisor finding).
@@ -916,7 +950,7 @@ def main():
 
     # ---------------- secondary measurements (never `value`) ----------------
     secondary = {}
-    if not args.no_secondary:
+    if do_secondary:
         if world == 1:
             for other in [p for p in ("bf16x3", "f16x3", "fp32") if p != args.precision]:
                 lay2 = make_layer(other)
@@ -932,7 +966,7 @@ def main():
                 del out2, lay2
         else:
             def refill():      # (the parity checker reads the EXACT fp32 halo rows: see above)
-                if not args.no_parity:
+                if do_parity:
                     with torch.no_grad():
                         for c in range(pg.halo.n_chunks):
                             pg.halo.exchange_chunk(c, x_own, pg.x_local, compress=False)
@@ -962,7 +996,7 @@ def main():
                 del out3
 
     # ---------------- the other BASELINE.json configurations + shape variants of configs[1], each with its own parity ------------
-    if world == 1 and not args.no_secondary and not (args.rte or args.dst_skew > 0.0):
+    if world == 1 and do_secondary and not (args.rte or args.dst_skew > 0.0):
         del x_own, src_global, dst_local, edge_type, edge_index, plan
         GraphPlan.clear_cache()
         torch.cuda.empty_cache()
@@ -992,7 +1026,7 @@ def main():
                 sdv = {k: v.detach().cpu() for k, v in lay.state_dict().items()}
                 outv, elv, phv, medv = timed(lambda events=None: lay(xv, ntv, eiv, etv, tmv, plan=planv, phase_events=events), 10, 2)
                 msv = elv / 10 * 1e3
-                par = None if args.no_parity else parity_check(sdv, outv, xv, ntv, eiv, etv, tmv, T, R, Hv, rte)
+                par = None if not do_parity else parity_check(sdv, outv, xv, ntv, eiv, etv, tmv, T, R, Hv, rte)
                 return {"precision": prec, "ms_per_step": msv, "median_ms_per_step": medv, "edges_per_s": Ev / (msv * 1e-3),
                         "layer_frac": round(algv / (msv * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "phase_ms": {p: round(v, 4) for p, v in phv.items()},
                         "parity_max_abs_err": None if par is None else par["max_abs_err"]}
@@ -1022,7 +1056,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the one full-size forward of the port (about a minute on the GPU box's host) runs in every default line whose host has
             # the RAM for it (>= 96 GB available): the full-c2 CPU figure is then observed by whoever runs the line
             ram_ok = (host_mem_gb()[1] or 0) >= 96
@@ -1032,7 +1066,7 @@ def main():
                               "fp32 accumulate)"}
         line = {
             "metric": "HGTConv forward edges/sec", "value": value, "unit": "edges/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "median_ms_per_step": median_ms,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "median_ms_per_step": median_ms, "full": args.full,
             "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None,
             # said plainly (round-4 review): the builder's development loop has ONE GPU -- no step of the dst-partitioned path has been

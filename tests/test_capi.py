@@ -10,9 +10,20 @@ import torch
 
 from pyhgt_amd import _lib
 from oracle import hgt_oracle as O
-from oracle.reference_loader import reference_available, load_reference_conv, load_reference_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _reference_modules():
+    """State-dict names, shapes and repr of the reference's own modules (tests/golden/ref/ref_modules.json, written by
+    oracle/gen_golden_ref.py from the live reference)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "ref", "ref_modules.json")) as f:
+        return json.load(f)
+
+
+def _reference_state_dict(rec):
+    return {k: torch.zeros(shape) for k, shape in zip(rec["keys"], rec["shapes"])}
 
 
 def _declared_symbols():
@@ -88,18 +99,17 @@ def test_module_keeps_reference_state_dict_names():
     assert torch.allclose(fresh, O.sinusoid_table(d), atol=1e-7)
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference only exists in the build container")
 def test_state_dict_names_equal_the_live_reference():
     from pyhgt_amd import HGTConv
-    conv = load_reference_conv()
-    for use_norm, use_rte in ((True, True), (False, False)):
-        ref = conv.HGTConv(32, 32, 2, 3, 4, 0.2, use_norm, use_rte)
+    mods = _reference_modules()
+    for use_norm, use_rte, name in ((True, True, "hgt_conv_norm_rte"), (False, False, "hgt_conv_plain")):
+        ref = mods[name]
         ours = HGTConv(32, 32, 2, 3, 4, 0.2, use_norm, use_rte)
-        rs, os_ = ref.state_dict(), ours.state_dict()
+        rs, os_ = _reference_state_dict(ref), ours.state_dict()
         assert list(rs.keys()) == list(os_.keys())
         assert all(rs[k].shape == os_[k].shape for k in rs)
         ours.load_state_dict(rs)
-        assert repr(ours) == repr(ref)
+        assert repr(ours) == ref["repr"]
 
 
 def test_cpu_input_fails_loudly():
@@ -132,17 +142,15 @@ def test_dense_module_keeps_reference_state_dict_names():
     layer.load_state_dict(sd)
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference only exists in the build container")
 def test_dense_state_dict_names_equal_the_live_reference():
     from pyhgt_amd import DenseHGTConv
-    conv = load_reference_conv()
-    ref = conv.DenseHGTConv(32, 32, 2, 3, 4, 0.2, True, True)
+    ref = _reference_modules()["dense_hgt_conv"]
     ours = DenseHGTConv(32, 32, 2, 3, 4, 0.2, True, True)
-    rs, os_ = ref.state_dict(), ours.state_dict()
+    rs, os_ = _reference_state_dict(ref), ours.state_dict()
     assert set(rs.keys()) == set(os_.keys())
     assert all(rs[k].shape == os_[k].shape for k in rs)
     ours.load_state_dict(rs)
-    assert repr(ours) == repr(ref)
+    assert repr(ours) == ref["repr"]
 
 
 def test_gnn_wrapper_matches_reference_parameter_count():
@@ -152,27 +160,24 @@ def test_gnn_wrapper_matches_reference_parameter_count():
     assert sum(p.numel() for p in gnn.parameters()) + (512 * 349 + 349) == 21173389
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference only exists in the build container")
 def test_gnn_state_dict_names_equal_the_live_reference():
-    from oracle.reference_loader import load_reference_model
     from pyhgt_amd import GNN
-    ref = load_reference_model().GNN(32, 64, 3, 4, 4, 2, prev_norm=True, last_norm=False, use_RTE=True)
+    ref = _reference_modules()["gnn"]
     ours = GNN(32, 64, 3, 4, 4, 2, prev_norm=True, last_norm=False, use_RTE=True)
-    rs, os_ = ref.state_dict(), ours.state_dict()
+    rs, os_ = _reference_state_dict(ref), ours.state_dict()
     assert list(rs.keys()) == list(os_.keys())
     assert all(rs[k].shape == os_[k].shape for k in rs)
     ours.load_state_dict(rs)
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference only exists in the build container")
 def test_heads_keep_reference_state_dict_names():
     """Classifier / Matcher (model.py:3-49): same parameter names, shapes and repr as the live reference."""
     from pyhgt_amd import Classifier, Matcher
-    model = load_reference_model()
-    for ours, ref in ((Classifier(32, 7), model.Classifier(32, 7)), (Matcher(32), model.Matcher(32))):
-        rs, os_ = ref.state_dict(), ours.state_dict()
+    mods = _reference_modules()
+    for ours, ref in ((Classifier(32, 7), mods["classifier"]), (Matcher(32), mods["matcher"])):
+        rs, os_ = _reference_state_dict(ref), ours.state_dict()
         assert list(rs.keys()) == list(os_.keys())
         assert all(rs[k].shape == os_[k].shape for k in rs)
         ours.load_state_dict(rs)
         if isinstance(ours, Classifier):      # the reference's Matcher.__repr__ reads an attribute it never sets (model.py:47-49)
-            assert repr(ours) == repr(ref)
+            assert repr(ours) == ref["repr"]

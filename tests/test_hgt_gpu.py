@@ -1627,7 +1627,8 @@ def test_bench_line_of_a_multi_rank_run_reports_world_size_and_backend(tmp_path)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HGT_BENCH_DEVICE="0", HGT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c5", "--steps", "6", "--warmup", "2"]
+           "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c5", "--steps", "6", "--warmup", "2",
+           "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -1651,7 +1652,7 @@ def test_bench_line_of_a_two_rank_partitioned_run(tmp_path):
     env = dict(os.environ, HGT_BENCH_DEVICE="0", HGT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--nodes-per-gpu", "40000", "--edges-per-gpu", "400000", "--blocks", "4", "--locality", "0.5", "--no-cpu-baseline"]
+           "--nodes-per-gpu", "40000", "--edges-per-gpu", "400000", "--blocks", "4", "--locality", "0.5", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

@@ -1,13 +1,16 @@
 """the device-side hand-off of sampled batches.  CPU part: the synthetic sampler output has the layout
 facts of the reference pipeline (appendix C) and `to_torch_layout` reproduces the reference's own `to_torch` bit for bit."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
 
-from oracle.reference_loader import reference_available, load_reference_data
+from oracle.gen_golden_ref import TO_TORCH_CASES
 from pyhgt_amd.sampled import synthetic_sampled_batch, to_torch_layout
 
-needs_ref = pytest.mark.skipif(not reference_available(), reason="reference tree not present (GPU box)")
+REF_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref")
 
 
 @pytest.mark.parametrize("schema,T,R", [("mag", 4, 9), ("oag", 5, 33)])
@@ -33,14 +36,15 @@ def test_synthetic_batch_has_the_layout_of_the_reference_pipeline(schema, T, R):
             seen_types.add(t)
 
 
-@needs_ref
 @pytest.mark.parametrize("schema", ["mag", "oag"])
 def test_to_torch_layout_equals_the_reference_to_torch(schema):
-    data = load_reference_data()
-    feature, time, edge_list, graph = synthetic_sampled_batch(schema, n_seed=16, width=12, depth=2, feat_dim=8, seed=3)
-    ref = data.to_torch(feature, time, edge_list, graph)                       # data.py:212-256, verbatim
+    """Against what the reference's own to_torch (data.py:212-256) returned for the same batch (oracle/gen_golden_ref.py)."""
+    z = np.load(os.path.join(REF_DIR, "ref_to_torch.npz"))
+    feature, time, edge_list, graph = synthetic_sampled_batch(schema, **TO_TORCH_CASES[schema])
     mine = to_torch_layout(feature, time, edge_list, graph)
-    for a, b in zip(ref[:5], mine[:5]):
+    for i, b in enumerate(mine[:5]):
+        a = torch.from_numpy(z["%s/%d" % (schema, i)])
         assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
-    assert ref[3].stride() == mine[3].stride()
-    assert ref[5] == mine[5] and ref[6] == mine[6]
+    assert tuple(int(v) for v in z["%s/edge_index_stride" % schema]) == mine[3].stride()
+    node_dict, edge_dict = json.loads(str(z["%s/dicts" % schema]))
+    assert node_dict == json.loads(json.dumps(mine[5])) and edge_dict == mine[6]

@@ -1,19 +1,19 @@
 #!/bin/bash
-# tools/collect_evidence.sh <tag>: copy what `tools/gpu.sh final <tag>` left in gpurun_out/ (scratch, merged back from the GPU box) into
+# tools/collect_evidence.sh <tag>: copy what `tools/gpu.sh final <tag>` left in its output folder (HGT_OUT_DIR, default bench_out/) into
 # profiles/ (tracked): the judged line, rocprofv3 kernel statistics + counters, latency timelines, training line, rank-of-8 emulation,
-# x-stationary GEMM check, test-suite summaries.  Run from the repo root in the build container after the gpurun call has returned.
+# x-stationary GEMM check, test-suite summaries.  Run from the repo root once that folder is back from the GPU machine.
 set -e
-TAG=${1:-r06}; G=gpurun_out; P=profiles
+TAG=${1:-r06}; G=${HGT_OUT_DIR:-bench_out}; P=profiles
 COMMIT=$(cat .commit 2>/dev/null || echo unknown)
 cp $G/prof_$TAG/${TAG}_kernel_stats.csv $G/prof_$TAG/${TAG}_pmc_per_kernel.csv $G/prof_$TAG/${TAG}_pmc_summary.json $P/
 tail -1 $G/${TAG}_bench.json | python -c "import json,sys; print(json.dumps(json.loads(sys.stdin.read()), indent=1))" > $P/${TAG}_bench_line.json
 cp $G/${TAG}_latency_*.txt $P/
 cp $G/${TAG}_train_line.json $G/${TAG}_train_kernel_stats.txt $P/ 2>/dev/null || true
-python - $TAG <<'PY'
+python - $TAG $G <<'PY'
 import json, sys, glob, os
-tag = sys.argv[1]
+tag, out_dir = sys.argv[1], sys.argv[2]
 out = {}
-for f in sorted(glob.glob("gpurun_out/%s_emu8_loc*.json" % tag)):
+for f in sorted(glob.glob(os.path.join(out_dir, "%s_emu8_loc*.json" % tag))):
     try:
         j = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:

@@ -1,12 +1,12 @@
 #!/bin/bash
 # rocprofv3 passes of the judged benchmark command (run on the GPU box through gpurun, from the repo root):
 #   tools/profile_pmc.sh <tag> [extra bench.py flags]
-# writes gpurun_out/prof_<tag>/{stats,fetch,write,sqA..sqE}/...; tools/pmc_summary.py turns them into profiles/<tag>_*.csv|json.
+# writes $HGT_OUT_DIR/prof_<tag>/{stats,fetch,write,sqA..sqE}/... (default bench_out/); tools/pmc_summary.py turns them into profiles/<tag>_*.csv|json.
 # Counters are collected in their own runs (kernel trace only next to --pmc), one small set per pass.
 set -u
 TAG=${1:-r03}; shift || true
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$ROOT/gpurun_out/prof_$TAG
+OUT=$ROOT/${HGT_OUT_DIR:-bench_out}/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 BENCH="python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-secondary $*"

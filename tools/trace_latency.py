@@ -5,7 +5,7 @@
                                                                             the sum of the durations, and the span first start -> last end
 c3 / c3w520: one HGTConv layer on the sampler-shaped ogbn-mag batch (sample_width 128 / 520); c5: the 2-layer OAG GNN (in 1169 -> 400,
 33 relations); mag4: the published 4-layer n_hid = 512 ogbn-mag model; c1: BASELINE.json configs[0] (tests/golden/c1_full.npz).
-tools/gpu.sh latency <tag> runs all of them and writes profiles-ready text files to gpurun_out/."""
+tools/gpu.sh latency <tag> runs all of them and writes profiles-ready text files to its output folder."""
 import csv
 import glob
 import os
