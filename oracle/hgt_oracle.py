@@ -128,10 +128,22 @@ def _segment_softmax(s, dst, n_nodes):
     return p / (z[dst] + 1e-16)
 
 
-def _update(sd, agg, x, node_type, num_types, use_norm, dtype, library_ops=False):
-    """conv.py:114-134 (eval mode: dropout is the identity).  library_ops=True uses the same
-    torch.nn.functional calls as the reference (F.gelu, LayerNorm) -- for the timed port; the
-    checker keeps the explicit formulas."""
+def _drop_masks(drop_masks):
+    """(m1, m2) of a training-mode forward: m1 multiplies the a_linear output (conv.py:125 / conv.py:261), m2 the
+    out_linear output of DenseHGTConv (conv.py:273); [N, d] tensors of 0 or 1/(1-p), or None (eval mode)."""
+    if drop_masks is None:
+        return None, None
+    if torch.is_tensor(drop_masks):
+        return drop_masks, None
+    m1, m2 = (tuple(drop_masks) + (None,))[:2]
+    return m1, m2
+
+
+def _update(sd, agg, x, node_type, num_types, use_norm, dtype, library_ops=False, drop_masks=None):
+    """conv.py:114-134 (eval mode: dropout is the identity; drop_masks=(m1, _) multiplies the a_linear output by m1 like
+    the training-mode self.drop of conv.py:125).  library_ops=True uses the same torch.nn.functional calls as the
+    reference (F.gelu, LayerNorm) -- for the timed port; the checker keeps the explicit formulas."""
+    m1, _ = _drop_masks(drop_masks)
     N, d = agg.shape
     Wa = _stack(sd, "a_linears.%d.weight", num_types, dtype)
     ba = _stack(sd, "a_linears.%d.bias", num_types, dtype)
@@ -143,6 +155,8 @@ def _update(sd, agg, x, node_type, num_types, use_norm, dtype, library_ops=False
         if rows.numel() == 0:
             continue
         o = g[rows] @ Wa[t].T + ba[t]                               # conv.py:125
+        if m1 is not None:
+            o = o * m1[rows].to(dtype)
         y = o * alpha[t] + x[rows] * (1.0 - alpha[t])               # conv.py:131/133
         if use_norm:
             w, b = sd["norms.%d.weight" % t].to(dtype), sd["norms.%d.bias" % t].to(dtype)
@@ -151,9 +165,12 @@ def _update(sd, agg, x, node_type, num_types, use_norm, dtype, library_ops=False
     return out
 
 
-def _update_dense(sd, agg, x, node_type, num_types, use_norm, dtype):
+def _update_dense(sd, agg, x, node_type, num_types, use_norm, dtype, drop_masks=None):
     """DenseHGTConv.update, conv.py:250-274 (eval mode): per type  y1 = LN_t(a_linear_t(agg) + x)  (no gelu on
-    the aggregate, no gate), then the shared dense layer  out = out_norm(out_linear(gelu(mid_linear(y1))) + y1)."""
+    the aggregate, no gate), then the shared dense layer  out = out_norm(out_linear(gelu(mid_linear(y1))) + y1).
+    drop_masks=(m1, m2): the two training-mode dropouts, m1 on the a_linear output (conv.py:261), m2 on the
+    out_linear output (conv.py:273)."""
+    m1, m2 = _drop_masks(drop_masks)
     N, d = agg.shape
     Wa = _stack(sd, "a_linears.%d.weight", num_types, dtype)
     ba = _stack(sd, "a_linears.%d.bias", num_types, dtype)
@@ -165,11 +182,16 @@ def _update_dense(sd, agg, x, node_type, num_types, use_norm, dtype):
         rows = (node_type == t).nonzero(as_tuple=True)[0]
         if rows.numel() == 0:
             continue
-        y1 = agg[rows] @ Wa[t].T + ba[t] + x[rows]                  # conv.py:259
+        o = agg[rows] @ Wa[t].T + ba[t]                             # conv.py:261
+        if m1 is not None:
+            o = o * m1[rows].to(dtype)
+        y1 = o + x[rows]
         if use_norm:
             y1 = _layer_norm(y1, sd["norms.%d.weight" % t].to(dtype), sd["norms.%d.bias" % t].to(dtype))   # conv.py:264
-        y2 = _gelu_erf(y1 @ Wm.T + bm) @ Wo.T + bo + y1             # conv.py:271
-        out[rows] = _layer_norm(y2, wn, bn)                         # conv.py:272
+        o2 = _gelu_erf(y1 @ Wm.T + bm) @ Wo.T + bo                  # conv.py:273
+        if m2 is not None:
+            o2 = o2 * m2[rows].to(dtype)
+        out[rows] = _layer_norm(o2 + y1, wn, bn)                    # conv.py:274
     return out
 
 
@@ -178,9 +200,10 @@ def _update_dense(sd, agg, x, node_type, num_types, use_norm, dtype):
 # --------------------------------------------------------------------------
 def forward_closed_form(sd, num_types, num_relations, n_heads, x, node_type, edge_index,
                         edge_type, edge_time=None, use_norm=True, use_RTE=True,
-                        dtype=torch.float64, return_att=False, return_agg=False, dense=False):
+                        dtype=torch.float64, return_att=False, return_agg=False, dense=False, drop_masks=None):
     """One HGTConv (or, with dense=True, DenseHGTConv: same message(), conv.py:197-248, update of conv.py:250-274)
-    forward (eval mode).  Math follows conv.py:60-134:
+    forward (eval mode; drop_masks=(m1, m2) replays the dropouts of a training-mode forward, see _update /
+    _update_dense).  Math follows conv.py:60-134:
 
       q_e = W_q[tau(i)] x_i + b          (conv.py:73-77,96)
       k_e = W_k[tau(j)] (x_j + RTE(dt_e)) + b   (conv.py:91-92,97)
@@ -258,7 +281,7 @@ def forward_closed_form(sd, num_types, num_relations, n_heads, x, node_type, edg
         att = s
     msg = (vp * att.unsqueeze(-1)).reshape(E, d)
     agg = torch.zeros(N, d, dtype=dtype).index_add_(0, dst, msg)
-    out = (_update_dense if dense else _update)(sd, agg, x, ntype, T, use_norm, dtype)
+    out = (_update_dense if dense else _update)(sd, agg, x, ntype, T, use_norm, dtype, drop_masks=drop_masks)
     res = [out]
     if return_att:
         res.append(att)
@@ -322,14 +345,15 @@ def forward_meta_relation_port(sd, num_types, num_relations, n_heads, x, node_ty
 # entry point 3: gradients (oracle for the backward pass, SURVEY.md section 8f-2 -- not built on the GPU yet)
 # --------------------------------------------------------------------------
 def backward_reference(sd, num_types, num_relations, n_heads, x, node_type, edge_index, edge_type, edge_time, grad_out,
-                       use_norm=True, use_RTE=True, dtype=torch.float64, dense=False):
+                       use_norm=True, use_RTE=True, dtype=torch.float64, dense=False, drop_masks=None):
     """d<out, grad_out> / d(x) and / d(every floating parameter of sd), by reverse-mode differentiation of
     forward_closed_form (every step of it is a differentiable torch op, so this is the exact backward of the math of
-    conv.py:60-134 in eval mode).  Pinned against autograd through the verbatim reference in tests/test_oracle.py."""
+    conv.py:60-134 in eval mode, or in training mode with the given dropout masks drop_masks=(m1, m2)).  Pinned against
+    autograd through the verbatim reference in tests/test_oracle.py."""
     leaf = {k: v.detach().to(dtype).requires_grad_(True) for k, v in sd.items() if v.is_floating_point()}
     xg = x.detach().to(dtype).requires_grad_(True)
     out = forward_closed_form(leaf, num_types, num_relations, n_heads, xg, node_type, edge_index, edge_type, edge_time,
-                              use_norm=use_norm, use_RTE=use_RTE, dtype=dtype, dense=dense)
+                              use_norm=use_norm, use_RTE=use_RTE, dtype=dtype, dense=dense, drop_masks=drop_masks)
     names = list(leaf.keys())
     grads = torch.autograd.grad((out * grad_out.to(dtype)).sum(), [xg] + [leaf[k] for k in names], allow_unused=True)
     res = {"x": grads[0]}

@@ -188,7 +188,7 @@ class _HGTConvTrain(torch.autograd.Function):
         lay = _lib.layout_for(layer.out_dim, layer.n_heads)
         T, R, H = layer.num_types, layer.num_relations, layer.n_heads
         ops = _Ops(plan, lay, T, R, H, layer.precision)
-        N, din, dout, dp = plan.N, layer.in_dim, layer.out_dim, lay.d_pad
+        N, E, din, dout, dp = plan.N, plan.E, layer.in_dim, layer.out_dim, lay.d_pad
         dev = x.device
         use_rte, use_norm = bool(layer.use_RTE), bool(layer.use_norm)
         dense = mid_w is not None
@@ -408,7 +408,7 @@ class _HGTConvTrain(torch.autograd.Function):
 
 def hgt_conv_train(layer, plan, x, packed, drop_p):
     """Training-mode forward of `layer` (HGTConv or DenseHGTConv) through the autograd Function.  `packed` =
-    layer._pack_parameters(grad=True); drop_p = dropout probability of conv.py:125 / 259,271 (0 in eval mode)."""
+    layer._pack_parameters(grad=True); drop_p = dropout probability of conv.py:125 / 261,273 (0 in eval mode)."""
     if plan.NQ != plan.N:
         raise NotImplementedError("pyhgt_amd: the backward pass covers single-GPU graphs (n_q_rows == n_nodes)")
     lay = packed["lay"]
@@ -426,7 +426,7 @@ def hgt_conv_train(layer, plan, x, packed, drop_p):
             draw = lambda: torch.zeros((plan.N, layer.out_dim), dtype=torch.float32, device=x.device)
         else:
             draw = lambda: torch.bernoulli(torch.full((plan.N, layer.out_dim), keep, dtype=torch.float32, device=x.device)) / keep
-        masks = (draw(), draw() if dense else None)          # DenseHGTConv drops twice (conv.py:259 and conv.py:271)
+        masks = (draw(), draw() if dense else None)          # DenseHGTConv drops twice (conv.py:261 and conv.py:273)
     return _HGTConvTrain.apply(layer, plan, masks, x, packed["w_qkv"], packed["b_qkv"], packed["w_a"], packed["b_a"], packed["ratt"],
                                packed["rmsg"], packed["rpri"], packed.get("skip"), packed.get("ln_w"), packed.get("ln_b"),
                                packed.get("rte_emb"), packed.get("rte_w"), packed.get("rte_b"), packed.get("mid_w"), packed.get("mid_b"),

@@ -1,7 +1,9 @@
 """GPU tests of the backward pass: gradients of pyhgt_amd.HGTConv / GNN w.r.t. the input and EVERY
 parameter of state_dict against oracle.backward_reference (reverse mode through the fp64 closed form, itself pinned against
 autograd through the verbatim reference in tests/test_oracle.py).  Tolerance: 2e-4 relative to the largest entry of each
-gradient tensor AND a per-entry atol + rtol bound (_grads_close)."""
+gradient tensor AND a per-entry atol + rtol bound (_grads_close).  Training mode is checked the same way with the dropout
+masks the forward drew (backward_reference(drop_masks=...)); graphs too large for the oracle are checked on a sample of target
+rows (sampled_backward_check).  The backward primitives one by one: tests/test_backward_kernels_gpu.py."""
 import ctypes as C
 
 import pytest
@@ -47,7 +49,7 @@ def _grads_close(name, got, ref, rtol=RTOL):
     return err
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3", "f16x3"])
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_hgtconv_backward_matches_oracle(case, precision):
     name, T, R, H, d, N, E, use_norm, use_RTE, gk, tw = case
@@ -91,7 +93,7 @@ DENSE_CASES = [
 ]
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3", "f16x3"])
 @pytest.mark.parametrize("case", DENSE_CASES, ids=[c[0] for c in DENSE_CASES])
 def test_dense_hgtconv_backward_matches_oracle(case, precision):
     """DenseHGTConv (conv.py:143-280): gradients of the input and of every parameter (a_linears, norms, mid_linear, out_linear,
@@ -242,14 +244,59 @@ def test_training_loop_reduces_the_loss(conv):
     assert sum(losses[-8:]) / 8 < 0.8 * sum(losses[:4]) / 4, (losses[:4], losses[-8:])
 
 
+def sampled_backward_check(layer, sd, graph, dims, use_norm, use_RTE, dense=False, n_random=150, seed=4, extra_targets=None,
+                           label=""):
+    """Forward + backward of `layer` (grad enabled: the training path, pyhgt_amd/autograd.py) on a whole device graph, checked
+    exactly on a sample: the loss weights only ~300 target rows (type-boundary tiles, first / last tile, max in-degree, random,
+    + extra_targets), so every gradient depends only on the sub-graph induced by ALL in-edges of those rows, where
+    oracle.backward_reference (fp64) is run; the sampled OUTPUT rows are compared the same way.  graph = (x, nt, ei, et, tm) on
+    the device, dims = (T, R, H, d)."""
+    from pyhgt_amd.synth import pick_check_targets, induced_in_neighbourhood
+    x, nt, ei, et, tm = graph
+    T, R, H, d = dims
+    N = x.size(0)
+    src, dst = ei[0], ei[1]
+    tg = pick_check_targets(nt, dst, n_random=n_random, tile=16, seed=seed)
+    if extra_targets is not None:
+        tg = torch.unique(torch.cat([tg, extra_targets.to(tg.device)]))
+    gout_rows = torch.randn(tg.numel(), d, generator=torch.Generator().manual_seed(6))
+    gout = torch.zeros(N, d, device=DEV)
+    gout[tg] = gout_rows.to(DEV)
+    GraphPlan.clear_cache()
+    xd = x.clone().requires_grad_(True)
+    out = layer(xd, nt, ei, et, tm if use_RTE else None)
+    out.backward(gout)
+    torch.cuda.synchronize()
+    xs, nts, eis, ets, tms, pos = induced_in_neighbourhood(x, nt, ei, et, tm if use_RTE else None, tg)
+    nodes = torch.unique(torch.cat([tg, src[torch.isin(dst, tg)]]))       # the sub-graph's node ids (sorted, like `pos`)
+    gsub = torch.zeros(xs.size(0), d)
+    gsub[pos] = gout_rows
+    fwd = O.forward_closed_form(sd, T, R, H, xs, nts, eis, ets, tms, use_norm=use_norm, use_RTE=use_RTE, dtype=torch.float64, dense=dense)
+    ferr = (out.detach()[tg].cpu().double() - fwd[pos]).abs().max().item()
+    assert ferr < 1e-4, ferr
+    ref = O.backward_reference(sd, T, R, H, xs, nts, eis, ets, tms, gsub, use_norm=use_norm, use_RTE=use_RTE, dense=dense)
+    worst = _grads_close("x[sub-graph]", xd.grad[nodes], ref["x"])
+    outside = torch.ones(N, dtype=torch.bool, device=DEV)
+    outside[nodes] = False
+    assert xd.grad[outside].abs().max().item() == 0.0                     # nothing else can receive gradient
+    for k, p in layer.named_parameters():
+        if k == "emb.emb.weight" and p.grad is None:
+            continue
+        assert p.grad is not None, k
+        worst = max(worst, _grads_close(k, p.grad, ref[k]))
+    print("sampled training path %s: %d sampled rows, %d sub-graph edges, forward err %.2e, worst gradient error %.2e" % (
+        label, tg.numel(), eis.size(1), ferr, worst))
+    del out, xd, gout
+    GraphPlan.clear_cache()
+    torch.cuda.empty_cache()
+    return worst
+
+
 @pytest.mark.parametrize("precision", ["bf16x3"])
 def test_training_path_at_the_benchmark_size_sampled(precision):
     """The training forward + backward at BASELINE.json configs[1] ITSELF (1M nodes / 10M edges, d=256, H=8: the unfused
     forward kernels with kept intermediates, the transposed 10M-edge plan, the hub-free spmm passes at full occupancy --
-    sizes no small case reaches).  Checked exactly on a sample: the loss weights only ~300 target rows (type-boundary tiles,
-    first / last tile, max in-degree, random), so every gradient depends only on the sub-graph induced by ALL in-edges of
-    those rows, where oracle.backward_reference (fp64) is run; the sampled OUTPUT rows are compared the same way."""
-    from pyhgt_amd.synth import pick_check_targets, induced_in_neighbourhood
+    sizes no small case reaches), checked on a sample (sampled_backward_check)."""
     T, R, H, d, N, E = 4, 8, 8, 256, 1_000_000, 10_000_000
     g = torch.Generator(device=DEV).manual_seed(2024)
     nt = torch.randint(0, T, (N,), generator=g, device=DEV).sort().values
@@ -262,35 +309,124 @@ def test_training_path_at_the_benchmark_size_sampled(precision):
     layer = HGTConv(d, d, T, R, H, 0.2, True, False, precision=precision).eval()
     layer.load_state_dict(sd)
     layer = layer.to(DEV)
-    tg = pick_check_targets(nt, dst, n_random=150, tile=16, seed=4)
-    gout_rows = torch.randn(tg.numel(), d, generator=torch.Generator().manual_seed(6))
-    gout = torch.zeros(N, d, device=DEV)
-    gout[tg] = gout_rows.to(DEV)
+    sampled_backward_check(layer, sd, (x, nt, ei, et, None), (T, R, H, d), True, False, label="at c2 size (%s)" % precision)
+
+
+def _mid_graph(N, E, T, R, d, seed, sorted_types=True, unknown=False, hubs=False, unclaimed=False):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    nt = torch.randint(0, T, (N,), generator=g, device=DEV)
+    if sorted_types:
+        nt = nt.sort().values
+    if unknown:
+        nt[::37] = -1
+        nt[5::41] = T + 1
+    x = torch.randn(N, d, generator=g, device=DEV)
+    src = torch.randint(0, N, (E,), generator=g, device=DEV)
+    dst = torch.randint(0, N, (E,), generator=g, device=DEV)
+    et = torch.randint(0, R, (E,), generator=g, device=DEV)
+    tm = torch.randint(0, 240, (E,), generator=g, device=DEV)
+    if unclaimed:
+        et[::29] = R
+    if hubs:
+        dst[:1500] = 17                    # > 1024 in-edges: hub target of the plan
+        src[2000:3600] = 23                # > 1024 out-edges: hub target of the transposed plan
+    ei = torch.stack([src, dst], dim=1).t()
+    return x, nt, ei, et, tm
+
+
+def _max_items(N, E, T, R):
+    sz = _lib.HgtPlanSizes()
+    assert _lib.load().hgt_plan_sizes_for(N, E, T, R, C.byref(sz)) == 0
+    return int(sz.max_items)
+
+
+MID_CASES = [
+    # name, conv, T, R, H, d, N, E, use_norm, use_RTE, graph kwargs, expected (rows per wavefront, outer items factor, gather kernel)
+    ("mid_60k", "hgt", 4, 40, 8, 256, 60000, 500000, True, False, {}, (8, 16, "items")),
+    ("mid_120k_rte_hubs", "hgt", 4, 8, 8, 256, 120000, 1200000, True, True, dict(sorted_types=False, unknown=True, hubs=True, unclaimed=True),
+     (32, 2, "sub_tile")),
+    ("mid_120k_rte_hubs_no_norm", "hgt", 4, 8, 8, 256, 120000, 1200000, False, True,
+     dict(sorted_types=False, unknown=True, hubs=True, unclaimed=True), (32, 2, "sub_tile")),
+    ("dense_70k", "dense", 3, 5, 4, 128, 70000, 500000, True, True, dict(unknown=True, unclaimed=True), (32, 2, "sub_tile")),
+]
+
+
+@pytest.mark.parametrize("case", MID_CASES, ids=[c[0] for c in MID_CASES])
+def test_training_path_mid_size_sampled(case):
+    """The default precision ("f16x3") training path between the small oracle cases and the 1M case: the size branches of the
+    backward kernels that only depend on the graph size, each asserted here so that a retuned threshold fails loudly."""
+    from pyhgt_amd import DenseHGTConv
+    name, conv, T, R, H, d, N, E, use_norm, use_RTE, gk, (rpw, ipw, gather) = case
+    # the branch predicates: hgt_backward.hip:695 (rows per wavefront), hgt_backward.hip:656 (relation-outer items), autograd.py:139
+    assert (32 if N >= 65536 else (8 if N >= 16384 else 2)) == rpw
+    assert (2 if _max_items(N, E, T, R) < 16384 else 16) == ipw
+    assert ("items" if (N < 65536 and R < 64) else "sub_tile") == gather
+    graph = _mid_graph(N, E, T, R, d, seed=N + R, **gk)
+    sd = O.make_state_dict(d, d, T, R, H, use_norm, use_RTE, seed=13, dense=conv == "dense")
+    cls = DenseHGTConv if conv == "dense" else HGTConv
+    layer = cls(d, d, T, R, H, 0.2, use_norm, use_RTE).eval()
+    assert layer.precision == "f16x3"
+    layer.load_state_dict(sd)
+    layer = layer.to(DEV)
+    extra = graph[2][1, 2000:2004] if gk.get("hubs") else None          # targets fed by the hub source: its dK / dV are checked
+    sampled_backward_check(layer, sd, graph, (T, R, H, d), use_norm, use_RTE, dense=conv == "dense", extra_targets=extra, label=name)
+
+
+@pytest.mark.parametrize("p", [0.2, 1.0])
+@pytest.mark.parametrize("conv", ["hgt", "dense"])
+def test_dropout_gradients_match_the_oracle_with_the_drawn_masks(conv, p, monkeypatch):
+    """Training mode (model.train(), dropout p): the masks the forward draws are captured at torch.bernoulli and replayed in
+    oracle.backward_reference(drop_masks=...) -- HGTConv drops the a_linear output (conv.py:125), DenseHGTConv the a_linear
+    output (conv.py:261) and the out_linear output (conv.py:273).  p = 1 draws no random numbers: both masks are zero."""
+    from pyhgt_amd import DenseHGTConv
+    dense = conv == "dense"
+    T, R, H, d, N, E = 3, 4, 4, 64, 2000, 10000
+    # HGTConv at p = 1 without LayerNorm: with o = 0 the normalised row LN(x (1 - a)) no longer depends on the gate a, so d skip
+    # is a sum of O(1) terms that cancel to ~1e-3 (fp32 rounding of the cancellation, not a property of the kernels)
+    use_norm = dense or p < 1.0
+    sd = O.make_state_dict(d, d, T, R, H, use_norm, True, seed=51, dense=dense)
+    x, nt, ei, et, tm = synthetic_typed_graph(N, E, d, T, R, seed=52, sorted_types=False)
+    nt = nt.clone()
+    nt[::17] = T + 1
+    layer = (DenseHGTConv if dense else HGTConv)(d, d, T, R, H, p, use_norm, True, keep_att=True)
+    layer.load_state_dict(sd)
+    layer = layer.to(DEV).train()
+    drawn = []
+    real_bernoulli = torch.bernoulli
+
+    def recording_bernoulli(*a, **k):
+        out = real_bernoulli(*a, **k)
+        drawn.append(out.clone())
+        return out
+
+    monkeypatch.setattr(torch, "bernoulli", recording_bernoulli)
+    gout = torch.randn(N, d, generator=torch.Generator().manual_seed(53))
+    xd = x.to(DEV).requires_grad_(True)
     GraphPlan.clear_cache()
-    xd = x.clone().requires_grad_(True)
-    out = layer(xd, nt, ei, et)                      # grad enabled: the training path (pyhgt_amd/autograd.py)
-    out.backward(gout)
+    out = layer(xd, nt.to(DEV), ei.to(DEV), et.to(DEV), tm.to(DEV))
+    out.backward(gout.to(DEV))
     torch.cuda.synchronize()
-    xs, nts, eis, ets, _, pos = induced_in_neighbourhood(x, nt, ei, et, None, tg)
-    nodes = torch.unique(torch.cat([tg, src[torch.isin(dst, tg)]]))       # the sub-graph's node ids (sorted, like `pos`)
-    gsub = torch.zeros(xs.size(0), d)
-    gsub[pos] = gout_rows
-    fwd = O.forward_closed_form(sd, T, R, H, xs, nts, eis, ets, None, use_norm=True, use_RTE=False, dtype=torch.float64)
-    ferr = (out.detach()[tg].cpu().double() - fwd[pos]).abs().max().item()
-    assert ferr < 1e-4, ferr
-    ref = O.backward_reference(sd, T, R, H, xs, nts, eis, ets, None, gsub, use_norm=True, use_RTE=False)
-    worst = _grads_close("x[sub-graph]", xd.grad[nodes], ref["x"])
-    outside = torch.ones(N, dtype=torch.bool, device=DEV)
-    outside[nodes] = False
-    assert xd.grad[outside].abs().max().item() == 0.0                     # nothing else can receive gradient
-    for k, p in layer.named_parameters():
-        assert p.grad is not None, k
-        worst = max(worst, _grads_close(k, p.grad, ref[k]))
-    print("training path at c2 size (%s): %d sampled rows, %d sub-graph edges, forward err %.2e, worst gradient error %.2e" % (
-        precision, tg.numel(), eis.size(1), ferr, worst))
-    del out, xd, gout
-    GraphPlan.clear_cache()
-    torch.cuda.empty_cache()
+    monkeypatch.undo()
+    n_masks = 2 if dense else 1
+    if p < 1.0:
+        assert len(drawn) == n_masks
+        masks = [(m / (1.0 - p)).cpu() for m in drawn]         # the expression of pyhgt_amd/autograd.py
+        assert all(0.75 < float((m != 0).float().mean()) < 0.85 for m in masks)          # keep probability 0.8
+    else:
+        assert len(drawn) == 0
+        masks = [torch.zeros(N, d) for _ in range(n_masks)]
+    dm = (masks[0], masks[1] if dense else None)
+    fwd, att = O.forward_closed_form(sd, T, R, H, x, nt, ei, et, tm, use_norm=use_norm, dense=dense, drop_masks=dm, return_att=True)
+    assert (out.detach().cpu().double() - fwd).abs().max().item() < 1e-4
+    assert layer.att is not None and (layer.att.cpu().double() - att).abs().max().item() < 1e-5      # keep_att under grad
+    ref = O.backward_reference(sd, T, R, H, x, nt, ei, et, tm, gout, use_norm=use_norm, dense=dense, drop_masks=dm)
+    worst = _grads_close("x", xd.grad, ref["x"])
+    for k, prm in layer.named_parameters():
+        if k == "emb.emb.weight" and prm.grad is None:
+            continue
+        assert prm.grad is not None, k
+        worst = max(worst, _grads_close(k, prm.grad, ref[k]))
+    print("dropout %s p=%.1f: worst relative gradient error %.2e" % (conv, p, worst))
 
 
 @pytest.mark.parametrize("d,H,R,rte", [(256, 8, 9, True), (512, 8, 5, False), (64, 4, 4, True), (400, 8, 33, True)])

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import hgt_oracle as O
-from oracle.gen_golden_ref import BACKWARD, LIVE_CONV
+from oracle.gen_golden_ref import BACKWARD, BACKWARD_DROPOUT, LIVE_CONV, dropout_masks
 from pyhgt_amd.synth import synthetic_typed_graph
 
 REF_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref")
@@ -110,6 +110,38 @@ def test_backward_oracle_matches_autograd_through_the_live_reference(dense):
     assert len(names) == len(sd)                # every parameter of the reference layer had a gradient
     for name in names:
         assert close(torch.from_numpy(z["param::" + name]), got[name]), name
+
+
+@pytest.mark.parametrize("dense", [False, True])
+def test_dropout_masks_sit_where_the_reference_drops(dense):
+    """Training mode: oracle.backward_reference(drop_masks=(m1, m2)) against autograd through the verbatim reference layer whose
+    nn.Dropout was replaced by multiplication with the same fixed masks (tests/golden/ref/ref_backward_dropout_*.npz,
+    oracle/gen_golden_ref.py) -- pins m1 to conv.py:125 (HGTConv) / conv.py:261 (DenseHGTConv) and m2 to conv.py:273."""
+    z = np.load(os.path.join(REF_DIR, "ref_backward_dropout_%s.npz" % ("dense" if dense else "hgt")))
+    b = BACKWARD_DROPOUT
+    T, R, H, d, N, E = b["T"], b["R"], b["H"], b["d"], b["N"], b["E"]
+    sd = O.make_state_dict(d, d, T, R, H, True, True, seed=b["param_seed"], dense=dense)
+    x, nt, ei, et, tm = synthetic_typed_graph(N, E, d, T, R, seed=b["graph_seed"])
+    g = torch.randn(N, d, generator=torch.Generator().manual_seed(b["g_seed"]))
+    m1, m2 = dropout_masks(b, dense)
+    assert torch.equal(m1, torch.from_numpy(z["mask1"])) and (not dense or torch.equal(m2, torch.from_numpy(z["mask2"])))
+    assert 0 < int((m1 == 0).sum()) < m1.numel()
+    out = O.forward_closed_form(sd, T, R, H, x, nt, ei, et, tm, dense=dense, drop_masks=(m1, m2))
+    assert (out - torch.from_numpy(z["out"]).double()).abs().max().item() < TOL
+    got = O.backward_reference(sd, T, R, H, x, nt, ei, et, tm, g, dense=dense, drop_masks=(m1, m2))
+
+    def close(a, b):
+        return (a.double() - b.double()).abs().max().item() <= 2e-4 * max(1.0, b.abs().max().item())
+    assert close(torch.from_numpy(z["x"]), got["x"])
+    names = [k[len("param::"):] for k in z.files if k.startswith("param::")]
+    assert len(names) == len(sd)
+    for name in names:
+        assert close(torch.from_numpy(z["param::" + name]), got[name]), name
+    # the eval-mode oracle (no masks) is far from these numbers: the fixture really depends on where the masks sit
+    assert not close(torch.from_numpy(z["x"]), O.backward_reference(sd, T, R, H, x, nt, ei, et, tm, g, dense=dense)["x"])
+    if dense:                               # ... and swapping the two Dense masks is caught too
+        swapped = O.backward_reference(sd, T, R, H, x, nt, ei, et, tm, g, dense=True, drop_masks=(m2, m1))
+        assert not all(close(torch.from_numpy(z["param::" + n]), swapped[n]) for n in names)
 
 
 @pytest.mark.parametrize("name", ["gnn_oag2", "gnn_mag4"])
