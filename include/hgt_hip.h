@@ -329,6 +329,13 @@ int hgt_edge_aggregate_slice(const void* plan, int64_t n_nodes, int64_t n_edges,
                              const float* msg_p, const void* msg_frag, float* agg, int64_t n_q_rows, int32_t apply_gelu,
                              void* hub_ws, int32_t rel_lo, int32_t rel_hi, float* state, int32_t has_prev, int32_t more,
                              void* stream);
+/* hgt_edge_aggregate_slice with hub_deterministic != 0: the hub targets (last slice) take the deterministic hub mode of
+ * HGT_FLAG_DETERMINISTIC_HUBS (hub_ws of hgt_hub_workspace_bytes_ex(.., deterministic = 1) bytes); hgt_conv_forward stage 4 uses it */
+int hgt_edge_aggregate_slice_ex(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations,
+                                int32_t n_heads, int32_t dk_pad, const float* logits, const float* V, const float* rte_v,
+                                const float* msg_p, const void* msg_frag, float* agg, int64_t n_q_rows, int32_t apply_gelu,
+                                void* hub_ws, int32_t rel_lo, int32_t rel_hi, float* state, int32_t has_prev, int32_t more,
+                                int32_t hub_deterministic, void* stream);
 /* msg_frag (ABI 3): hgt_relation_frag_pack(msg_p) = the relation message matrices as bf16 hi/mid MFMA fragments.  Non-NULL:
  * the per-(target, relation) transforms  (sum att_e v_e) M[rel]  run on the matrix cores, 16 targets x one relation at a time,
  * as 3-term split-bf16 products with fp32 accumulation (relative error of a product <= ~3*2^-18, like the split-bf16 typed
@@ -623,6 +630,7 @@ typedef struct hgt_conv_args {
                                       * (hub, relation) range writes its partial row / exp-sum to its own slot and the finalize kernel sums
                                       * the slots in (relation, piece) order, so two forwards are bit-identical on every row (the default
                                       * hub path adds fp32 partials atomically: hub rows then differ in the last bits from run to run).
+                                      * Every edge phase honours it: whole-layer calls and stages 3, 4 (source buckets) and 5.
                                       * Costs workspace: hgt_conv_workspace_bytes_ex(options bit 1) */
 
 /* phase boundaries at which hgt_conv_forward records phase_events[i]:

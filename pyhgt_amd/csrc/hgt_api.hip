@@ -518,8 +518,8 @@ edge_phase:
     if (rc != HGT_ERR_UNSUPPORTED) {
         // (done, or a real error)
     } else if (sliced) {
-        rc = hgt_edge_aggregate_slice(a->plan, N, E, T, R, H, lay.dk_pad, logits, V, rte_v, msg_p, msg_f, agg, NQ, 1, hub_ws, sl_lo, sl_hi,
-                                      (float*)(wb + w.off_state), sl_lo > 0, sl_more, stream);
+        rc = hgt_edge_aggregate_slice_ex(a->plan, N, E, T, R, H, lay.dk_pad, logits, V, rte_v, msg_p, msg_f, agg, NQ, 1, hub_ws, sl_lo,
+                                         sl_hi, (float*)(wb + w.off_state), sl_lo > 0, sl_more, det_hubs ? 1 : 0, stream);
         if (rc != HGT_OK || sl_more) return rc;      // state + un-normalised rows stay in the workspace for the next slice
     } else {
         rc = hgt_edge_aggregate_ex(a->plan, N, E, T, R, H, lay.dk_pad, logits, V, rte_v, msg_p, msg_f, (f16 && msg_f) ? 1 : 0, agg, NQ,

@@ -1359,10 +1359,12 @@ extern "C" int hgt_edge_aggregate_ex(const void* plan, int64_t N, int64_t E, int
 }
 
 // One slice [rel_lo, rel_hi) of the relation buckets (include/hgt_hip.h): matrix-core kernel only (msg_frag required).
-extern "C" int hgt_edge_aggregate_slice(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
-                                        const float* logits, const float* V, const float* rte_v, const float* msg_p,
-                                        const void* msg_frag, float* agg, int64_t n_q_rows, int32_t apply_gelu, void* hub_ws,
-                                        int32_t rel_lo, int32_t rel_hi, float* state, int32_t has_prev, int32_t more, void* stream) {
+// hub_deterministic != 0: the hub targets of the last slice are accumulated without atomics (hub_ws of hgt_hub_workspace_bytes_ex(.., 1))
+extern "C" int hgt_edge_aggregate_slice_ex(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
+                                           const float* logits, const float* V, const float* rte_v, const float* msg_p,
+                                           const void* msg_frag, float* agg, int64_t n_q_rows, int32_t apply_gelu, void* hub_ws,
+                                           int32_t rel_lo, int32_t rel_hi, float* state, int32_t has_prev, int32_t more,
+                                           int32_t hub_deterministic, void* stream) {
     if (!plan || !V || !msg_p || !msg_frag || !agg || !state || (E > 0 && !logits) || H <= 0 || 64 % H != 0 || dk_pad <= 0)
         return HGT_ERR_INVALID_ARG;
     if (rel_lo < 0 || rel_hi > R + 1 || rel_lo > rel_hi) return HGT_ERR_INVALID_ARG;
@@ -1371,7 +1373,7 @@ extern "C" int hgt_edge_aggregate_slice(const void* plan, int64_t N, int64_t E, 
     const int lph = 64 / H;
     if (dk_pad % lph != 0) return HGT_ERR_INVALID_ARG;
     HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
-    HgtHubBuffers hb = carve_hub(hub_ws, pv, H, E);
+    HgtHubBuffers hb = carve_hub(hub_ws, pv, H, E, dk_pad, R, hub_deterministic != 0);
     const HgtRelSlice sl = {(int)rel_lo, (int)rel_hi, state, has_prev ? 1 : 0, more ? 1 : 0};
     const int sp = mfma_split_for(dk_pad / lph, lph);
     if (sp == 0) return HGT_ERR_UNSUPPORTED;
@@ -1380,6 +1382,13 @@ extern "C" int hgt_edge_aggregate_slice(const void* plan, int64_t N, int64_t E, 
     if (rc != HGT_OK) return rc;
     HGT_CHECK_LAUNCH();
     return HGT_OK;
+}
+extern "C" int hgt_edge_aggregate_slice(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
+                                        const float* logits, const float* V, const float* rte_v, const float* msg_p,
+                                        const void* msg_frag, float* agg, int64_t n_q_rows, int32_t apply_gelu, void* hub_ws,
+                                        int32_t rel_lo, int32_t rel_hi, float* state, int32_t has_prev, int32_t more, void* stream) {
+    return hgt_edge_aggregate_slice_ex(plan, N, E, T, R, H, dk_pad, logits, V, rte_v, msg_p, msg_frag, agg, n_q_rows, apply_gelu, hub_ws,
+                                       rel_lo, rel_hi, state, has_prev, more, 0, stream);
 }
 
 static int edge_aggregate_update_impl(bool f16, const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,

@@ -249,3 +249,66 @@ def test_target_blocked_halo_chunks_over_gloo(world, case, n_blocks, tmp_path):
     mp.spawn(_worker_blocked, args=(world, port, case, n_blocks, str(tmp_path)), nprocs=world, join=True)
     for r in range(world):
         assert os.path.isfile(os.path.join(str(tmp_path), "ok%d.pt" % r))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# HaloPlan(emulate=...): one process plays any rank without a process group (bench.py --emulate-world, the one-GPU parity tests
+# of all ranks of a partition).  Its receive side must be the negotiated one, field for field.
+# ---------------------------------------------------------------------------------------------------------------------
+_RECV_FIELDS = ("need", "halo_order", "halo_chunk", "src_local", "halo_types", "node_type_local")
+_RECV_LISTS = ("recv_splits", "recv_chunk_off", "recv_chunk_splits")
+
+
+def _worker_emulate(rank, world, port, kind, case, n_chunks, tmpdir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from pyhgt_amd.dist import HaloPlan, partition, target_blocks
+        torch.set_num_threads(2)
+        if kind == "slices":      # the graph of _worker: equal-slice chunks of the pipelined / bucketed schedules
+            N, E, d, T, R = 600, 5000, 32, 3, 4
+            x, nt, ei, et, tm = synthetic_typed_graph(N, E, d, T, R, seed=77, sorted_types=False)
+            offsets = [round(r * N / world) for r in range(world + 1)]
+        else:                     # the graphs of _worker_blocked: first-use chunks of the blocked schedule
+            N, E, d, T, R = 960, 9000, 16, 3, 4
+            x, nt, ei, et, tm = _blocked_graph(case, N, E, d, T, R, world)
+            offsets = [r * (N // world) for r in range(world)] + [N]
+        nt = nt.clone()
+        nt[::23] = T              # nodes of no known type travel as halo rows too
+        sh = partition(nt, ei, et, tm, world, rank, node_offsets=offsets)
+        lo, hi = offsets[rank], offsets[rank + 1]
+        eblock = None
+        if kind == "blocked":
+            bounds = target_blocks(sh["dst_local"], hi - lo, n_chunks, align=16)
+            eblock = torch.searchsorted(torch.tensor(bounds[1:]), sh["dst_local"], right=True).clamp(max=n_chunks - 1)
+        real = HaloPlan(sh["node_type_own"], sh["src_global"], offsets, rank, world, n_chunks=n_chunks, edge_block=eblock)
+        emu = HaloPlan(sh["node_type_own"], sh["src_global"], offsets, rank, world, n_chunks=n_chunks, edge_block=eblock,
+                       emulate={"node_type_global": nt})
+        assert real.n_halo > 0 or (case == "island" and rank == world - 1)
+        assert (emu.n_own, emu.n_halo, emu.n_local, emu.n_chunks) == (real.n_own, real.n_halo, real.n_local, real.n_chunks)
+        for f in _RECV_FIELDS:
+            a, b = getattr(real, f), getattr(emu, f)
+            assert a.dtype == b.dtype and torch.equal(a, b), f
+        for f in _RECV_LISTS:
+            assert list(getattr(real, f)) == list(getattr(emu, f)), f
+        for (ra, oa), (rb, ob) in zip(real.chunk_row_lists(T), emu.chunk_row_lists(T)):
+            assert torch.equal(ra, rb) and torch.equal(oa, ob)
+        # the mirrored send side packs local rows of this rank only
+        assert emu.n_halo == 0 or (int(emu.send_rows.min()) >= 0 and int(emu.send_rows.max()) < hi - lo)
+        torch.save(torch.tensor([real.n_halo]), os.path.join(tmpdir, "ok%d.pt" % rank))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world,kind,case,n_chunks", [(2, "slices", None, 1), (3, "slices", None, 4), (4, "slices", None, 7),
+                                                      (3, "blocked", "uniform", 5), (4, "blocked", "island", 4),
+                                                      (4, "blocked", "front", 8), (8, "blocked", "uniform", 8)])
+def test_emulated_halo_plan_equals_the_negotiated_one(world, kind, case, n_chunks, tmp_path):
+    """HaloPlan(emulate={"node_type_global": ...}) builds a rank's receive side from the global graph alone.  On the graphs the
+    gloo workers above negotiate (equal-slice chunks; first-use chunks of target blocks, with a rank without halo rows and
+    dead chunks), every receive-side field of every rank must equal what the four all-to-alls produce."""
+    port = _free_port()
+    mp.spawn(_worker_emulate, args=(world, port, kind, case, n_chunks, str(tmp_path)), nprocs=world, join=True)
+    for r in range(world):
+        assert os.path.isfile(os.path.join(str(tmp_path), "ok%d.pt" % r))

@@ -4,6 +4,7 @@
 Tolerance: 1e-4 absolute on fp32 outputs (BASELINE.json north_star); integer plan data bit-exact."""
 import ctypes as C
 import os
+import time
 
 import numpy as np
 import pytest
@@ -2227,3 +2228,317 @@ def test_c24_pack_of_256_column_rows_is_bit_exact(n):
     assert lib.hgt_unpack_rows_c24(wire.data_ptr(), n, d, back.data_ptr(), d, st) == 0
     torch.cuda.synchronize()
     assert ((back - x[idx.long()]).abs() <= x[idx.long()].abs() * 2.0 ** -16 * 1.0001).all()
+
+
+# ------------------------------------------------------------------ BASELINE.json configs[3] at its own size, one rank after the other
+C3_T, C3_R, C3_H, C3_D, C3_W, C3_NL, C3_EL = 4, 8, 8, 256, 8, 1_000_000, 10_000_000
+FOUR_GIB_ROW = (1 << 32) // (C3_D * 4)        # 4 194 304: from this node on, a row of Q / K / V sits >= 4 GiB from its table's base
+
+
+def _fp64_on_device(sd, T, R, H, x, nt, ei, et, tm=None, use_rte=False):
+    """O.forward_closed_form in float64 with torch's operators on the device (the graphs of the tests below are too large for the
+    host in float64).  Deterministic algorithms: index_add_ then sums the in-edges of a row by sorting instead of with float64
+    atomics, which serialise on the hub rows of the skewed graph (630k in-edges on one row: minutes otherwise)."""
+    was, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        with torch.device(DEV):
+            return O.forward_closed_form({k: v.to(DEV) for k, v in sd.items()}, T, R, H, x.to(DEV), nt.to(DEV), ei.to(DEV),
+                                         et.to(DEV), None if tm is None else tm.to(DEV), use_norm=True, use_RTE=use_rte,
+                                         dtype=torch.float64)
+    finally:
+        torch.use_deterministic_algorithms(was, warn_only=warn)
+
+
+def _fp64_rows(sd, g, targets, x_sub_of=None, max_edges=1 << 21):
+    """Exact float64 outputs of the rows `targets` (sorted, on the device) of the graph g: the closed form on the sub-graph of ALL
+    their in-edges (pyhgt_amd.synth.induced_in_neighbourhood, exact for those rows), in groups of consecutive rows cut where the
+    running in-edge count crosses a multiple of max_edges (bounds the float64 temporaries).  x_sub_of(node_ids) -> the feature rows the kernel under test computes from (default g["x"][node_ids])."""
+    from pyhgt_amd.synth import induced_in_neighbourhood
+    grp = torch.div(torch.cumsum(g["deg"][targets], 0), max_edges, rounding_mode="floor")
+    out = torch.empty(targets.numel(), g["d"], dtype=torch.float64, device=DEV)
+    for gv in torch.unique(grp).tolist():
+        sel = (grp == gv).nonzero().flatten()
+        ids, nts, eis, ets, _, pos = induced_in_neighbourhood(g["ids"], g["nt"], g["ei"], g["et"], None, targets[sel])
+        ids = ids.flatten().to(DEV)
+        xs = g["x"][ids] if x_sub_of is None else x_sub_of(ids)
+        out[sel] = _fp64_on_device(sd, g["T"], g["R"], g["H"], xs, nts, eis, ets)[pos.to(DEV)]
+    return out
+
+
+def _c24_outside(x, lo, hi):
+    """x_sub_of for a rank [lo, hi) with the 24-bit exchange: every row it receives went through the wire format."""
+    def f(ids):
+        rows = x[ids].contiguous()
+        own = ((ids >= lo) & (ids < hi)).unsqueeze(1)
+        return torch.where(own, rows, _c24_round_trip(rows))
+    return f
+
+
+def _partitioned_forward(pg, layer, x_own, flags, compress, poison):
+    """One PartitionedGraph forward with the given kernel flags and halo format.  poison: the halo rows of x_local are NaN and the
+    workspace is all 0xFF bytes (NaN) beforehand -- a halo row or K|V row read before it is received / projected, or a reliance on a
+    zeroed workspace, makes NaN outputs."""
+    layer.kernel_flags = flags
+    pg.compress = compress
+    if poison:
+        if pg.x_local is None or pg.x_local.size(1) != x_own.size(1):
+            pg.x_local = torch.empty(pg.n_local, x_own.size(1), device=DEV)
+        pg.x_local.fill_(float("nan"))
+        need = layer.workspace_bytes(pg.n_local, pg.plan.E, pg.n_buckets if pg.layer_mode(layer) == "bucketed" else 1)
+        if pg.workspace is None or pg.workspace.numel() < need:
+            pg.workspace = None
+            pg.workspace = torch.empty(need, dtype=torch.uint8, device=DEV)
+        pg.workspace.fill_(0xFF)
+    with torch.no_grad():
+        out = pg.forward(layer, x_own)
+    torch.cuda.synchronize()
+    bad = ~torch.isfinite(out).all(dim=1)
+    assert not bool(bad.any()), "%s schedule, rank %d: %d non-finite output rows, the first is row %d" % (
+        pg.layer_mode(layer), pg.halo.rank, int(bad.sum()), int(bad.nonzero()[0]))
+    return out
+
+
+@pytest.fixture(scope="module", params=["uniform", "skew"])
+def c3_graph(request):
+    """The configs[3] graph (bench.py:configs3_share's recipe, global tensors kept): 8 natural blocks of 1M nodes / 10M edges, node
+    types sorted within each block, uniform sources and targets ("uniform") or targets of Zipf skew 0.8 with 3/4 of the sources from
+    the target's own block ("skew", the DESIGN.md section 6 variant: hub targets inside the ranks); its in-edge-balanced partition
+    over 8 ranks with 8 target blocks per rank; ~14k check rows and their float64 outputs."""
+    from pyhgt_amd.dist import partition, partition_offsets, target_blocks
+    from pyhgt_amd.synth import pick_check_targets
+    from pyhgt_amd.conv import _Workspace
+    if torch.cuda.get_device_properties(0).total_memory < (128 << 30):
+        pytest.skip("the 8M-node configs[3] graph needs a GPU with 128 GiB or more")
+    t0 = time.time()
+    skew, locality = (0.0, 0.0) if request.param == "uniform" else (0.8, 0.75)
+    T, R, H, d, W, Nl, El = C3_T, C3_R, C3_H, C3_D, C3_W, C3_NL, C3_EL
+    N, E = W * Nl, W * El
+    gg = torch.Generator(device=DEV).manual_seed(1234)
+    nt = torch.randint(0, T, (W, Nl), generator=gg, device=DEV).sort(dim=1).values.reshape(-1)
+    dst = torch.randint(0, N, (E,), generator=gg, device=DEV)
+    if skew > 0.0:
+        u = torch.rand(E, generator=gg, device=DEV)
+        dst = (dst // Nl) * Nl + (Nl * u ** (1.0 / (1.0 - skew))).long().clamp(0, Nl - 1)
+        del u
+    src = torch.randint(0, N, (E,), generator=gg, device=DEV)
+    if locality > 0.0:
+        near = torch.rand(E, generator=gg, device=DEV) < locality
+        src = torch.where(near, (dst // Nl) * Nl + src % Nl, src)
+        del near
+    et = torch.randint(0, R, (E,), generator=gg, device=DEV)
+    ei = torch.stack([src, dst])
+    del src, dst
+    x = torch.randn(N, d, generator=torch.Generator(device=DEV).manual_seed(7), device=DEV)
+    g = dict(name=request.param, T=T, R=R, H=H, d=d, W=W, N=N, x=x, nt=nt, ei=ei, et=et, one_call={},
+             ids=torch.arange(N, device=DEV).unsqueeze(1), deg=torch.bincount(ei[1], minlength=N),
+             sd=O.make_state_dict(d, d, T, R, H, True, False, seed=33))
+    g["offsets"] = offsets = partition_offsets(ei[1], N, W)
+    g["shares"], cuts = [], []
+    for r in range(W):
+        sh = partition(nt, ei, et, None, W, r, node_offsets=offsets)
+        sh["edge_ids"] = None
+        sh["block_bounds"] = target_blocks(sh["dst_local"], offsets[r + 1] - offsets[r], 8)
+        cuts += [offsets[r] + b for b in sh["block_bounds"]]
+        g["shares"].append(sh)
+    # check rows: pick_check_targets, plus +-64 rows around EVERY type boundary (it stops at 16 of the 31), every rank cut, every
+    # target-block cut of every rank and the 4 GiB line
+    type_cuts = ((nt[1:] != nt[:-1]).nonzero().flatten() + 1).tolist()
+    assert len(type_cuts) == W * T - 1
+    rows = [pick_check_targets(nt, ei[1], n_random=1500, seed=3)]
+    for c in type_cuts + list(offsets) + cuts + [FOUR_GIB_ROW]:
+        rows.append(torch.arange(max(0, c - 64), min(N, c + 64), device=DEV))
+    g["tg"] = tg = torch.unique(torch.cat(rows))
+    # preconditions: K / V rows beyond 4 GiB, and many checked rows that gather them
+    assert (N - 1) * d * 4 >= 1 << 32
+    flag = torch.zeros(N, dtype=torch.bool, device=DEV)
+    flag[tg] = True
+    far = flag[ei[1]] & (ei[0] >= FOUR_GIB_ROW)
+    n_far = int(torch.unique(ei[1][far]).numel())
+    assert n_far >= 500, n_far
+    t1 = time.time()
+    g["ref"] = _fp64_rows(g["sd"], g, tg)
+    torch.cuda.synchronize()
+    t1 = time.time() - t1
+    print("\nconfigs[3] %s: N=%d E=%d, %d check rows (%d with a source >= node %d, %d in-edges), max in-degree %d, offsets %s, "
+          "set-up %.1f s (float64 rows %.1f s)" % (request.param, N, E, tg.numel(), n_far, FOUR_GIB_ROW, int(g["deg"][tg].sum()),
+                                                   int(g["deg"].max()), offsets, time.time() - t0, t1))
+    yield g
+    g.clear()
+    del x, nt, ei, et, tg, flag, far, rows
+    GraphPlan.clear_cache()
+    _Workspace.clear()
+    torch.cuda.empty_cache()
+
+
+def _c3_one_call(g, precision):
+    """HGTConv on the whole 8M-node graph (the output of "bf16x3" is kept for the stitched comparison)."""
+    if precision in g["one_call"]:
+        return g["one_call"][precision]
+    layer = _layer_from(g["sd"], g["d"], g["T"], g["R"], g["H"], True, False, keep_att=False, precision=precision)
+    with torch.no_grad():
+        out = layer(g["x"], g["nt"], g["ei"], g["et"])
+    torch.cuda.synchronize()
+    if precision == "bf16x3":
+        g["one_call"][precision] = out
+    return out
+
+
+@pytest.mark.parametrize("precision", ["f16x3", "bf16x3", "fp32"])
+def test_configs3_one_call_layer_against_fp64(c3_graph, precision):
+    """The one-call layer on 8M nodes / 80M edges: Q, K and V take 8.2 GB each, so every source >= node 4 194 304 is gathered from
+    beyond 4 GiB of its table's base (the 64-bit-offset instantiations of the logits and fused aggregation kernels), and the
+    x-stationary Q|K|V GEMM writes rows past 4 GiB.  Check rows vs float64, every row finite."""
+    g = c3_graph
+    t0 = time.time()
+    out = _c3_one_call(g, precision)
+    t1 = time.time()
+    err = (out[g["tg"]].double() - g["ref"]).abs().max().item()
+    finite = bool(torch.isfinite(out).all())
+    print("configs[3] %s one-call %s: max|err| %.2e over %d rows, %.1f s" % (g["name"], precision, err, g["tg"].numel(), t1 - t0))
+    del out
+    assert finite
+    assert err < PREC_TOL[precision]
+
+
+def test_configs3_eight_ranks_one_after_another(c3_graph):
+    """All 8 ranks of the configs[3] partition on ONE GPU, one after the other: HaloPlan(emulate=...) gives each rank its exact
+    receive side, the all-to-all is a copy out of the global feature table.  Before a first forward the halo rows of x_local are NaN
+    and the workspace is filled with 0xFF bytes (NaN), so a halo or K|V row read before it is received / projected, or a reliance on
+    a zeroed workspace, shows up.  Per rank: the target-blocked schedule (8 blocks, fp32 and 24-bit halo rows) vs float64, the
+    stitched output vs the one-call layer on ALL rows, a second forward bit for bit; rank 0 also: blocked == pipelined bit for bit
+    (deterministic hub mode), and the pipelined / source-bucketed schedules on 4 equal-slice chunks vs float64."""
+    from pyhgt_amd.dist import HaloPlan, PartitionedGraph
+    g = c3_graph
+    T, R, H, d, W, offsets, tg, x = g["T"], g["R"], g["H"], g["d"], g["W"], g["offsets"], g["tg"], g["x"]
+    one = _c3_one_call(g, "bf16x3")
+    layer = _layer_from(g["sd"], d, T, R, H, True, False, keep_att=False, precision="bf16x3")
+    det = _lib.HGT_FLAG_DETERMINISTIC_HUBS       # (the default hub path adds fp32 partials atomically: not bit-reproducible)
+
+    worst = dict(fp32=0.0, c24=0.0, default_hubs=0.0, stitched=0.0)
+    covered, hub_ranks = 0, 0
+    for r in range(W):
+        t0 = time.time()
+        sh = g["shares"][r]
+        lo, hi = offsets[r], offsets[r + 1]
+        bounds = sh["block_bounds"]
+        eblock = torch.searchsorted(torch.tensor(bounds[1:], device=DEV), sh["dst_local"], right=True).clamp(max=7)
+        hp = HaloPlan(sh["node_type_own"], sh["src_global"], offsets, r, W, n_chunks=8, edge_block=eblock,
+                      emulate={"node_type_global": g["nt"]})
+        del eblock
+        hp.exchange_chunk = _fake_exchange_for(hp, x)
+        pg = PartitionedGraph(None, None, sh["dst_local"], sh["edge_type"], None, T, R, 0, r, W, node_offsets=offsets, halo=hp,
+                              mode="blocked", n_chunks=8)
+        assert pg.layer_mode(layer) == "blocked" and pg.block_bounds == bounds and len(pg.blocks) == 8
+        hub_ranks += int(not pg.plan.no_hubs)
+        x_own = x[lo:hi]
+        sel = ((tg >= lo) & (tg < hi)).nonzero().flatten()
+        rows, ref = tg[sel] - lo, g["ref"][sel]
+
+        def err(out, ref=ref):
+            return (out[rows].double() - ref).abs().max().item()
+        out = _partitioned_forward(pg, layer, x_own, 0, False, True)          # the default hub path
+        e_def = err(out)
+        worst["default_hubs"] = max(worst["default_hubs"], e_def)
+        worst["stitched"] = max(worst["stitched"], (out - one[lo:hi]).abs().max().item())
+        covered += hi - lo
+        del out
+        out = _partitioned_forward(pg, layer, x_own, det, False, True)
+        assert torch.equal(out, _partitioned_forward(pg, layer, x_own, det, False, False)), "rank %d: a second forward differs" % r
+        e_det = err(out)
+        worst["fp32"] = max(worst["fp32"], e_det)
+        if r == 0:
+            pg.mode = "pipelined"                                             # the same fused kernel over the whole range
+            out_p = _partitioned_forward(pg, layer, x_own, det | _lib.HGT_FLAG_FUSED_ANY_SIZE, False, True)
+            pg.mode = "blocked"
+            assert torch.equal(out, out_p), "blocked and pipelined differ: max %.3e" % (out - out_p).abs().max().item()
+            del out_p
+        del out
+        ref_c24 = _fp64_rows(g["sd"], g, tg[sel], x_sub_of=_c24_outside(x, lo, hi))
+        out = _partitioned_forward(pg, layer, x_own, det, True, True)         # halo K|V straight off the 24-bit wire buffer
+        assert torch.equal(out, _partitioned_forward(pg, layer, x_own, det, True, False)), "rank %d (24-bit): a second forward differs" % r
+        e_c24 = err(out, ref_c24)
+        worst["c24"] = max(worst["c24"], e_c24)
+        del out
+        extra = ""
+        if r == 0:
+            hp4 = HaloPlan(sh["node_type_own"], sh["src_global"], offsets, r, W, n_chunks=4, emulate={"node_type_global": g["nt"]})
+            hp4.exchange_chunk = _fake_exchange_for(hp4, x)
+            pg4 = PartitionedGraph(None, None, sh["dst_local"], sh["edge_type"], None, T, R, 0, r, W, node_offsets=offsets, halo=hp4,
+                                   mode="bucketed", n_chunks=4)
+            assert pg4.layer_mode(layer) == "bucketed" and pg4.n_buckets * R < 64
+            out = _partitioned_forward(pg4, layer, x_own, det, False, True)
+            assert torch.equal(out, _partitioned_forward(pg4, layer, x_own, det, False, False)), "bucketed: a second forward differs"
+            e_b = err(out)
+            del out
+            pg4.mode = "pipelined"
+            e_p = err(_partitioned_forward(pg4, layer, x_own, 0, False, True))
+            extra = ", 4 chunks: bucketed %.2e, pipelined %.2e" % (e_b, e_p)
+            assert e_b < TOL and e_p < TOL
+            del pg4, hp4
+        print("configs[3] %s rank %d: n_own %d, n_halo %d, hubs %s, %d rows: max|err| blocked %.2e (default hubs %.2e), 24-bit %.2e%s; "
+              "%.1f s" % (g["name"], r, hi - lo, hp.n_halo, not pg.plan.no_hubs, rows.numel(), e_det, e_def,
+                          e_c24, extra, time.time() - t0))
+        del pg, hp
+    print("configs[3] %s: 8 ranks, max|err| vs float64 %.2e (24-bit halo %.2e), stitched vs one-call layer %.2e on all %d rows" % (
+        g["name"], max(worst["fp32"], worst["default_hubs"]), worst["c24"], worst["stitched"], covered))
+    assert covered == g["N"]
+    assert worst["fp32"] < TOL and worst["default_hubs"] < TOL and worst["c24"] < TOL
+    assert worst["stitched"] < TOL
+    if g["name"] == "skew":
+        assert hub_ranks > 0
+
+
+@pytest.mark.parametrize("d,use_rte", [(512, True), (400, False)])
+def test_partitioned_schedules_at_the_reference_widths(d, use_rte):
+    """n_hid 512 (ogbn-mag) and 400 (OAG: d_k 50 padded to 64): rows of 512 padded columns, wider than the target-blocked schedule
+    covers.  4 ranks of a 24k-node graph with a hub target, unclaimed edges and nodes of unknown type, played one after the other
+    (HaloPlan(emulate=...)), every schedule, fp32 and 24-bit halo rows: "blocked" must run the pipelined schedule; every rank's
+    output vs float64 on the whole graph (poisoned halo rows and workspace), a second forward bit for bit."""
+    from pyhgt_amd.dist import HaloPlan, PartitionedGraph, partition, partition_offsets, target_blocks
+    N, E, T, R, H, W, C = 24_000, 200_000, 3, 5, 8, 4, 4
+    x, nt, ei, et, tm = synthetic_typed_graph(N, E, d, T, R, seed=94, sorted_types=False, strided_edge_index=False, device=DEV)
+    ei[1, :2500] = 13_300               # a hub target (> 1024 in-edges)
+    et[::13] = R + 1                    # unclaimed edges
+    nt[::29] = T                        # nodes of no known type
+    tm = tm if use_rte else None
+    offsets = partition_offsets(ei[1], N, W)
+    sd = O.make_state_dict(d, d, T, R, H, True, use_rte, seed=95)
+    ref = _fp64_on_device(sd, T, R, H, x, nt, ei, et, tm, use_rte)
+    layer = _layer_from(sd, d, T, R, H, True, use_rte, keep_att=False, precision="bf16x3")
+    det = _lib.HGT_FLAG_DETERMINISTIC_HUBS
+    ref_c24, worst, hub_ranks = {}, {}, {}
+    for mode in ("blocked", "bucketed", "pipelined"):
+        for r in range(W):
+            sh = partition(nt, ei, et, tm, W, r, node_offsets=offsets)
+            lo, hi = offsets[r], offsets[r + 1]
+            eblock = None
+            if mode == "blocked":
+                bounds = target_blocks(sh["dst_local"], hi - lo, C)
+                eblock = torch.searchsorted(torch.tensor(bounds[1:], device=DEV), sh["dst_local"], right=True).clamp(max=C - 1)
+            hp = HaloPlan(sh["node_type_own"], sh["src_global"], offsets, r, W, n_chunks=C, edge_block=eblock,
+                          emulate={"node_type_global": nt})
+            assert hp.n_halo > 0
+            hp.exchange_chunk = _fake_exchange_for(hp, x)
+            pg = PartitionedGraph(None, None, sh["dst_local"], sh["edge_type"], sh["edge_time"], T, R, 0, r, W, node_offsets=offsets,
+                                  halo=hp, mode=mode, n_chunks=C)
+            assert pg.layer_mode(layer) == ("pipelined" if mode == "blocked" else mode)
+            hub_ranks[mode] = hub_ranks.get(mode, 0) + int(not (pg.bucket_plan or pg.plan).no_hubs)
+            for compress in (False, True):
+                out = _partitioned_forward(pg, layer, x[lo:hi], det, compress, True)
+                again = _partitioned_forward(pg, layer, x[lo:hi], det, compress, False)
+                assert torch.equal(out, again), "%s rank %d: a second forward differs by %.3e" % (
+                    mode, r, (out - again).abs().max().item())
+                if compress and r not in ref_c24:
+                    own = torch.zeros(N, 1, dtype=torch.bool, device=DEV)
+                    own[lo:hi] = True
+                    ref_c24[r] = _fp64_on_device(sd, T, R, H, torch.where(own, x, _c24_round_trip(x)), nt, ei, et, tm, use_rte)[lo:hi]
+                e = (out.double() - (ref_c24[r] if compress else ref[lo:hi])).abs().max().item()
+                key = (mode, compress)
+                worst[key] = max(worst.get(key, 0.0), e)
+            del pg, hp
+    for (mode, compress), e in worst.items():
+        print("d=%d H=%d rte=%s 4 ranks, %s%s: max|err| vs float64 %.2e" % (d, H, use_rte, mode, " 24-bit" if compress else "", e))
+    print("d=%d: ranks with hub targets per schedule %s" % (d, hub_ranks))
+    assert max(worst.values()) < TOL
+    assert all(n > 0 for n in hub_ranks.values())       # the deterministic hub mode ran in every schedule
