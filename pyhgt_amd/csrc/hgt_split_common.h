@@ -143,12 +143,25 @@ __device__ __forceinline__ unsigned abs_bits4(const float4 v) {
     return __builtin_bit_cast(unsigned, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
 }
 
-// tanh of the typed input adapter (model.py:74) as  1 - 2 / (e^(2x) + 1)  on the hardware exp2 / rcp (each ~1 ulp: |error| <= ~1.5e-7,
-// saturates to +-1 without a branch; libm's tanhf is ~40 instructions with two of them) -- one definition for the fused epilogues and
-// hgt_tanh_inplace, so that both forms of the adapter publish the same values
+// tanh of the typed input adapter (model.py:74), accurate in RELATIVE terms like torch.tanh (measured in tests/test_gnn_scale_gpu.py):
+// on |x|, the sign copied back at the end (so -0 stays -0):
+//   |x| <  0.25: the odd Taylor polynomial |x| - |x|^3 (1/3 - x^2 (2/15 - x^2 (17/315 - ...))) through x^11 (truncation < 3e-10
+//                relative), exact for tiny and subnormal x;
+//   |x| >= 0.25: (1 - s) / (1 + s) with s = e^(-2|x|) on the hardware exp2 / rcp (each ~1 ulp; 1 - s >= 0.39 keeps the subtraction free
+//                of cancellation), exactly 1 once s < 2^-25 and at inf, NaN stays NaN.
+// (The former 1 - 2 / (e^(2x) + 1) lost all relative accuracy as x -> 0.)  Branch-free; one definition for the fused epilogues and
+// hgt_tanh_inplace, so that both forms of the adapter publish the same values.
 __device__ __forceinline__ float hgt_tanh(float x) {
-    const float t = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);      // e^(2x) = 2^(2x log2 e)
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(t + 1.0f);
+    const float a = fabsf(x);
+    const float s = __builtin_amdgcn_exp2f(a * -2.8853900817779268f);     // e^(-2|x|) = 2^(-2|x| log2 e), in [0, 1]
+    const float big = (1.0f - s) * __builtin_amdgcn_rcpf(1.0f + s);
+    const float a2 = a * a;
+    float p = fmaf(a2, 8.8632355299021966e-3f, -2.1869488536155203e-2f);    // 1382/155925, -62/2835
+    p = fmaf(a2, p, 5.3968253968253968e-2f);                                 // 17/315
+    p = fmaf(a2, p, -1.3333333333333333e-1f);                                // -2/15
+    p = fmaf(a2, p, 3.3333333333333333e-1f);                                 // 1/3
+    const float small = fmaf(-a * a2, p, a);
+    return __builtin_copysignf(a < 0.25f ? small : big, x);
 }
 
 template <int CTRL>

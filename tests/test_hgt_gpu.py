@@ -2235,7 +2235,7 @@ C3_T, C3_R, C3_H, C3_D, C3_W, C3_NL, C3_EL = 4, 8, 8, 256, 8, 1_000_000, 10_000_
 FOUR_GIB_ROW = (1 << 32) // (C3_D * 4)        # 4 194 304: from this node on, a row of Q / K / V sits >= 4 GiB from its table's base
 
 
-def _fp64_on_device(sd, T, R, H, x, nt, ei, et, tm=None, use_rte=False):
+def _fp64_on_device(sd, T, R, H, x, nt, ei, et, tm=None, use_rte=False, use_norm=True):
     """O.forward_closed_form in float64 with torch's operators on the device (the graphs of the tests below are too large for the
     host in float64).  Deterministic algorithms: index_add_ then sums the in-edges of a row by sorting instead of with float64
     atomics, which serialise on the hub rows of the skewed graph (630k in-edges on one row: minutes otherwise)."""
@@ -2244,7 +2244,7 @@ def _fp64_on_device(sd, T, R, H, x, nt, ei, et, tm=None, use_rte=False):
     try:
         with torch.device(DEV):
             return O.forward_closed_form({k: v.to(DEV) for k, v in sd.items()}, T, R, H, x.to(DEV), nt.to(DEV), ei.to(DEV),
-                                         et.to(DEV), None if tm is None else tm.to(DEV), use_norm=True, use_RTE=use_rte,
+                                         et.to(DEV), None if tm is None else tm.to(DEV), use_norm=use_norm, use_RTE=use_rte,
                                          dtype=torch.float64)
     finally:
         torch.use_deterministic_algorithms(was, warn_only=warn)
@@ -2253,16 +2253,19 @@ def _fp64_on_device(sd, T, R, H, x, nt, ei, et, tm=None, use_rte=False):
 def _fp64_rows(sd, g, targets, x_sub_of=None, max_edges=1 << 21):
     """Exact float64 outputs of the rows `targets` (sorted, on the device) of the graph g: the closed form on the sub-graph of ALL
     their in-edges (pyhgt_amd.synth.induced_in_neighbourhood, exact for those rows), in groups of consecutive rows cut where the
-    running in-edge count crosses a multiple of max_edges (bounds the float64 temporaries).  x_sub_of(node_ids) -> the feature rows the kernel under test computes from (default g["x"][node_ids])."""
+    running in-edge count crosses a multiple of max_edges (bounds the float64 temporaries).  x_sub_of(node_ids) -> the feature rows the kernel under test computes from (default g["x"][node_ids]).
+    Optional keys of g: "tm" (edge times, with "use_rte": True) and "use_norm" (default True)."""
     from pyhgt_amd.synth import induced_in_neighbourhood
     grp = torch.div(torch.cumsum(g["deg"][targets], 0), max_edges, rounding_mode="floor")
     out = torch.empty(targets.numel(), g["d"], dtype=torch.float64, device=DEV)
+    use_rte = g.get("use_rte", False)
     for gv in torch.unique(grp).tolist():
         sel = (grp == gv).nonzero().flatten()
-        ids, nts, eis, ets, _, pos = induced_in_neighbourhood(g["ids"], g["nt"], g["ei"], g["et"], None, targets[sel])
+        ids, nts, eis, ets, tms, pos = induced_in_neighbourhood(g["ids"], g["nt"], g["ei"], g["et"], g["tm"] if use_rte else None,
+                                                                targets[sel])
         ids = ids.flatten().to(DEV)
         xs = g["x"][ids] if x_sub_of is None else x_sub_of(ids)
-        out[sel] = _fp64_on_device(sd, g["T"], g["R"], g["H"], xs, nts, eis, ets)[pos.to(DEV)]
+        out[sel] = _fp64_on_device(sd, g["T"], g["R"], g["H"], xs, nts, eis, ets, tms, use_rte, g.get("use_norm", True))[pos.to(DEV)]
     return out
 
 
