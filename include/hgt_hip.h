@@ -164,8 +164,11 @@ int hgt_plan_from_sorted(const int32_t* src, const int32_t* dst, const int32_t* 
 #define HGT_LINEAR_TANH 0x1000     /* ABI 7, split variants: tanh applied to the output (model.py:70-76: the GNN's typed adapter + tanh in one kernel).
                                     * Only the latency-regime tile kernel and the K > 256 slab kernel carry it: HGT_ERR_UNSUPPORTED otherwise (and
                                     * nothing launched) -> plain call + hgt_tanh_inplace */
-#define HGT_LINEAR_NO_TILE 0x400   /* ABI 7: never the latency-regime tile kernel (hgt_gemm_tile.hip; the default below 49 152 rows) -- it is
-                                    * bit-identical to the slab kernels; the bit exists for tests and A/B timings */
+#define HGT_LINEAR_NO_TILE 0x400   /* ABI 7: never the latency-regime tile kernel (hgt_gemm_tile.hip; the default for up to HGT_TILE_MAX_ROWS = 16 384
+                                    * rows and at most 64 groups: K <= 256 with at most 1 024 workgroups, K > 256 when all tiles are resident at
+                                    * once) -- bit-identical to the slab kernels; the bit exists for tests and A/B timings.  (Not covered by
+                                    * this: k_merge_update16, a merge update of hgt_edge_aggregate_items_update, whose sums differ from its
+                                    * 32 x 32 form's in the last bits.) */
 int hgt_typed_linear(const float* x, int64_t ldx, const int32_t* rows, const int32_t* group_off,
                      int32_t n_groups, int64_t n_rows, int32_t k, int32_t n_out,
                      const float* W, int64_t w_group_stride, const float* bias, int64_t b_group_stride,
