@@ -3,7 +3,7 @@
 OAG/train_paper_field.py:218-279): sampled batch -> to_device_graph (instead of to_torch + .to(device)) -> GNN -> Classifier
 -> nll_loss -> backward -> optimizer step, on sampler-shaped synthetic batches (the datasets are not available offline).
 
-    python examples/train_synthetic.py [--schema mag|oag] [--steps 30] [--conv hgt|dense_hgt]
+    python examples/train_synthetic.py [--schema mag|oag] [--steps 30] [--conv hgt|dense_hgt] [--n-hid 128] [--n-heads 8]
 
 Everything on the hot path runs on the HIP kernels of pyhgt_amd (forward and backward); torch supplies the optimizer, the loss
 and the autograd boundary."""
@@ -61,5 +61,7 @@ if __name__ == "__main__":
     ap.add_argument("--schema", default="mag", choices=["mag", "oag"])
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--conv", default="hgt", choices=["hgt", "dense_hgt"])
+    ap.add_argument("--n-hid", type=int, default=int(os.environ.get("HGT_TRAIN_D", 128)), help="hidden width (e.g. 768 with 8 heads)")
+    ap.add_argument("--n-heads", type=int, default=int(os.environ.get("HGT_TRAIN_H", 8)))
     a = ap.parse_args()
-    run(a.schema, a.steps, a.conv)
+    run(a.schema, a.steps, a.conv, n_hid=a.n_hid, n_heads=a.n_heads)

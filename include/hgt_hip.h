@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define HGT_ABI_VERSION 7
+#define HGT_ABI_VERSION 8
 
 /* error codes */
 #define HGT_OK 0
@@ -482,6 +482,14 @@ int hgt_head_dot(const float* a, const float* b, int64_t n_rows, int32_t n_heads
 int hgt_relation_outer(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations, int32_t n_heads,
                        int32_t dk_pad, const float* weights, const float* a_src, const float* rte_a, const float* b_dst, float* out,
                        void* stream);
+/* ABI 8: the same sums for heads of 128 or 256 padded columns (n_hid 768 / 1024 with 8 heads, 512 with 4 or 2, 256 with 1): one
+ * workgroup per 128 x 128 block of a head's matrix, exact fp32 products on the matrix cores (v_mfma_f32_32x32x2_f32).  Same arguments
+ * and contract as hgt_relation_outer (+= into out, a relation without edges is left untouched, rte_a optional; a_src / rte_a /
+ * b_dst 16-byte aligned); HGT_ERR_UNSUPPORTED for every other dk_pad -- hgt_relation_outer covers heads of up to 64 columns. */
+int hgt_relation_outer_wide(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations, int32_t n_heads,
+                            int32_t dk_pad, const float* weights, const float* a_src, const float* rte_a, const float* b_dst,
+                            float* out, void* stream);
+/* d <= 1024 (rows of up to 512 columns and wider ones run two instantiations of one kernel: 8 / 16 columns per lane) */
 int hgt_node_update_bwd(const float* grad_out, const float* trans, const float* x, int64_t ldx, const int64_t* node_type,
                         const float* skip, const float* ln_w, int32_t use_norm, const float* drop_mask, int64_t n_rows, int32_t d,
                         int32_t n_types, float* d_trans, float* dx, int64_t ld_dx, float* d_alpha, float* d_ln_w, float* d_ln_b,

@@ -77,7 +77,7 @@ class HgtConvArgs(C.Structure):
     ]
 
 
-ABI_VERSION = 7          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
+ABI_VERSION = 8          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
 
 _i32, _i64, _u64, _vp = C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
 
@@ -147,6 +147,7 @@ SIGNATURES = {
     "hgt_edge_gather_sorted": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "hgt_head_dot": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "hgt_relation_outer": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hgt_relation_outer_wide": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hgt_node_update_bwd_ex": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
                                          _vp]),
     "hgt_single_group_offsets": (C.c_int, [_vp, _i32, _vp, _vp]),

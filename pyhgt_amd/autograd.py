@@ -19,7 +19,22 @@ import torch
 
 from . import _lib
 
-__all__ = ["hgt_conv_train", "TypedLinearFunction"]
+__all__ = ["hgt_conv_train", "training_supported", "TypedLinearFunction", "MAX_TRAIN_DK_PAD"]
+
+
+MAX_TRAIN_DK_PAD = 256      # widest (padded) head the training path covers: the matrix-core form of hgt_edge_spmm ends there
+
+
+def training_supported(out_dim, n_heads):
+    """(ok, reason): can a layer of this width / head count run the training forward + backward?  Host-only (the layout
+    arithmetic of hgt_layout_for); the one statement of the limit -- hgt_conv_train's guard and the tests both call it.
+    Heads of up to 64 padded columns take hgt_relation_outer, 128 and 256 hgt_relation_outer_wide; wider heads (out_dim 512
+    with one head, 1024 with two) run inference only."""
+    lay = _lib.layout_for(out_dim, n_heads)
+    if lay.dk_pad > MAX_TRAIN_DK_PAD:
+        return False, ("the backward pass supports heads of at most %d (padded) columns; out_dim=%d / n_heads=%d gives %d.  "
+                       "Inference has no such limit (INTEGRATION.md, training limits)" % (MAX_TRAIN_DK_PAD, out_dim, n_heads, lay.dk_pad))
+    return True, ""
 
 
 def _p(t):
@@ -102,7 +117,8 @@ class _Ops:
         nb = C.c_uint64()
         _chk("hgt_relation_frag_bytes", self.lib.hgt_relation_frag_bytes(self.R, self.H, self.dkp, C.byref(nb)))
         if nb.value == 0:
-            raise RuntimeError("pyhgt_amd: training needs a layout the matrix-core aggregation covers (a head of at most 256 columns)")
+            raise RuntimeError("pyhgt_amd: training needs a layout the matrix-core aggregation covers: heads of at most %d (padded) "
+                               "columns, this layout has %d (autograd.training_supported)" % (MAX_TRAIN_DK_PAD, self.dkp))
         f = torch.empty(int(nb.value), dtype=torch.uint8, device=self.dev)
         _chk("hgt_relation_frag_pack", self.lib.hgt_relation_frag_pack(_p(msg_p), self.R, self.H, self.dkp, _p(f), _st()))
         return f
@@ -115,6 +131,15 @@ class _Ops:
 
     def logits(self, plan, Q, K, rte_k, att_t):
         out = torch.empty(plan.E, self.H, dtype=torch.float32, device=self.dev)
+        if self.dkp >= 128:
+            # wide heads: the vector-ALU kernel cannot hold a head's relation matrix in registers and re-reads it per edge (604 ms per
+            # call at 1 M nodes / 10 M edges, n_hid 768 / 8 heads) -- the matrix-core form of the inference path instead (18 ms;
+            # 3-term split products like the aggregation's, also for precision='fp32' layers)
+            frag = self.frags(att_t)
+            _chk("hgt_edge_logits_mfma", self.lib.hgt_edge_logits_mfma(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(Q), _p(K),
+                                                                     _p(rte_k), _p(att_t), _p(frag), 0, _p(out), _st()))
+            frag.record_stream(torch.cuda.current_stream())
+            return out
         _chk("hgt_edge_logits", self.lib.hgt_edge_logits(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(Q), _p(K), _p(rte_k),
                                                        _p(att_t), _p(out), _st()))
         return out
@@ -165,8 +190,10 @@ class _Ops:
 
     def outer(self, plan, w, a, rte_a, b):
         out = torch.zeros(self.R, self.H, self.dkp, self.dkp, dtype=torch.float32, device=self.dev)
-        _chk("hgt_relation_outer", self.lib.hgt_relation_outer(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(w), _p(a),
-                                                             _p(rte_a), _p(b), _p(out), _st()))
+        # heads of up to 64 padded columns: register-resident blocks per wavefront; 128 / 256: one workgroup per 128 x 128 block
+        name = "hgt_relation_outer" if self.dkp <= 64 else "hgt_relation_outer_wide"
+        _chk(name, getattr(self.lib, name)(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(w), _p(a), _p(rte_a), _p(b),
+                                           _p(out), _st()))
         return out
 
 
@@ -411,13 +438,9 @@ def hgt_conv_train(layer, plan, x, packed, drop_p):
     layer._pack_parameters(grad=True); drop_p = dropout probability of conv.py:125 / 261,273 (0 in eval mode)."""
     if plan.NQ != plan.N:
         raise NotImplementedError("pyhgt_amd: the backward pass covers single-GPU graphs (n_q_rows == n_nodes)")
-    lay = packed["lay"]
-    if lay.dk_pad > 64:
-        # hgt_relation_outer (the relation gradients) splits a head over at most 64 lanes x registers, and the MFMA form of
-        # hgt_edge_spmm needs heads of at most 256 columns: say so HERE instead of failing inside loss.backward()
-        raise NotImplementedError("pyhgt_amd: the backward pass supports heads of at most 64 (padded) columns; out_dim=%d / n_heads=%d "
-                                  "gives %d.  Inference has no such limit (INTEGRATION.md, training limits)" % (layer.out_dim, layer.n_heads,
-                                                                                                              lay.dk_pad))
+    ok, reason = training_supported(layer.out_dim, layer.n_heads)
+    if not ok:      # said HERE instead of failing inside loss.backward()
+        raise NotImplementedError("pyhgt_amd: " + reason)
     dense = "mid_w" in packed
     masks = None
     if drop_p > 0.0:

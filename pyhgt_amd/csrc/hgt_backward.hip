@@ -32,9 +32,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 // per-type parameter gradients are summed in registers while the type does not change and flushed with atomics.
 // ---------------------------------------------------------------------------------------------
 constexpr int NUB_ROWS = 32;
-constexpr int NUB_MAXC = 8;     // columns per lane: d <= 512
+constexpr int NUB_MAXC = 8;          // columns per lane of k_node_update_bwd: d <= 512
+constexpr int NUB_MAXC_WIDE = 16;    // ... of k_node_update_bwd_wide: 512 < d <= 1024 (like MAX_PER_LANE of the forward, hgt_update.hip)
 
-__global__ __launch_bounds__(256) void k_node_update_bwd(
+template <int NUB_MAXC>
+__device__ __forceinline__ void node_update_bwd_rows(
     const float* __restrict__ gout, const float* __restrict__ trans, const float* __restrict__ x, int64_t ldx,
     const int64_t* __restrict__ node_type, const float* __restrict__ skip, const float* __restrict__ lnw, int use_norm,
     const float* __restrict__ drop_mask, int64_t NQ, int d, int T, float* __restrict__ d_trans, float* __restrict__ dx, int64_t ld_dx,
@@ -145,6 +147,21 @@ __global__ __launch_bounds__(256) void k_node_update_bwd(
     }
     flush();
 }
+
+#define HGT_NUB_PARAMS                                                                                                              \
+    const float *__restrict__ gout, const float *__restrict__ trans, const float *__restrict__ x, int64_t ldx,                       \
+        const int64_t *__restrict__ node_type, const float *__restrict__ skip, const float *__restrict__ lnw, int use_norm,           \
+        const float *__restrict__ drop_mask, int64_t NQ, int d, int T, float *__restrict__ d_trans, float *__restrict__ dx,            \
+        int64_t ld_dx, float *__restrict__ d_alpha, float *__restrict__ d_lnw, float *__restrict__ d_lnb, int shared_norm,             \
+        int rows_per_wave
+#define HGT_NUB_ARGS \
+    gout, trans, x, ldx, node_type, skip, lnw, use_norm, drop_mask, NQ, d, T, d_trans, dx, ld_dx, d_alpha, d_lnw, d_lnb, shared_norm, rows_per_wave
+
+__global__ __launch_bounds__(256) void k_node_update_bwd(HGT_NUB_PARAMS) { node_update_bwd_rows<NUB_MAXC>(HGT_NUB_ARGS); }
+// rows of 513 .. 1024 columns (n_hid 768 / 1024): the same walk with 16 columns per lane
+__global__ __launch_bounds__(256) void k_node_update_bwd_wide(HGT_NUB_PARAMS) { node_update_bwd_rows<NUB_MAXC_WIDE>(HGT_NUB_ARGS); }
+#undef HGT_NUB_PARAMS
+#undef HGT_NUB_ARGS
 
 // dagg = dg * gelu'(agg), gelu = exact erf form (conv.py:119)
 __global__ void k_gelu_bwd(const float* __restrict__ dg, const float* __restrict__ agg, float* __restrict__ out, int64_t n) {
@@ -678,6 +695,132 @@ struct LaunchOuter {
     }
 };
 
+// Heads of 128 and 256 padded columns (hgt_relation_outer_wide): per head the sum is a dkp x dkp GEMM whose reduction dimension is
+// the relation's edges -- far past what a wavefront's registers hold, so a WORKGROUP owns one 128 x 128 block of one head of one
+// relation (blockIdx.y = (head, row block, column block), blockIdx.z = relation) and its four wavefronts the four 64 x 64 quadrants:
+// 2 x 2 v_mfma_f32_32x32x2_f32 accumulators each (exact fp32 products, 64 registers).  The workgroup walks the matching items of
+// its slice of the item list; per batch of OW_UB edges its 256 threads gather the 128-column segments of the source rows (+ temporal
+// rows), scale them with the edge weight and park them next to the target rows' segments in LDS ([edge][column], stride 160 floats:
+// the two edges of an MFMA pair fall into different bank halves), so a segment is read from memory once per block instead of once
+// per quadrant.  Two LDS buffers: one barrier per batch; the next batch of the item is fetched while the matrix cores run.
+constexpr int OW_UB = 16;             // edges per batch (two per thread and operand)
+constexpr int OW_RS = 128 + 32;       // LDS row stride in floats
+constexpr int OW_ITEMS_SMALL = 8, OW_ITEMS_LARGE = 64;   // items per workgroup = this x (R + 1): LaunchOuter's 2 / 16 per wavefront x 4
+
+struct OwBatch {                      // one thread's share of a batch: 4 columns of two edges' rows, and the edges' weights
+    float4 a[2], t[2], b[2];
+    float w[2];
+};
+
+template <bool RTE>
+__global__ __launch_bounds__(256, 2) void k_relation_outer_wide(
+    const HgtItem* __restrict__ items, const HgtPlanHeader* __restrict__ hdr, const int32_t* __restrict__ esrc,
+    const int32_t* __restrict__ edst, const uint16_t* __restrict__ ertei, const float* __restrict__ w, const float* __restrict__ a,
+    const float* __restrict__ rte_a, const float* __restrict__ b, float* __restrict__ out, int HT, int dkp, int items_per_wg) {
+    __shared__ __attribute__((aligned(16))) float s_rows[2][2][OW_UB][OW_RS];      // [buffer][a | b][edge][column]
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nblk_h = dkp / 128;                              // 128-column blocks per head side: 1 or 2
+    const int h = blockIdx.y / (nblk_h * nblk_h);
+    const int kb = (blockIdx.y / nblk_h) % nblk_h, cb = blockIdx.y % nblk_h;
+    const int rel_sel = blockIdx.z;
+    const int64_t ld = (int64_t)HT * dkp;
+    const int n_items = hdr->n_items;
+    const int first = blockIdx.x * items_per_wg;
+    if (first >= n_items) return;
+    const int last = min(first + items_per_wg, n_items);
+    // gather role: thread = (edge slot u of the batch (and u + 8), 4 columns)
+    const int u = tid >> 5, c4 = (tid & 31) * 4;
+    const float* a_seg = a + h * dkp + kb * 128 + c4;
+    const float* t_seg = RTE ? rte_a + h * dkp + kb * 128 + c4 : nullptr;
+    const float* b_seg = b + h * dkp + cb * 128 + c4;
+    // matrix-core role: wavefront = quadrant (qr, qc); lane = (edge of the pair, row / column inside a 32-wide tile)
+    const int qr = wib >> 1, qc = wib & 1;
+    const int er = lane >> 5, cc = lane & 31;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    OwBatch bt;
+    auto fetch = [=](int e0, int end) {
+        OwBatch n;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int e = e0 + u + 8 * k;
+            const int idx = min(e, end - 1);           // slots beyond the item re-read its last edge with weight 0
+            const int s = esrc[idx], dd = edst[idx];
+            n.a[k] = *reinterpret_cast<const float4*>(a_seg + (int64_t)s * ld);
+            if constexpr (RTE) n.t[k] = *reinterpret_cast<const float4*>(t_seg + (int64_t)ertei[idx] * ld);
+            else n.t[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);      // (never read: a fully written struct stays in registers)
+            n.b[k] = *reinterpret_cast<const float4*>(b_seg + (int64_t)dd * ld);
+            n.w[k] = e < end ? w[(int64_t)idx * HT + h] : 0.0f;
+        }
+        return n;
+    };
+    int buf = 0;
+    bool any = false;
+    for (int ib = first; ib < last; ib += 64) {
+        // 64 item headers at a time (lane i = item ib + i), the same in every wavefront: the loops below are workgroup-uniform
+        const HgtItem mine = items[min(ib + lane, n_items - 1)];
+        const bool take = (ib + lane < last) && mine.rel == rel_sel;
+        unsigned long long todo = __builtin_amdgcn_ballot_w64(take);
+        while (todo) {
+            const int li_ = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int beg = __builtin_amdgcn_readlane(mine.beg, li_), end = __builtin_amdgcn_readlane(mine.end, li_);
+            if (beg >= end) continue;
+            any = true;
+            bt = fetch(beg, end);
+            for (int e0 = beg; e0 < end; e0 += OW_UB) {
+                float (*sa)[OW_RS] = s_rows[buf][0];
+                float (*sb)[OW_RS] = s_rows[buf][1];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    float4 v = bt.a[k];
+                    if constexpr (RTE) { v.x += bt.t[k].x; v.y += bt.t[k].y; v.z += bt.t[k].z; v.w += bt.t[k].w; }
+                    v.x *= bt.w[k]; v.y *= bt.w[k]; v.z *= bt.w[k]; v.w *= bt.w[k];
+                    *reinterpret_cast<float4*>(&sa[u + 8 * k][c4]) = v;
+                    *reinterpret_cast<float4*>(&sb[u + 8 * k][c4]) = bt.b[k];
+                }
+                // one barrier per batch: this buffer was last read two batches ago, before the previous batch's barrier
+                __syncthreads();
+                if (e0 + OW_UB < end) bt = fetch(e0 + OW_UB, end);
+#pragma unroll
+                for (int pr = 0; pr < OW_UB / 2; ++pr) {
+                    float fa[2], fb[2];
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        fa[i] = sa[2 * pr + er][qr * 64 + i * 32 + cc];
+                        fb[i] = sb[2 * pr + er][qc * 64 + i * 32 + cc];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+                }
+                buf ^= 1;
+            }
+        }
+    }
+    if (any) {
+        // C layout of a 32 x 32 tile: column c = lane & 31, row k = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+        float* o = out + (((int64_t)rel_sel * HT + h) * dkp + kb * 128 + qr * 64) * dkp + cb * 128 + qc * 64;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int k = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * er;
+                    unsafeAtomicAdd(&o[(int64_t)k * dkp + j * 32 + cc], acc[i][j][r]);
+                }
+    }
+}
+
 static inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 }  // namespace
@@ -686,7 +829,7 @@ static int node_update_bwd_impl(const float* grad_out, const float* trans, const
                                 const float* skip, const float* ln_w, int32_t use_norm, int32_t shared_norm, const float* drop_mask,
                                 int64_t n_rows, int32_t d, int32_t n_types, float* d_trans, float* dx, int64_t ld_dx, float* d_alpha,
                                 float* d_ln_w, float* d_ln_b, void* stream) {
-    if (!grad_out || !trans || !x || !node_type || !d_trans || !dx || (skip && !d_alpha) || n_rows < 0 || d <= 0 || d > 64 * NUB_MAXC)
+    if (!grad_out || !trans || !x || !node_type || !d_trans || !dx || (skip && !d_alpha) || n_rows < 0 || d <= 0 || d > 64 * NUB_MAXC_WIDE)
         return HGT_ERR_INVALID_ARG;
     if (use_norm && (!ln_w || !d_ln_w || !d_ln_b)) return HGT_ERR_INVALID_ARG;
     if (n_rows == 0) return HGT_OK;
@@ -694,9 +837,10 @@ static int node_update_bwd_impl(const float* grad_out, const float* trans, const
     // ~100 wavefronts walking 32 rows one after the other (c3: 119 us) -- 2 rows there, 8 in between
     const int rpw = n_rows >= 65536 ? NUB_ROWS : (n_rows >= 16384 ? 8 : 2);
     const int64_t waves = (n_rows + rpw - 1) / rpw;
-    k_node_update_bwd<<<nblk(waves, 4), 256, 0, (hipStream_t)stream>>>(grad_out, trans, x, ldx, node_type, skip, ln_w, use_norm, drop_mask,
-                                                                       n_rows, d, n_types, d_trans, dx, ld_dx, d_alpha, d_ln_w, d_ln_b,
-                                                                       shared_norm, rpw);
+    // d <= 512 keeps the 8-columns-per-lane kernel (its registers, its results); wider rows take the 16-column instantiation
+    auto* kernel = d <= 64 * NUB_MAXC ? k_node_update_bwd : k_node_update_bwd_wide;
+    kernel<<<nblk(waves, 4), 256, 0, (hipStream_t)stream>>>(grad_out, trans, x, ldx, node_type, skip, ln_w, use_norm, drop_mask, n_rows, d,
+                                                            n_types, d_trans, dx, ld_dx, d_alpha, d_ln_w, d_ln_b, shared_norm, rpw);
     HGT_CHECK_LAUNCH();
     return HGT_OK;
 }
@@ -826,6 +970,34 @@ extern "C" int hgt_relation_outer(const void* plan, int64_t N, int64_t E, int32_
     while (vec * dk_pad > 128 && vec > 1 && l2 * 2 <= 64) { vec /= 2; l2 *= 2; }
     int rc = dispatch_layout<LaunchOuter>(vec, l2, pv, weights, a_src, rte_a, b_dst, out, (int)R, (int)H, (hipStream_t)stream);
     if (rc != HGT_OK) return rc;
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+// hgt_relation_outer for heads of 128 / 256 padded columns (ABI 8): same arguments and contract (+= into the caller's buffer, a
+// relation without edges stays untouched, rte_a optional).  Everything else is HGT_ERR_UNSUPPORTED and launches nothing:
+// hgt_relation_outer keeps the narrower heads.
+extern "C" int hgt_relation_outer_wide(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
+                                       const float* weights, const float* a_src, const float* rte_a, const float* b_dst, float* out,
+                                       void* stream) {
+    if (!plan || !a_src || !b_dst || !out || (E > 0 && !weights) || H <= 0 || R <= 0 || dk_pad <= 0) return HGT_ERR_INVALID_ARG;
+    if (dk_pad != 128 && dk_pad != 256) return HGT_ERR_UNSUPPORTED;
+    if ((((uintptr_t)a_src | (uintptr_t)b_dst | (uintptr_t)rte_a) & 15) != 0) return HGT_ERR_INVALID_ARG;      // 16-byte row loads
+    const int64_t blocks = (int64_t)H * (dk_pad / 128) * (dk_pad / 128);
+    if (blocks > 65535 || R > 65535) return HGT_ERR_TOO_LARGE;
+    if (E == 0) return HGT_OK;
+    HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
+    // items are ordered (tile, relation): ~8 / ~64 items of the selected relation per workgroup, the two regimes of LaunchOuter::run
+    // (sampled batches: enough workgroups to fill the chip; large graphs: fewer 128 x 128 atomic flushes)
+    const int ipw = (pv.L.max_items < 16384 ? OW_ITEMS_SMALL : OW_ITEMS_LARGE) * (R + 1);
+    dim3 grid((unsigned)((pv.L.max_items + ipw - 1) / ipw), (unsigned)blocks, (unsigned)R);
+    if (grid.x == 0) return HGT_OK;
+    if (rte_a)
+        k_relation_outer_wide<true><<<grid, 256, 0, (hipStream_t)stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, weights, a_src,
+                                                                            rte_a, b_dst, out, (int)H, (int)dk_pad, ipw);
+    else
+        k_relation_outer_wide<false><<<grid, 256, 0, (hipStream_t)stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, weights, a_src,
+                                                                             rte_a, b_dst, out, (int)H, (int)dk_pad, ipw);
     HGT_CHECK_LAUNCH();
     return HGT_OK;
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Training-step timing of one HGTConv at BASELINE.json configs[1]: forward + backward through
-pyhgt_amd/autograd.py against the inference forward, plan (and transposed plan) cached."""
+pyhgt_amd/autograd.py against the inference forward, plan (and transposed plan) cached.  Sizes from the environment: HGT_TRAIN_N,
+HGT_TRAIN_E (nodes, edges), HGT_TRAIN_D, HGT_TRAIN_H (width, heads); HGT_TRAIN_NO_SMALL=1 skips the sampled-batch part."""
 import json
 import os
 import sys
@@ -85,7 +86,9 @@ def sampled_batches(dev):
 
 def main():
     dev = "cuda:0"
-    N, E, d, T, R, H = (int(os.environ.get("HGT_TRAIN_N", 1000000)), int(os.environ.get("HGT_TRAIN_E", 10000000)), 256, 4, 8, 8)
+    # HGT_TRAIN_D / HGT_TRAIN_H: layer width and head count (defaults: configs[1]; 768 / 8 and 1024 / 8 are the wide-head layouts)
+    N, E, d, T, R, H = (int(os.environ.get("HGT_TRAIN_N", 1000000)), int(os.environ.get("HGT_TRAIN_E", 10000000)),
+                        int(os.environ.get("HGT_TRAIN_D", 256)), 4, 8, int(os.environ.get("HGT_TRAIN_H", 8)))
     x, nt, ei, et, tm = [t.to(dev) for t in synthetic_typed_graph(N, E, d, T, R, seed=1)]
     layer = HGTConv(d, d, T, R, H, 0.2, True, False).to(dev)
     plan = GraphPlan(nt, ei, et, None, T, R)
@@ -103,8 +106,9 @@ def main():
     layer.train()
     xg = x.clone().requires_grad_(True)
     g = torch.randn(N, d, device=dev)
+    iters = 5 if N >= 200000 else 50          # a sampled-batch-sized graph steps in ~2 ms: time enough of them
     for phase in ("forward_ms", "forward_backward_ms"):
-        for it in range(2 + 5):
+        for it in range(2 + iters):
             if it == 2:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -114,8 +118,8 @@ def main():
                 layer.zero_grad(set_to_none=True)
                 xg.grad = None
         torch.cuda.synchronize()
-        res["training_" + phase] = (time.perf_counter() - t0) / 5 * 1e3
-    res["N"], res["E"] = N, E
+        res["training_" + phase] = (time.perf_counter() - t0) / iters * 1e3
+    res["N"], res["E"], res["d"], res["H"] = N, E, d, H
     res["peak_mem_gb"] = torch.cuda.max_memory_allocated() / 2 ** 30
     fwd_b, bwd_b = training_step_bytes(N, E, d, H)
     bf, bb = sum(fwd_b.values()), sum(bwd_b.values())
