@@ -7,6 +7,11 @@ over in-edges, relation-wise aggregation on the matrix cores), run kernel by ker
 the aggregate and the a_linear output stay available; the backward strings together the kernels of
 csrc/hgt_backward.hip + the forward kernels on the transposed graph (the derivation is in that file's header).
 
+Layout of this file: TENSOR_SLOTS (the one statement of the Function's input order), the kernel-choice predicates, the typed-linear
+route (_typed_linear / _wgrad, shared with TypedLinearFunction), _Step (the per-call context: kernel wrappers, then the named steps
+of the forward and of the backward, named after the steps of csrc/hgt_api.hip where they correspond), and the two Functions, whose
+forward / backward only dispatch to the steps.
+
 PyTorch's role: the Function boundary, parameter packing with differentiable stack/cat/pad ops (so the gradients of the
 packed arrays flow back to the reference-named parameters by themselves), tiny O(R H d_k^2) / O(T 240 d) chain-rule steps on
 relation matrices and temporal tables, and the dropout mask (torch RNG, like the reference's nn.Dropout at conv.py:125).
@@ -14,15 +19,26 @@ There is no CPU or eager fallback: CPU tensors raise.
 """
 import ctypes as C
 import math
+from types import SimpleNamespace
 
 import torch
 
 from . import _lib
+from ._lib import check
+from .conv import _ptr, _stream
 
-__all__ = ["hgt_conv_train", "training_supported", "TypedLinearFunction", "MAX_TRAIN_DK_PAD"]
+__all__ = ["hgt_conv_train", "training_supported", "logits_form", "outer_form", "spmm_takes_items", "TypedLinearFunction", "MAX_TRAIN_DK_PAD"]
 
 
 MAX_TRAIN_DK_PAD = 256      # widest (padded) head the training path covers: the matrix-core form of hgt_edge_spmm ends there
+
+# Inputs of _HGTConvTrain: PLAIN_SLOTS (no gradient), then these tensors under the names of HGTConv._pack_parameters (None where a
+# layer has no such parameter).  hgt_conv_train builds .apply's arguments from this table, forward reads them by name and backward
+# returns its gradients through it: a new parameter is added HERE and in the step that uses it.
+PLAIN_SLOTS = ("layer", "plan", "drop_masks")
+TENSOR_SLOTS = ("x", "w_qkv", "b_qkv", "w_a", "b_a", "ratt", "rmsg", "rpri", "skip", "ln_w", "ln_b", "rte_emb", "rte_w", "rte_b",
+                "mid_w", "mid_b", "out_w", "out_b", "out_ln_w", "out_ln_b")
+_SPLIT = ("bf16x3", "f16x3")      # precisions of the split-bf16 x3 MFMA GEMMs (the differentiable path evaluates "f16x3" layers with the bf16 split)
 
 
 def training_supported(out_dim, n_heads):
@@ -37,164 +53,78 @@ def training_supported(out_dim, n_heads):
     return True, ""
 
 
-def _p(t):
-    return 0 if t is None else t.data_ptr()
+# -- which kernel runs (host predicates; the tests call them to aim their cases at each branch) -----------------------------------
+def logits_form(dk_pad):
+    """'mfma' (hgt_edge_logits_mfma) or 'valu' (hgt_edge_logits).  Wide heads: the vector-ALU kernel cannot hold a head's relation
+    matrix in registers and re-reads it per edge (604 ms per call at 1 M nodes / 10 M edges, n_hid 768 / 8 heads) -- the matrix-core
+    form of the inference path instead (18 ms; 3-term split products like the aggregation's, also for precision='fp32' layers)."""
+    return "mfma" if dk_pad >= 128 else "valu"
 
 
-def _st():
-    return torch.cuda.current_stream().cuda_stream
+def outer_form(dk_pad):
+    """Entry point of the relation outer products.  Heads of up to 64 padded columns: register-resident blocks per wavefront;
+    128 / 256: one workgroup per 128 x 128 block."""
+    return "hgt_relation_outer" if dk_pad <= 64 else "hgt_relation_outer_wide"
 
 
-def _chk(name, rc):
-    _lib.check(rc, name)
+def spmm_takes_items(N, E, R, ld_out, out_col):
+    """Does a gather pass take hgt_edge_spmm_items (else hgt_edge_spmm)?  Sampled batches: the item-parallel form (one wavefront
+    per <= 16-edge item + an ordered merge) -- the sub-tile kernel's wavefronts each walk sixteen targets' edges one after the other
+    (285 vs ~25 us per call at c3).  The kernel stores 4-column vectors and keeps a relation per lane."""
+    return N < 65536 and E > 0 and R < 64 and ld_out % 4 == 0 and out_col % 4 == 0
 
 
-class _Ops:
-    """Thin typed wrappers around the C ABI calls the training path needs (all on the current stream)."""
-
-    def __init__(self, plan, lay, T, R, H, precision):
-        self.lib = _lib.load()
-        self.plan, self.lay = plan, lay
-        self.T, self.R, self.Hreal = T, R, H
-        self.H = lay.heads                                   # kernels run with the layout's head count (extra heads: zero)
-        self.dk, self.dkp, self.dp = lay.d_k, lay.dk_pad, lay.d_pad
-        self.split = precision in ("bf16x3", "f16x3")      # (the differentiable path evaluates "f16x3" layers with the bf16 split)
-        self.N, self.E = plan.N, plan.E
-        self.dev = plan.device
-        self._scratch = {}
-
-    # -- dense ---------------------------------------------------------------------------------------------
-    def typed_linear(self, x, ldx, rows, off, n_groups, n_rows, k, n_out, W, w_off, wgs, bias, b_off, bgs, outs, block_cols,
-                     by_pos=0, prologue=0):
-        """y = prologue(x[rows]) W[g]^T + b[g]; W / bias given as (tensor, element offset).  outs: up to 3 column blocks."""
-        lib = self.lib
-        o = [_p(t) for t in outs] + [0] * (3 - len(outs))
-        wp = W.data_ptr() + 4 * w_off
-        bp = 0 if bias is None else bias.data_ptr() + 4 * b_off
-        if self.split and (n_out % 4 == 0) and (block_cols % 4 == 0):
-            nb = C.c_uint64()
-            _chk("hgt_split_weights_bytes", lib.hgt_split_weights_bytes(n_groups, k, n_out, C.byref(nb)))
-            tiles = torch.empty(int(nb.value), dtype=torch.uint8, device=self.dev)
-            _chk("hgt_split_weights", lib.hgt_split_weights(wp, wgs, n_groups, k, n_out, _p(tiles), _st()))
-            _chk("hgt_typed_linear_bf16x3", lib.hgt_typed_linear_bf16x3(_p(x), ldx, rows, off, n_groups, n_rows, k, n_out, _p(tiles), bp, bgs,
-                                                                      o[0], o[1], o[2], block_cols, by_pos, prologue, _st()))
-            tiles.record_stream(torch.cuda.current_stream())
-        else:
-            _chk("hgt_typed_linear", lib.hgt_typed_linear(_p(x), ldx, rows, off, n_groups, n_rows, k, n_out, wp, wgs, bp, bgs,
-                                                        o[0], o[1], o[2], block_cols, by_pos, prologue, 0, _st()))
-
-    def wgrad(self, A, lda, B, ldb, rows, off, n_groups, n_rows, m, n_cols, with_colsum=False):
-        """dW[g] = A_g^T B_g (and, with_colsum, db[g] = column sums of A_g from the same pass): split-bf16 x3 MFMA kernel for
-        bf16x3 layers, the exact fp32 MFMA kernel (+ the column-sum kernel) otherwise."""
-        out = torch.zeros(n_groups, m, n_cols, dtype=torch.float32, device=self.dev)
-        cs = torch.zeros(n_groups, m, dtype=torch.float32, device=self.dev) if with_colsum else None
-        if self.split:
-            _chk("hgt_typed_wgrad_bf16x3", self.lib.hgt_typed_wgrad_bf16x3(_p(A), lda, _p(B), ldb, rows, off, n_groups, n_rows, m, n_cols,
-                                                                         _p(out), m * n_cols, _p(cs), m, _st()))
-        else:
-            _chk("hgt_typed_wgrad", self.lib.hgt_typed_wgrad(_p(A), lda, _p(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _p(out),
-                                                           m * n_cols, _st()))
-            if with_colsum:
-                _chk("hgt_typed_colsum", self.lib.hgt_typed_colsum(_p(A), lda, rows, off, n_groups, n_rows, m, _p(cs), m, _st()))
-        return (out, cs) if with_colsum else out
-
-    def colsum(self, A, lda, rows, off, n_groups, n_rows, m):
-        out = torch.zeros(n_groups, m, dtype=torch.float32, device=self.dev)
-        _chk("hgt_typed_colsum", self.lib.hgt_typed_colsum(_p(A), lda, rows, off, n_groups, n_rows, m, _p(out), m, _st()))
-        return out
-
-    # -- relation matrices ------------------------------------------------------------------------------------
-    def pack(self, att_like, msg_like, pri):
-        """hgt_relation_pack: (att_t[r,h,c,k] = att_like[r,h,k,c] * pri / sqrt(dk), msg_p = msg_like), zero padded to dk_pad."""
-        R, H, dkp = self.R, self.H, self.dkp
-        att_t = torch.empty(R, H, dkp, dkp, dtype=torch.float32, device=self.dev)
-        msg_p = torch.empty(R, H, dkp, dkp, dtype=torch.float32, device=self.dev)
-        _chk("hgt_relation_pack", self.lib.hgt_relation_pack(_p(att_like.contiguous()), _p(msg_like.contiguous()), _p(pri.contiguous()), R,
-                                                           self.Hreal, H, self.dk, dkp, _p(att_t), _p(msg_p), _st()))
-        return att_t, msg_p
-
-    def frags(self, msg_p):
+# -- the typed-linear route: the layer's GEMMs and TypedLinearFunction ---------------------------------------------------------
+def _typed_linear(split, x, ldx, rows, off, n_groups, n_rows, k, n_out, W, w_off, wgs, bias, b_off, bgs, outs, block_cols, by_pos=0,
+                  prologue=0):
+    """y = prologue(x[rows]) W[g]^T + b[g]; W / bias given as (tensor, element offset).  outs: up to 3 column blocks of block_cols.
+    split: the split-bf16 x3 MFMA kernel (where its 4-column stores fit) instead of the exact fp32 one."""
+    lib = _lib.load()
+    o = [_ptr(t) for t in outs] + [0] * (3 - len(outs))
+    wp = W.data_ptr() + 4 * w_off
+    bp = 0 if bias is None else bias.data_ptr() + 4 * b_off
+    if split and n_out % 4 == 0 and block_cols % 4 == 0:
         nb = C.c_uint64()
-        _chk("hgt_relation_frag_bytes", self.lib.hgt_relation_frag_bytes(self.R, self.H, self.dkp, C.byref(nb)))
-        if nb.value == 0:
-            raise RuntimeError("pyhgt_amd: training needs a layout the matrix-core aggregation covers: heads of at most %d (padded) "
-                               "columns, this layout has %d (autograd.training_supported)" % (MAX_TRAIN_DK_PAD, self.dkp))
-        f = torch.empty(int(nb.value), dtype=torch.uint8, device=self.dev)
-        _chk("hgt_relation_frag_pack", self.lib.hgt_relation_frag_pack(_p(msg_p), self.R, self.H, self.dkp, _p(f), _st()))
-        return f
+        check(lib.hgt_split_weights_bytes(n_groups, k, n_out, C.byref(nb)), "hgt_split_weights_bytes")
+        tiles = torch.empty(int(nb.value), dtype=torch.uint8, device=x.device)
+        check(lib.hgt_split_weights(wp, wgs, n_groups, k, n_out, _ptr(tiles), _stream()), "hgt_split_weights")
+        check(lib.hgt_typed_linear_bf16x3(_ptr(x), ldx, rows, off, n_groups, n_rows, k, n_out, _ptr(tiles), bp, bgs, o[0], o[1], o[2],
+                                          block_cols, by_pos, prologue, _stream()), "hgt_typed_linear_bf16x3")
+        tiles.record_stream(torch.cuda.current_stream())
+    else:
+        check(lib.hgt_typed_linear(_ptr(x), ldx, rows, off, n_groups, n_rows, k, n_out, wp, wgs, bp, bgs, o[0], o[1], o[2], block_cols,
+                                   by_pos, prologue, 0, _stream()), "hgt_typed_linear")
 
-    # -- edge phase -------------------------------------------------------------------------------------------
-    def _hub_ws(self, plan):
-        nb = C.c_uint64()
-        _chk("hgt_hub_workspace_bytes", self.lib.hgt_hub_workspace_bytes(plan.E, self.H, self.dkp, C.byref(nb)))
-        return torch.empty(max(int(nb.value), 256), dtype=torch.uint8, device=self.dev)
 
-    def logits(self, plan, Q, K, rte_k, att_t):
-        out = torch.empty(plan.E, self.H, dtype=torch.float32, device=self.dev)
-        if self.dkp >= 128:
-            # wide heads: the vector-ALU kernel cannot hold a head's relation matrix in registers and re-reads it per edge (604 ms per
-            # call at 1 M nodes / 10 M edges, n_hid 768 / 8 heads) -- the matrix-core form of the inference path instead (18 ms;
-            # 3-term split products like the aggregation's, also for precision='fp32' layers)
-            frag = self.frags(att_t)
-            _chk("hgt_edge_logits_mfma", self.lib.hgt_edge_logits_mfma(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(Q), _p(K),
-                                                                     _p(rte_k), _p(att_t), _p(frag), 0, _p(out), _st()))
-            frag.record_stream(torch.cuda.current_stream())
-            return out
-        _chk("hgt_edge_logits", self.lib.hgt_edge_logits(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(Q), _p(K), _p(rte_k),
-                                                       _p(att_t), _p(out), _st()))
-        return out
+def _wgrad(split, A, lda, B, ldb, rows, off, n_groups, n_rows, m, n_cols, with_colsum=True):
+    """(dW[g] = A_g^T B_g, db[g] = column sums of A_g or None): split-bf16 x3 MFMA kernel (both from one pass) for split precisions,
+    the exact fp32 MFMA kernel + the column-sum kernel otherwise."""
+    lib = _lib.load()
+    dw = torch.zeros(n_groups, m, n_cols, dtype=torch.float32, device=A.device)
+    db = torch.zeros(n_groups, m, dtype=torch.float32, device=A.device) if with_colsum else None
+    if split:
+        check(lib.hgt_typed_wgrad_bf16x3(_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols,
+                                         _ptr(db), m, _stream()), "hgt_typed_wgrad_bf16x3")
+    else:
+        check(lib.hgt_typed_wgrad(_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols, _stream()),
+              "hgt_typed_wgrad")
+        if with_colsum:
+            check(lib.hgt_typed_colsum(_ptr(A), lda, rows, off, n_groups, n_rows, m, _ptr(db), m, _stream()), "hgt_typed_colsum")
+    return dw, db
 
-    def softmax_(self, plan, logits):
-        _chk("hgt_edge_softmax", self.lib.hgt_edge_softmax(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, _p(logits), _st()))
-        return logits
 
-    def _items_scratch(self, plan):
-        """Scratch of the item-parallel gather passes (sampled batches), one buffer per plan size, reused by every call of a step."""
-        key = ("items", plan.E)
-        buf = self._scratch.get(key)
-        if buf is None:
-            nb = C.c_uint64()
-            _chk("hgt_edge_aggregate_items_bytes", self.lib.hgt_edge_aggregate_items_bytes(plan.E, self.H, self.dkp, C.byref(nb)))
-            buf = self._scratch[key] = torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=self.dev)
-        return buf
+# -- saved state by name ------------------------------------------------------------------------------------------------------
+def _save_named(ctx, tensors):
+    """Save {name: tensor or None} for the backward: the tensors through ctx.save_for_backward (torch keeps its version-counter
+    checks and the graph's lifetime rules), the names on the side."""
+    ctx.saved_names = tuple(k for k, t in tensors.items() if t is not None)
+    ctx.absent_names = tuple(k for k, t in tensors.items() if t is None)
+    ctx.save_for_backward(*(tensors[k] for k in ctx.saved_names))
 
-    def spmm(self, plan, w, rows_ptr, rte_rows, f_p, f_frag, out, out_col, ld_out, n_q_rows):
-        # sampled batches: the item-parallel form (one wavefront per <= 16-edge item + an ordered merge) -- the sub-tile kernel's
-        # wavefronts each walk sixteen targets' edges one after the other (285 vs ~25 us per call at c3, round 6)
-        if plan.N < 65536 and plan.E > 0 and self.R < 64 and ld_out % 4 == 0 and out_col % 4 == 0:
-            sc = self._items_scratch(plan)
-            rc = self.lib.hgt_edge_spmm_items(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(w), rows_ptr, _p(rte_rows),
-                                              _p(f_frag), out.data_ptr() + 4 * out_col, ld_out, n_q_rows, _p(sc), sc.numel(), _st())
-            if rc == 0:
-                sc.record_stream(torch.cuda.current_stream())
-                return
-            if rc != -2:
-                _chk("hgt_edge_spmm_items", rc)
-        hub = self._hub_ws(plan)
-        _chk("hgt_edge_spmm", self.lib.hgt_edge_spmm(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(w), rows_ptr,
-                                                   _p(rte_rows), _p(f_p), _p(f_frag), out.data_ptr() + 4 * out_col, ld_out, n_q_rows,
-                                                   _p(hub), _st()))
-        hub.record_stream(torch.cuda.current_stream())
 
-    def to_edge_ids(self, plan, sorted_vals):
-        out = torch.empty_like(sorted_vals)
-        _chk("hgt_att_export", self.lib.hgt_att_export(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, _p(sorted_vals), _p(out), self.H,
-                                                     _st()))
-        return out
-
-    def to_sorted(self, plan, by_id):
-        out = torch.empty_like(by_id)
-        _chk("hgt_edge_gather_sorted", self.lib.hgt_edge_gather_sorted(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, _p(by_id), _p(out),
-                                                                     _st()))
-        return out
-
-    def outer(self, plan, w, a, rte_a, b):
-        out = torch.zeros(self.R, self.H, self.dkp, self.dkp, dtype=torch.float32, device=self.dev)
-        # heads of up to 64 padded columns: register-resident blocks per wavefront; 128 / 256: one workgroup per 128 x 128 block
-        name = "hgt_relation_outer" if self.dkp <= 64 else "hgt_relation_outer_wide"
-        _chk(name, getattr(self.lib, name)(plan.ptr, plan.N, plan.E, self.T, self.R, self.H, self.dkp, _p(w), _p(a), _p(rte_a), _p(b),
-                                           _p(out), _st()))
-        return out
+def _load_named(ctx):
+    """What _save_named kept, as a namespace; a tensor that was absent is None."""
+    return SimpleNamespace(**dict.fromkeys(ctx.absent_names), **dict(zip(ctx.saved_names, ctx.saved_tensors)))
 
 
 def _rte_row_lists(T, dev):
@@ -203,234 +133,382 @@ def _rte_row_lists(T, dev):
     return rows, off
 
 
+class _Step:
+    """One forward or backward call of a layer on a plan: sizes, the kernel wrappers (all on the current stream), then the named
+    steps.  p = the Function's tensor inputs by name, s = the saved tensors by name."""
+
+    def __init__(self, layer, plan, lay):
+        self.lib = _lib.load()
+        self.layer, self.plan, self.lay = layer, plan, lay
+        self.T, self.R, self.Hreal = layer.num_types, layer.num_relations, layer.n_heads
+        self.H = lay.heads                                   # kernels run with the layout's head count (extra heads: zero)
+        self.dk, self.dkp, self.dp = lay.d_k, lay.dk_pad, lay.d_pad
+        self.din, self.dout = layer.in_dim, layer.out_dim
+        # data gradients (d gelu(agg), dx) run on the layer's own typed-linear kernels: split-bf16 x3 for split precisions, relative
+        # error ~1e-5, two orders below the gradient tolerance; precision='fp32' layers keep the exact typed-linear kernel.  The
+        # relation transforms of every hgt_edge_spmm -- the training forward's aggregation included -- are ALWAYS split-bf16 MFMA
+        # products under grad, also for precision='fp32': ~1e-5 away from the exact VALU aggregation of the inference path
+        self.split = layer.precision in _SPLIT
+        self.use_norm = bool(layer.use_norm)
+        self.N, self.E = plan.N, plan.E
+        self.dev = plan.device
+        self.rows = plan.row_lists()
+        self._scratch = {}
+
+    def new(self, *shape, zero=False, dtype=torch.float32):
+        return (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=self.dev)
+
+    def graph(self, plan):
+        """Leading arguments of every edge kernel."""
+        return plan.ptr, plan.N, plan.E, self.T, self.R, self.H
+
+    def node_linear(self, x, k, n_out, W, wgs, bias, bgs, out, prologue=0):
+        """out = prologue(x) W[type]^T + b[type] over the target rows of a known type (the others stay unwritten)."""
+        _typed_linear(self.split, x, k, self.rows.rows_q, self.rows.off_q, self.T, self.N, k, n_out, W, 0, wgs, bias, 0, bgs, [out], n_out,
+                      prologue=prologue)
+
+    # -- relation matrices ------------------------------------------------------------------------------------
+    def pack(self, att_like, msg_like, pri):
+        """hgt_relation_pack: (att_t[r,h,c,k] = att_like[r,h,k,c] * pri / sqrt(dk), msg_p = msg_like), zero padded to dk_pad."""
+        R, H, dkp = self.R, self.H, self.dkp
+        att_t, msg_p = self.new(R, H, dkp, dkp), self.new(R, H, dkp, dkp)
+        check(self.lib.hgt_relation_pack(_ptr(att_like.contiguous()), _ptr(msg_like.contiguous()), _ptr(pri.contiguous()), R, self.Hreal, H,
+                                         self.dk, dkp, _ptr(att_t), _ptr(msg_p), _stream()), "hgt_relation_pack")
+        return att_t, msg_p
+
+    def frags(self, msg_p):
+        nb = C.c_uint64()
+        check(self.lib.hgt_relation_frag_bytes(self.R, self.H, self.dkp, C.byref(nb)), "hgt_relation_frag_bytes")
+        if nb.value == 0:
+            raise RuntimeError("pyhgt_amd: training needs a layout the matrix-core aggregation covers: heads of at most %d (padded) "
+                               "columns, this layout has %d (autograd.training_supported)" % (MAX_TRAIN_DK_PAD, self.dkp))
+        f = self.new(int(nb.value), dtype=torch.uint8)
+        check(self.lib.hgt_relation_frag_pack(_ptr(msg_p), self.R, self.H, self.dkp, _ptr(f), _stream()), "hgt_relation_frag_pack")
+        return f
+
+    # -- edge phase -------------------------------------------------------------------------------------------
+    def logits(self, plan, Q, K, rte_k, att_t):
+        out = self.new(plan.E, self.H)
+        if logits_form(self.dkp) == "mfma":
+            frag = self.frags(att_t)
+            check(self.lib.hgt_edge_logits_mfma(*self.graph(plan), self.dkp, _ptr(Q), _ptr(K), _ptr(rte_k), _ptr(att_t), _ptr(frag), 0,
+                                                _ptr(out), _stream()), "hgt_edge_logits_mfma")
+            frag.record_stream(torch.cuda.current_stream())
+        else:
+            check(self.lib.hgt_edge_logits(*self.graph(plan), self.dkp, _ptr(Q), _ptr(K), _ptr(rte_k), _ptr(att_t), _ptr(out), _stream()),
+                  "hgt_edge_logits")
+        return out
+
+    def _items_scratch(self, plan):
+        """Scratch of the item-parallel gather passes (sampled batches), one buffer per plan size, reused by every pass of this call."""
+        key = ("items", plan.E)
+        buf = self._scratch.get(key)
+        if buf is None:
+            nb = C.c_uint64()
+            check(self.lib.hgt_edge_aggregate_items_bytes(plan.E, self.H, self.dkp, C.byref(nb)), "hgt_edge_aggregate_items_bytes")
+            buf = self._scratch[key] = self.new(max(int(nb.value), 16), dtype=torch.uint8)
+        return buf
+
+    def spmm(self, plan, w, rows_ptr, rte_rows, f_p, f_frag, out, out_col, ld_out, n_q_rows):
+        """out[:, out_col : out_col + dp] = sum_r (sum_e w_e rows[src_e]) F_r over the in-edges of every target of `plan`."""
+        optr = out.data_ptr() + 4 * out_col
+        if spmm_takes_items(plan.N, plan.E, self.R, ld_out, out_col):
+            sc = self._items_scratch(plan)
+            rc = self.lib.hgt_edge_spmm_items(*self.graph(plan), self.dkp, _ptr(w), rows_ptr, _ptr(rte_rows), _ptr(f_frag), optr, ld_out,
+                                              n_q_rows, _ptr(sc), sc.numel(), _stream())
+            if rc == 0:
+                sc.record_stream(torch.cuda.current_stream())
+                return
+            if rc != -2:      # HGT_ERR_UNSUPPORTED = nothing was launched: the sub-tile kernel below takes the pass
+                check(rc, "hgt_edge_spmm_items")
+        nb = C.c_uint64()
+        check(self.lib.hgt_hub_workspace_bytes(plan.E, self.H, self.dkp, C.byref(nb)), "hgt_hub_workspace_bytes")
+        hub = self.new(max(int(nb.value), 256), dtype=torch.uint8)
+        check(self.lib.hgt_edge_spmm(*self.graph(plan), self.dkp, _ptr(w), rows_ptr, _ptr(rte_rows), _ptr(f_p), _ptr(f_frag), optr, ld_out,
+                                     n_q_rows, _ptr(hub), _stream()), "hgt_edge_spmm")
+        hub.record_stream(torch.cuda.current_stream())
+
+    def to_edge_ids(self, plan, sorted_vals, out_heads=None):
+        """Per-edge values in plan order -> the caller's edge order.  out_heads: row stride of the result (the layout's head count;
+        self.att wants the model's)."""
+        out = torch.empty_like(sorted_vals) if out_heads is None else self.new(plan.E, out_heads)
+        check(self.lib.hgt_att_export(*self.graph(plan), _ptr(sorted_vals), _ptr(out), out.size(1), _stream()), "hgt_att_export")
+        return out
+
+    def to_sorted(self, plan, by_id):
+        out = torch.empty_like(by_id)
+        check(self.lib.hgt_edge_gather_sorted(*self.graph(plan), _ptr(by_id), _ptr(out), _stream()), "hgt_edge_gather_sorted")
+        return out
+
+    def outer(self, plan, w, a, rte_a, b):
+        out = self.new(self.R, self.H, self.dkp, self.dkp, zero=True)
+        name = outer_form(self.dkp)
+        check(getattr(self.lib, name)(*self.graph(plan), self.dkp, _ptr(w), _ptr(a), _ptr(rte_a), _ptr(b), _ptr(out), _stream()), name)
+        return out
+
+    def drop_(self, t, mask):
+        if mask is not None:
+            check(self.lib.hgt_mul_inplace(_ptr(t), _ptr(mask), t.numel(), _stream()), "hgt_mul_inplace")
+
+    # == forward steps (the message path, conv.py:60-111, is shared by both layers) ==========================================
+    def relation_images(self, p):
+        att_t, msg_p = self.pack(p.ratt, p.rmsg, p.rpri)
+        return att_t, msg_p, self.frags(msg_p)
+
+    def project(self, x, p):
+        """Q|K|V once per node (conv.py:96-97,103)."""
+        dp, din = self.dp, self.din
+        qkv = self.new(3, self.N, dp)
+        _typed_linear(self.split, x, din, self.rows.rows_all, self.rows.off_all, self.T, self.N, din, 3 * dp, p.w_qkv, 0, 3 * dp * din,
+                      p.b_qkv, 0, 3 * dp, [qkv[0], qkv[1], qkv[2]], dp)
+        return qkv
+
+    def temporal_tables(self, p):
+        """(rte_k, rte_v): K / V images of the 240 temporal rows per source type (conv.py:91-92,298-299 hoisted off the edges)."""
+        T, dp, din, L = self.T, self.dp, self.din, _lib.HGT_RTE_LEN
+        rr, ro = _rte_row_lists(T, self.dev)
+        rte_lin = self.new(L, din)
+        _typed_linear(self.split, p.rte_emb, din, rr.data_ptr(), ro.data_ptr(), 1, L, din, din, p.rte_w, 0, 0, p.rte_b, 0, 0, [rte_lin], din,
+                      by_pos=1)
+        rte_kv = self.new(2, T * L, dp)
+        _typed_linear(self.split, rte_lin, din, rr.data_ptr(), ro.data_ptr(), T, T * L, din, 2 * dp, p.w_qkv, dp * din, 3 * dp * din, None, 0, 0,
+                      [rte_kv[0], rte_kv[1]], dp, by_pos=1)
+        return rte_kv[0], rte_kv[1]
+
+    def attention(self, Q, K, rte_k, att_t):
+        """(att in plan order, self.att of conv.py:108 in the caller's edge order or None): logits (conv.py:98-99), softmax in place."""
+        att = self.logits(self.plan, Q, K, rte_k, att_t)
+        check(self.lib.hgt_edge_softmax(*self.graph(self.plan), _ptr(att), _stream()), "hgt_edge_softmax")
+        keep = self.layer.keep_att and self.E > 0
+        return att, (self.to_edge_ids(self.plan, att, out_heads=self.layer.n_heads) if keep else None)
+
+    def aggregate(self, att, V, rte_v, msg_p, msg_f):
+        """agg = sum_r (sum_e att_e v_e) M_r (conv.py:104,109-111 + scatter-add)."""
+        agg = self.new(self.N, self.dp)
+        self.spmm(self.plan, att, V.data_ptr(), rte_v, msg_p, msg_f, agg, 0, self.dp, self.N)
+        return agg
+
+    def a_linear(self, agg, p, mask, gelu):
+        """drop(a_linear(gelu(agg))) (HGTConv, conv.py:119-125) or drop(a_linear(agg)) (DenseHGTConv, conv.py:259-261)."""
+        trans = self.new(self.N, self.dout)
+        self.node_linear(agg, self.dp, self.dout, p.w_a, self.dout * self.dp, p.b_a, self.dout, trans, prologue=int(gelu))
+        self.drop_(trans, mask)
+        return trans
+
+    def update_hgt(self, p, x, agg, m1, m2):
+        """HGTConv (conv.py:119-133): a_linear(gelu(agg)) -> dropout -> gated skip -> LayerNorm.  Returns (out, what the backward keeps)."""
+        trans = self.a_linear(agg, p, m1, gelu=True)
+        out = self.new(self.N, self.dout)
+        check(self.lib.hgt_node_update(_ptr(trans), _ptr(x), self.din, _ptr(self.plan.node_type), _ptr(p.skip), _ptr(p.ln_w), _ptr(p.ln_b),
+                                       int(self.use_norm), self.N, self.dout, self.T, _ptr(out), _stream()), "hgt_node_update")
+        return out, dict(trans=trans)
+
+    def update_dense(self, p, x, agg, m1, m2):
+        """DenseHGTConv (conv.py:250-274): y1 = LN_t(drop(a_linear(agg)) + x); out = out_norm(drop(out_linear(gelu(mid_linear(y1)))) + y1)."""
+        lib, N, T, dout, nt = self.lib, self.N, self.T, self.dout, _ptr(self.plan.node_type)
+        trans = self.a_linear(agg, p, m1, gelu=False)
+        y1 = self.new(N, dout)
+        check(lib.hgt_node_update_ex(_ptr(trans), _ptr(x), self.din, nt, None, _ptr(p.ln_w), _ptr(p.ln_b), int(self.use_norm), 0, N, dout, T,
+                                     _ptr(y1), _stream()), "hgt_node_update_ex")
+        off2 = self.new(2, dtype=torch.int32)                # the target rows of every known type as ONE group (the shared dense layer)
+        check(lib.hgt_single_group_offsets(self.rows.off_q, T, _ptr(off2), _stream()), "hgt_single_group_offsets")
+        mid = self.new(N, 2 * dout, zero=True)
+        _typed_linear(self.split, y1, dout, self.rows.rows_q, off2.data_ptr(), 1, N, dout, 2 * dout, p.mid_w, 0, 0, p.mid_b, 0, 0, [mid], 2 * dout)
+        trans2 = self.new(N, dout, zero=True)
+        _typed_linear(self.split, mid, 2 * dout, self.rows.rows_q, off2.data_ptr(), 1, N, 2 * dout, dout, p.out_w, 0, 0, p.out_b, 0, 0, [trans2],
+                      dout, prologue=1)
+        self.drop_(trans2, m2)
+        out = self.new(N, dout)
+        check(lib.hgt_node_update_ex(_ptr(trans2), _ptr(y1), dout, nt, None, _ptr(p.out_ln_w), _ptr(p.out_ln_b), 1, 1, N, dout, T, _ptr(out),
+                                     _stream()), "hgt_node_update_ex")
+        return out, dict(trans=trans, y1=y1, mid=mid, trans2=trans2, off2=off2)
+
+    # == backward steps ======================================================================================================
+    def a_linear_bwd(self, s, d_trans, gelu):
+        """trans = a_linear(f(agg)), f = gelu or identity: (d agg, d w_a, d b_a)."""
+        N, dp, dout = self.N, self.dp, self.dout
+        a_in = torch.nn.functional.gelu(s.agg) if gelu else s.agg                  # exact erf form, conv.py:119
+        d_w_a, d_b_a = _wgrad(self.split, d_trans, dout, a_in, dp, self.rows.rows_q, self.rows.off_q, self.T, N, dout, dp)
+        del a_in
+        dagg = self.new(N, dp)
+        self.node_linear(d_trans, dout, dp, s.w_a.transpose(1, 2).contiguous(), dp * dout, None, 0, dagg)      # [T][dp][dout]
+        if gelu:
+            dg, dagg = dagg, self.new(N, dp)
+            check(self.lib.hgt_gelu_bwd(_ptr(dg), _ptr(s.agg), _ptr(dagg), dagg.numel(), _stream()), "hgt_gelu_bwd")
+        # rows of an unknown type get no a_linear (their agg gradient is zero): typed_linear leaves them unwritten
+        check(self.lib.hgt_zero_rows(self.rows.rows_q, self.rows.off_q + 4 * self.T, dp, _ptr(dagg), _stream()), "hgt_zero_rows")
+        return dagg, d_w_a, d_b_a
+
+    def _ln_grads(self):
+        return [self.new(self.T, self.dout, zero=True) if self.use_norm else None for _ in range(2)]
+
+    def update_hgt_bwd(self, s, gout):
+        """update_hgt in reverse (conv.py:125-133): (d agg, the skip branch of dx, gradients by slot name)."""
+        N, T, din, dout = self.N, self.T, self.din, self.dout
+        d_lnw, d_lnb = self._ln_grads()
+        d_trans, dx_skip = self.new(N, dout), self.new(N, din)
+        d_alpha = self.new(T, zero=True)
+        check(self.lib.hgt_node_update_bwd(_ptr(gout), _ptr(s.trans), _ptr(s.x), din, _ptr(self.plan.node_type), _ptr(s.skip), _ptr(s.ln_w),
+                                           int(self.use_norm), _ptr(s.m1), N, dout, T, _ptr(d_trans), _ptr(dx_skip), din, _ptr(d_alpha),
+                                           _ptr(d_lnw), _ptr(d_lnb), _stream()), "hgt_node_update_bwd")
+        alpha = torch.sigmoid(s.skip)
+        d_skip = d_alpha * alpha * (1.0 - alpha)
+        dagg, d_w_a, d_b_a = self.a_linear_bwd(s, d_trans, gelu=True)
+        return dagg, dx_skip, dict(w_a=d_w_a, b_a=d_b_a, skip=d_skip, ln_w=d_lnw, ln_b=d_lnb)
+
+    def update_dense_bwd(self, s, gout):
+        """update_dense in reverse (conv.py:250-274): (d agg, the residual branch of dx, gradients by slot name)."""
+        lib, N, T, din, dout, nt = self.lib, self.N, self.T, self.din, self.dout, _ptr(self.plan.node_type)
+        rows_q, off2 = self.rows.rows_q, s.off2.data_ptr()
+        d_lnw, d_lnb = self._ln_grads()
+        d_trans, dx_skip = self.new(N, dout), self.new(N, din)
+        d_oln_w, d_oln_b = self.new(1, dout, zero=True), self.new(1, dout, zero=True)
+        d_t2 = self.new(N, dout)                                                      # gradient of out_linear's (dropped) output
+        d_y1 = self.new(N, dout)                                                      # residual branch of y1
+        check(lib.hgt_node_update_bwd_ex(_ptr(gout), _ptr(s.trans2), _ptr(s.y1), dout, nt, None, _ptr(s.out_ln_w), 1, 1, _ptr(s.m2), N, dout, T,
+                                         _ptr(d_t2), _ptr(d_y1), dout, None, _ptr(d_oln_w), _ptr(d_oln_b), _stream()), "hgt_node_update_bwd_ex")
+        g2 = torch.nn.functional.gelu(s.mid)
+        d_out_w, d_out_b = _wgrad(self.split, d_t2, dout, g2, 2 * dout, rows_q, off2, 1, N, dout, 2 * dout)
+        del g2
+        out_w_t = s.out_w.t().contiguous()                                            # [2 dout][dout]
+        d_g2 = self.new(N, 2 * dout, zero=True)
+        _typed_linear(self.split, d_t2, dout, rows_q, off2, 1, N, dout, 2 * dout, out_w_t, 0, 0, None, 0, 0, [d_g2], 2 * dout)
+        d_mid = torch.empty_like(d_g2)
+        check(lib.hgt_gelu_bwd(_ptr(d_g2), _ptr(s.mid), _ptr(d_mid), d_mid.numel(), _stream()), "hgt_gelu_bwd")
+        del d_g2
+        d_mid_w, d_mid_b = _wgrad(self.split, d_mid, 2 * dout, s.y1, dout, rows_q, off2, 1, N, 2 * dout, dout)
+        mid_w_t = s.mid_w.t().contiguous()                                            # [dout][2 dout]
+        d_y1b = self.new(N, dout, zero=True)
+        _typed_linear(self.split, d_mid, 2 * dout, rows_q, off2, 1, N, 2 * dout, dout, mid_w_t, 0, 0, None, 0, 0, [d_y1b], dout)
+        d_y1 += d_y1b
+        del d_mid, d_y1b
+        check(lib.hgt_node_update_bwd_ex(_ptr(d_y1), _ptr(s.trans), _ptr(s.x), din, nt, None, _ptr(s.ln_w), int(self.use_norm), 0, _ptr(s.m1), N,
+                                         dout, T, _ptr(d_trans), _ptr(dx_skip), din, None, _ptr(d_lnw), _ptr(d_lnb), _stream()),
+              "hgt_node_update_bwd_ex")
+        dagg, d_w_a, d_b_a = self.a_linear_bwd(s, d_trans, gelu=False)
+        return dagg, dx_skip, dict(w_a=d_w_a, b_a=d_b_a, ln_w=d_lnw, ln_b=d_lnb, mid_w=d_mid_w[0], mid_b=d_mid_b[0], out_w=d_out_w[0],
+                                   out_b=d_out_b[0], out_ln_w=d_oln_w[0], out_ln_b=d_oln_b[0])
+
+    def attention_bwd(self, s, dagg):
+        """d s, the gradient of the logits in plan order (conv.py:98-111): d att = <dagg_i M^T, v_e>, rho = <dagg, agg> per head, then the
+        softmax backward."""
+        plan, N, E, H = self.plan, self.N, self.E, self.H
+        ones_pri = torch.full((self.R, self.Hreal), math.sqrt(self.dk), dtype=torch.float32, device=self.dev)      # pri / sqrt(dk) == 1
+        m_t, _ = self.pack(s.rmsg, s.rmsg, ones_pri)                                  # m_t[r,h,c,k] = M[r,h,k,c]
+        d_att = self.logits(plan, dagg, s.qkv[2], s.rte_v, m_t)
+        rho = self.new(N, H)
+        check(self.lib.hgt_head_dot(_ptr(dagg), _ptr(s.agg), N, H, self.dkp, _ptr(rho), _stream()), "hgt_head_dot")
+        ds = self.new(E, H)
+        check(self.lib.hgt_edge_softmax_bwd(*self.graph(plan), _ptr(s.att), _ptr(d_att), _ptr(rho), H, _ptr(ds), _stream()),
+              "hgt_edge_softmax_bwd")
+        return ds
+
+    def qkv_bwd(self, s, dagg, ds, scale):
+        """dqkv [N, 3 dp] by three gather passes: dQ over the plan, dK and dV over the transposed plan.  Also returns the
+        (matrices, fragments) of the dK and of the dV pass, which temporal_bwd runs again grouped by table row."""
+        plan, dp, N = self.plan, self.dp, self.N
+        Q, K = s.qkv[0], s.qkv[1]
+        a_s = s.ratt * scale                                                         # A[k][c] * pri / sqrt(dk)
+        dqkv = self.new(N, 3 * dp, zero=True)
+        # dQ_i = sum_r (sum_e ds_e k_e) . (A s)           [out = in . F, F[k][c] = A[k][c] s]
+        _, f_q = self.pack(s.ratt, a_s, s.rpri)
+        self.spmm(plan, ds, K.data_ptr(), s.rte_k, f_q, self.frags(f_q), dqkv, 0, 3 * dp, N)
+        # transposed graph: dK_j = sum_r (sum_e ds_e q_i) . (A s)^T,  dV_j = sum_r (sum_e att_e dagg_i) . M^T
+        plan_t = plan.transposed()
+        ds_t = self.to_sorted(plan_t, self.to_edge_ids(plan, ds))
+        att_tr = self.to_sorted(plan_t, self.to_edge_ids(plan, s.att))
+        _, f_k = self.pack(s.ratt, a_s.transpose(2, 3), s.rpri)
+        f_k = (f_k, self.frags(f_k))
+        self.spmm(plan_t, ds_t, Q.data_ptr(), None, *f_k, dqkv, dp, 3 * dp, N)
+        _, f_v = self.pack(s.ratt, s.rmsg.transpose(2, 3), s.rpri)
+        f_v = (f_v, self.frags(f_v))
+        self.spmm(plan_t, att_tr, dagg.data_ptr(), None, *f_v, dqkv, 2 * dp, 3 * dp, N)
+        return dqkv, f_k, f_v
+
+    def relation_bwd(self, s, dagg, ds, scale):
+        """Gradients of relation_msg / relation_att / relation_pri: two outer products over the edges + the pri / att chain rule."""
+        plan, Hr, dk = self.plan, self.Hreal, self.dk
+        d_msg = self.outer(plan, s.att, s.qkv[2], s.rte_v, dagg)[:, :Hr, :dk, :dk]      # d relation_msg[r,h,k,c]
+        o_att = self.outer(plan, ds, s.qkv[1], s.rte_k, s.qkv[0])[:, :Hr, :dk, :dk]     # sum ds_e k_e[k] q_i[c]
+        return dict(rmsg=d_msg.contiguous(), ratt=o_att * scale, rpri=(o_att * s.ratt).sum(dim=(2, 3)) / math.sqrt(dk))
+
+    def temporal_bwd(self, s, dagg, ds, f_k, f_v):
+        """use_RTE: the gradient of the temporal tables is the dK / dV gather passes grouped by (source type, dt) instead of by source.
+        Returns (gradients by slot name, the tables' share of d w_qkv[:, dp:3dp])."""
+        plan, T, dp = self.plan, self.T, self.dp
+        plan_r, tab = plan.rte_plan(T, self.R)
+        # (ds and att go to edge order a second time: the two [E, H] copies of qkv_bwd are not kept alive across relation_bwd)
+        ds_r = self.to_sorted(plan_r, self.to_edge_ids(plan, ds))
+        att_r = self.to_sorted(plan_r, self.to_edge_ids(plan, s.att))
+        d_tab = self.new(tab, 2 * dp, zero=True)
+        # sources of plan_r are the original TARGETS, shifted by `tab` ids: the row pointer is shifted back
+        self.spmm(plan_r, ds_r, s.qkv[0].data_ptr() - 4 * tab * dp, None, *f_k, d_tab, 0, 2 * dp, tab)
+        self.spmm(plan_r, att_r, dagg.data_ptr() - 4 * tab * dp, None, *f_v, d_tab, dp, 2 * dp, tab)
+        # tables = (emb W_rte^T + b_rte) W_{k|v}[t]^T: chain rule on [T*240, d] arrays with torch ops (tiny)
+        with torch.enable_grad():
+            e_, w_, b_ = (t.detach().requires_grad_(True) for t in (s.rte_emb, s.rte_w, s.rte_b))
+            wkv = s.w_qkv.detach()[:, dp:3 * dp, :].requires_grad_(True)             # [T][2dp][din]
+            lin = e_ @ w_.t() + b_                                                   # [240, din]
+            tabs = torch.einsum("pd,tod->tpo", lin, wkv).reshape(T * _lib.HGT_RTE_LEN, 2 * dp)
+            ge, gw, gb, gkv = torch.autograd.grad(tabs, [e_, w_, b_, wkv], d_tab)
+        return dict(rte_emb=ge, rte_w=gw, rte_b=gb), gkv
+
+    def project_bwd(self, s, dqkv, dx_skip, d_w_kv_tables, want_dx):
+        """project in reverse (conv.py:96-97,103): d w_qkv, d b_qkv and, if asked for, dx (+ the skip / residual branch)."""
+        T, N, dp, din, rows = self.T, self.N, self.dp, self.din, self.rows
+        d_w_qkv, d_b_qkv = _wgrad(self.split, dqkv, 3 * dp, s.x, din, rows.rows_all, rows.off_all, T, N, 3 * dp, din)
+        if d_w_kv_tables is not None:
+            d_w_qkv[:, dp:3 * dp, :] += d_w_kv_tables
+        grads = dict(w_qkv=d_w_qkv, b_qkv=d_b_qkv)
+        if want_dx:
+            w_qkv_t = s.w_qkv.transpose(1, 2).contiguous()                           # [T][din][3dp]
+            dx = self.new(N, din, zero=True)
+            _typed_linear(self.split, dqkv, 3 * dp, rows.rows_all, rows.off_all, T, N, 3 * dp, din, w_qkv_t, 0, din * 3 * dp, None, 0, 0, [dx], din)
+            dx += dx_skip
+            grads["x"] = dx
+        return grads
+
+
 class _HGTConvTrain(torch.autograd.Function):
     """HGTConv / DenseHGTConv forward + backward on the HIP kernels.  The message path (conv.py:60-111) is shared; the update is
     conv.py:114-134 (HGTConv: gelu, a_linear, dropout, gated skip, LayerNorm) or conv.py:250-274 (DenseHGTConv: a_linear, dropout,
     plain residual, LayerNorm, then the shared dense layer with its own dropout and out_norm)."""
 
     @staticmethod
-    def forward(ctx, layer, plan, drop_masks, x, w_qkv, b_qkv, w_a, b_a, ratt, rmsg, rpri, skip, ln_w, ln_b, rte_emb, rte_w, rte_b,
-                mid_w, mid_b, out_w, out_b, oln_w, oln_b):
-        lib = _lib.load()
-        lay = _lib.layout_for(layer.out_dim, layer.n_heads)
-        T, R, H = layer.num_types, layer.num_relations, layer.n_heads
-        ops = _Ops(plan, lay, T, R, H, layer.precision)
-        N, E, din, dout, dp = plan.N, plan.E, layer.in_dim, layer.out_dim, lay.d_pad
-        dev = x.device
-        use_rte, use_norm = bool(layer.use_RTE), bool(layer.use_norm)
-        dense = mid_w is not None
-        rows = plan.row_lists()
-        x = x.contiguous()
-        att_t, msg_p = ops.pack(ratt, rmsg, rpri)
-        msg_f = ops.frags(msg_p)
-        # projections (conv.py:96-97,103 once per node)
-        qkv = torch.empty(3, N, dp, dtype=torch.float32, device=dev)
-        ops.typed_linear(x, din, rows.rows_all, rows.off_all, T, N, din, 3 * dp, w_qkv, 0, 3 * dp * din, b_qkv, 0, 3 * dp,
-                         [qkv[0], qkv[1], qkv[2]], dp)
-        rte_k = rte_v = rte_lin = None
-        if use_rte:     # temporal tables (conv.py:91-92,298-299 hoisted off the edges)
-            rr, ro = _rte_row_lists(T, dev)
-            rte_lin = torch.empty(_lib.HGT_RTE_LEN, din, dtype=torch.float32, device=dev)
-            ops.typed_linear(rte_emb, din, rr.data_ptr(), ro.data_ptr(), 1, _lib.HGT_RTE_LEN, din, din, rte_w, 0, 0, rte_b, 0, 0, [rte_lin], din,
-                             by_pos=1)
-            rte_kv = torch.empty(2, T * _lib.HGT_RTE_LEN, dp, dtype=torch.float32, device=dev)
-            ops.typed_linear(rte_lin, din, rr.data_ptr(), ro.data_ptr(), T, T * _lib.HGT_RTE_LEN, din, 2 * dp, w_qkv, dp * din, 3 * dp * din,
-                             None, 0, 0, [rte_kv[0], rte_kv[1]], dp, by_pos=1)
-            rte_k, rte_v = rte_kv[0], rte_kv[1]
-        # attention (conv.py:98-99,108): logits in sorted edge order, normalised in place
-        att = ops.softmax_(plan, ops.logits(plan, qkv[0], qkv[1], rte_k, att_t))
-        if layer.keep_att and E > 0:      # self.att (conv.py:108) in the caller's edge order, like the inference path
-            a_out = torch.empty(E, layer.n_heads, dtype=torch.float32, device=dev)
-            _chk("hgt_att_export", lib.hgt_att_export(plan.ptr, N, E, T, R, ops.H, _p(att), _p(a_out), layer.n_heads, _st()))
-            layer.att = a_out
-        else:
-            layer.att = None
-        # aggregation (conv.py:104,109-111 + scatter-add): agg = sum_r (sum_e att_e v_e) M_r
-        agg = torch.empty(N, dp, dtype=torch.float32, device=dev)
-        ops.spmm(plan, att, qkv[2].data_ptr(), rte_v, msg_p, msg_f, agg, 0, dp, N)
+    def forward(ctx, layer, plan, drop_masks, *tensors):
+        p = SimpleNamespace(**dict(zip(TENSOR_SLOTS, tensors)))
+        step = _Step(layer, plan, _lib.layout_for(layer.out_dim, layer.n_heads))
+        dense = p.mid_w is not None
+        x = p.x.contiguous()
+        att_t, msg_p, msg_f = step.relation_images(p)
+        qkv = step.project(x, p)
+        rte_k, rte_v = step.temporal_tables(p) if layer.use_RTE else (None, None)
+        att, layer.att = step.attention(qkv[0], qkv[1], rte_k, att_t)
+        agg = step.aggregate(att, qkv[2], rte_v, msg_p, msg_f)
         m1, m2 = drop_masks if drop_masks is not None else (None, None)
-        empty = x.new_empty(0)
-        trans = torch.empty(N, dout, dtype=torch.float32, device=dev)
-        out = torch.empty(N, dout, dtype=torch.float32, device=dev)
-        if not dense:
-            # update (conv.py:119-133): a_linear(gelu(agg)) -> dropout -> gated skip -> LayerNorm
-            ops.typed_linear(agg, dp, rows.rows_q, rows.off_q, T, N, dp, dout, w_a, 0, dout * dp, b_a, 0, dout, [trans], dout, prologue=1)
-            if m1 is not None:
-                _chk("hgt_mul_inplace", lib.hgt_mul_inplace(_p(trans), _p(m1), trans.numel(), _st()))
-            _chk("hgt_node_update", lib.hgt_node_update(_p(trans), _p(x), din, _p(plan.node_type), _p(skip), _p(ln_w), _p(ln_b), int(use_norm),
-                                                      N, dout, T, _p(out), _st()))
-            y1 = mid = trans2 = off2 = empty
-        else:
-            # DenseHGTConv.update (conv.py:250-274): y1 = LN_t(drop(a_linear(agg)) + x); out = out_norm(drop(out_linear(gelu(mid_linear(y1)))) + y1)
-            ops.typed_linear(agg, dp, rows.rows_q, rows.off_q, T, N, dp, dout, w_a, 0, dout * dp, b_a, 0, dout, [trans], dout)
-            if m1 is not None:
-                _chk("hgt_mul_inplace", lib.hgt_mul_inplace(_p(trans), _p(m1), trans.numel(), _st()))
-            y1 = torch.empty(N, dout, dtype=torch.float32, device=dev)
-            _chk("hgt_node_update_ex", lib.hgt_node_update_ex(_p(trans), _p(x), din, _p(plan.node_type), None, _p(ln_w), _p(ln_b),
-                                                            int(use_norm), 0, N, dout, T, _p(y1), _st()))
-            off2 = torch.empty(2, dtype=torch.int32, device=dev)
-            _chk("hgt_single_group_offsets", lib.hgt_single_group_offsets(rows.off_q, T, _p(off2), _st()))
-            mid = torch.zeros(N, 2 * dout, dtype=torch.float32, device=dev)
-            ops.typed_linear(y1, dout, rows.rows_q, off2.data_ptr(), 1, N, dout, 2 * dout, mid_w, 0, 0, mid_b, 0, 0, [mid], 2 * dout)
-            trans2 = torch.zeros(N, dout, dtype=torch.float32, device=dev)
-            ops.typed_linear(mid, 2 * dout, rows.rows_q, off2.data_ptr(), 1, N, 2 * dout, dout, out_w, 0, 0, out_b, 0, 0, [trans2], dout,
-                             prologue=1)
-            if m2 is not None:
-                _chk("hgt_mul_inplace", lib.hgt_mul_inplace(_p(trans2), _p(m2), trans2.numel(), _st()))
-            _chk("hgt_node_update_ex", lib.hgt_node_update_ex(_p(trans2), _p(y1), dout, _p(plan.node_type), None, _p(oln_w), _p(oln_b), 1, 1,
-                                                            N, dout, T, _p(out), _st()))
-        ctx.layer, ctx.plan, ctx.lay = layer, plan, lay
-        ctx.use_rte, ctx.use_norm, ctx.dense = use_rte, use_norm, dense
-        ctx.save_for_backward(x, w_qkv, w_a, ratt, rmsg, rpri, skip if skip is not None else empty, ln_w if ln_w is not None else empty,
-                              rte_emb, rte_w, rte_b, qkv, att, agg, trans,
-                              m1 if m1 is not None else empty, m2 if m2 is not None else empty, rte_k if use_rte else empty,
-                              rte_v if use_rte else empty, y1, mid, trans2, off2,
-                              mid_w if dense else empty, out_w if dense else empty, oln_w if dense else empty)
+        out, kept = (step.update_dense if dense else step.update_hgt)(p, x, agg, m1, m2)
+        ctx.layer, ctx.plan, ctx.lay, ctx.dense = layer, plan, step.lay, dense
+        _save_named(ctx, dict(x=x, w_qkv=p.w_qkv, w_a=p.w_a, ratt=p.ratt, rmsg=p.rmsg, rpri=p.rpri, skip=p.skip, ln_w=p.ln_w,
+                              rte_emb=p.rte_emb, rte_w=p.rte_w, rte_b=p.rte_b, mid_w=p.mid_w, out_w=p.out_w, out_ln_w=p.out_ln_w,
+                              qkv=qkv, att=att, agg=agg, rte_k=rte_k, rte_v=rte_v, m1=m1, m2=m2, **kept))
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        layer, plan, lay = ctx.layer, ctx.plan, ctx.lay
-        (x, w_qkv, w_a, ratt, rmsg, rpri, skip, ln_w, rte_emb, rte_w, rte_b, qkv, att, agg, trans, m1, m2, rte_k, rte_v, y1, mid, trans2,
-         off2, mid_w, out_w, oln_w) = ctx.saved_tensors
-        lib = _lib.load()
-        T, R, H = layer.num_types, layer.num_relations, layer.n_heads
-        ops = _Ops(plan, lay, T, R, H, layer.precision)
-        # (data gradients d gelu(agg), dx run on the layer's own typed-linear kernels: split-bf16 x3 by default, relative error
-        #  ~1e-5, two orders below the gradient tolerance; precision='fp32' layers keep the exact typed-linear kernel.  The
-        #  relation transforms of every hgt_edge_spmm -- the training forward's aggregation included -- are ALWAYS split-bf16 MFMA
-        #  products under grad, also for precision='fp32': ~1e-5 away from the exact VALU aggregation of the inference path)
-        N, E, din, dout, dp, dk, dkp = plan.N, plan.E, layer.in_dim, layer.out_dim, lay.d_pad, lay.d_k, lay.dk_pad
-        Hr, H = H, lay.heads                                 # model heads / layout heads
-        dev = x.device
-        use_rte, use_norm, dense = ctx.use_rte, ctx.use_norm, ctx.dense
-        rows = plan.row_lists()
-        gout = gout.contiguous().float()
-        m1 = None if m1.numel() == 0 else m1
-        m2 = None if m2.numel() == 0 else m2
-        if not use_rte:
-            rte_k = rte_v = None
-        Q, K, V = qkv[0], qkv[1], qkv[2]
-        d_skip = d_mid_w = d_mid_b = d_out_w = d_out_b = d_oln_w = d_oln_b = None
-        d_lnw = torch.zeros(T, dout, dtype=torch.float32, device=dev) if use_norm else None
-        d_lnb = torch.zeros(T, dout, dtype=torch.float32, device=dev) if use_norm else None
-        d_trans = torch.empty(N, dout, dtype=torch.float32, device=dev)
-        dx_skip = torch.empty(N, din, dtype=torch.float32, device=dev)
-        dagg = torch.empty(N, dp, dtype=torch.float32, device=dev)
-        w_a_t = w_a.transpose(1, 2).contiguous()                                     # [T][dp][dout]
-        if not dense:
-            # ---- update backward (conv.py:125-133)
-            d_alpha = torch.zeros(T, dtype=torch.float32, device=dev)
-            _chk("hgt_node_update_bwd", lib.hgt_node_update_bwd(_p(gout), _p(trans), _p(x), din, _p(plan.node_type), _p(skip), _p(ln_w),
-                                                              int(use_norm), _p(m1), N, dout, T, _p(d_trans), _p(dx_skip), din,
-                                                              _p(d_alpha), _p(d_lnw), _p(d_lnb), _st()))
-            alpha = torch.sigmoid(skip)
-            d_skip = d_alpha * alpha * (1.0 - alpha)
-            # a_linear: trans = gelu(agg) W_a^T + b_a
-            g = torch.nn.functional.gelu(agg)                                       # exact erf form, conv.py:119
-            d_w_a, d_b_a = ops.wgrad(d_trans, dout, g, dp, rows.rows_q, rows.off_q, T, N, dout, dp, with_colsum=True)
-            del g
-            dg = torch.empty(N, dp, dtype=torch.float32, device=dev)
-            ops.typed_linear(d_trans, dout, rows.rows_q, rows.off_q, T, N, dout, dp, w_a_t, 0, dp * dout, None, 0, 0, [dg], dp)
-            _chk("hgt_gelu_bwd", lib.hgt_gelu_bwd(_p(dg), _p(agg), _p(dagg), dagg.numel(), _st()))
-            del dg
-        else:
-            # ---- DenseHGTConv.update backward (conv.py:250-274 in reverse)
-            d_oln_w = torch.zeros(1, dout, dtype=torch.float32, device=dev)
-            d_oln_b = torch.zeros(1, dout, dtype=torch.float32, device=dev)
-            d_t2 = torch.empty(N, dout, dtype=torch.float32, device=dev)           # gradient of out_linear's (dropped) output
-            d_y1 = torch.empty(N, dout, dtype=torch.float32, device=dev)           # residual branch of y1
-            _chk("hgt_node_update_bwd_ex", lib.hgt_node_update_bwd_ex(_p(gout), _p(trans2), _p(y1), dout, _p(plan.node_type), None, _p(oln_w),
-                                                                    1, 1, _p(m2), N, dout, T, _p(d_t2), _p(d_y1), dout, None, _p(d_oln_w),
-                                                                    _p(d_oln_b), _st()))
-            g2 = torch.nn.functional.gelu(mid)
-            d_out_w, d_out_b = ops.wgrad(d_t2, dout, g2, 2 * dout, rows.rows_q, off2.data_ptr(), 1, N, dout, 2 * dout, with_colsum=True)
-            del g2
-            out_w_t = out_w.t().contiguous()                                           # [2 dout][dout]
-            d_g2 = torch.zeros(N, 2 * dout, dtype=torch.float32, device=dev)
-            ops.typed_linear(d_t2, dout, rows.rows_q, off2.data_ptr(), 1, N, dout, 2 * dout, out_w_t, 0, 0, None, 0, 0, [d_g2], 2 * dout)
-            d_mid = torch.empty_like(d_g2)
-            _chk("hgt_gelu_bwd", lib.hgt_gelu_bwd(_p(d_g2), _p(mid), _p(d_mid), d_mid.numel(), _st()))
-            del d_g2
-            d_mid_w, d_mid_b = ops.wgrad(d_mid, 2 * dout, y1, dout, rows.rows_q, off2.data_ptr(), 1, N, 2 * dout, dout, with_colsum=True)
-            mid_w_t = mid_w.t().contiguous()                                           # [dout][2 dout]
-            d_y1b = torch.zeros(N, dout, dtype=torch.float32, device=dev)
-            ops.typed_linear(d_mid, 2 * dout, rows.rows_q, off2.data_ptr(), 1, N, 2 * dout, dout, mid_w_t, 0, 0, None, 0, 0, [d_y1b], dout)
-            d_y1 += d_y1b
-            del d_mid, d_y1b
-            _chk("hgt_node_update_bwd_ex", lib.hgt_node_update_bwd_ex(_p(d_y1), _p(trans), _p(x), din, _p(plan.node_type), None, _p(ln_w),
-                                                                    int(use_norm), 0, _p(m1), N, dout, T, _p(d_trans), _p(dx_skip), din,
-                                                                    None, _p(d_lnw), _p(d_lnb), _st()))
-            d_w_a, d_b_a = ops.wgrad(d_trans, dout, agg, dp, rows.rows_q, rows.off_q, T, N, dout, dp, with_colsum=True)
-            ops.typed_linear(d_trans, dout, rows.rows_q, rows.off_q, T, N, dout, dp, w_a_t, 0, dp * dout, None, 0, 0, [dagg], dp)
-            d_oln_w, d_oln_b = d_oln_w[0], d_oln_b[0]
-            d_out_w, d_out_b, d_mid_w, d_mid_b = d_out_w[0], d_out_b[0], d_mid_w[0], d_mid_b[0]
-        # rows of an unknown type get no a_linear (their agg gradient is zero): typed_linear leaves them unwritten
-        _chk("hgt_zero_rows", lib.hgt_zero_rows(rows.rows_q, rows.off_q + 4 * T, dp, _p(dagg), _st()))
-
-        # ---- aggregation / attention backward (conv.py:98-111)
-        sqrt_dk = math.sqrt(dk)
-        ones_pri = torch.full((R, Hr), sqrt_dk, dtype=torch.float32, device=dev)    # pri / sqrt(dk) == 1
-        m_t, _ = ops.pack(rmsg, rmsg, ones_pri)                                      # m_t[r,h,c,k] = M[r,h,k,c]
-        d_att = ops.logits(plan, dagg, V, rte_v, m_t)                                # <dagg_i M^T, v_e>
-        rho = torch.empty(N, H, dtype=torch.float32, device=dev)
-        _chk("hgt_head_dot", lib.hgt_head_dot(_p(dagg), _p(agg), N, H, dkp, _p(rho), _st()))
-        ds = torch.empty(E, H, dtype=torch.float32, device=dev)
-        _chk("hgt_edge_softmax_bwd", lib.hgt_edge_softmax_bwd(plan.ptr, N, E, T, R, H, _p(att), _p(d_att), _p(rho), H, _p(ds), _st()))
-        del d_att
-        scale = (rpri / sqrt_dk).view(R, Hr, 1, 1)
-        a_s = ratt * scale                                                           # A[k][c] * pri / sqrt(dk)
-        dqkv = torch.zeros(N, 3 * dp, dtype=torch.float32, device=dev)
-        # dQ_i = sum_r (sum_e ds_e k_e) . (A s)           [out = in . F, F[k][c] = A[k][c] s]
-        _, f_q = ops.pack(ratt, a_s, rpri)
-        ops.spmm(plan, ds, K.data_ptr(), rte_k, f_q, ops.frags(f_q), dqkv, 0, 3 * dp, N)
-        # transposed graph: dK_j = sum_r (sum_e ds_e q_i) . (A s)^T,  dV_j = sum_r (sum_e att_e dagg_i) . M^T
-        plan_t = plan.transposed()
-        ds_t = ops.to_sorted(plan_t, ops.to_edge_ids(plan, ds))
-        att_tr = ops.to_sorted(plan_t, ops.to_edge_ids(plan, att))
-        _, f_k = ops.pack(ratt, a_s.transpose(2, 3), rpri)
-        ops.spmm(plan_t, ds_t, Q.data_ptr(), None, f_k, ops.frags(f_k), dqkv, dp, 3 * dp, N)
-        _, f_v = ops.pack(ratt, rmsg.transpose(2, 3), rpri)
-        ops.spmm(plan_t, att_tr, dagg.data_ptr(), None, f_v, ops.frags(f_v), dqkv, 2 * dp, 3 * dp, N)
-        # relation parameters
-        d_msg = ops.outer(plan, att, V, rte_v, dagg)[:, :Hr, :dk, :dk]               # d relation_msg[r,h,k,c]
-        o_att = ops.outer(plan, ds, K, rte_k, Q)[:, :Hr, :dk, :dk]                   # sum ds_e k_e[k] q_i[c]
-        d_ratt = o_att * scale
-        d_rpri = (o_att * ratt).sum(dim=(2, 3)) / sqrt_dk
-
-        # ---- temporal tables (use_RTE): their gradient is the same two spmm's grouped by (source type, dt) instead of by source
-        d_rte_emb = d_rte_w = d_rte_b = None
-        d_w_qkv_extra = None
-        if use_rte:
-            plan_r, tab = plan.rte_plan(T, R)
-            ds_r = ops.to_sorted(plan_r, ops.to_edge_ids(plan, ds))
-            att_r = ops.to_sorted(plan_r, ops.to_edge_ids(plan, att))
-            d_tab = torch.zeros(tab, 2 * dp, dtype=torch.float32, device=dev)
-            # sources of plan_r are the original TARGETS, shifted by `tab` ids: the row pointer is shifted back
-            ops.spmm(plan_r, ds_r, Q.data_ptr() - 4 * tab * dp, None, f_k, ops.frags(f_k), d_tab, 0, 2 * dp, tab)
-            ops.spmm(plan_r, att_r, dagg.data_ptr() - 4 * tab * dp, None, f_v, ops.frags(f_v), d_tab, dp, 2 * dp, tab)
-            # tables = (emb W_rte^T + b_rte) W_{k|v}[t]^T: chain rule on [T*240, d] arrays with torch ops (tiny)
-            with torch.enable_grad():
-                e_, w_, b_ = (t.detach().requires_grad_(True) for t in (rte_emb, rte_w, rte_b))
-                wkv = w_qkv.detach()[:, dp:3 * dp, :].requires_grad_(True)           # [T][2dp][din]
-                lin = e_ @ w_.t() + b_                                               # [240, din]
-                tabs = torch.einsum("pd,tod->tpo", lin, wkv).reshape(T * _lib.HGT_RTE_LEN, 2 * dp)
-                ge, gw, gb, gkv = torch.autograd.grad(tabs, [e_, w_, b_, wkv], d_tab)
-            d_rte_emb, d_rte_w, d_rte_b = ge, gw, gb
-            d_w_qkv_extra = gkv
-
-        # ---- projections backward (conv.py:96-97,103)
-        d_w_qkv, d_b_qkv = ops.wgrad(dqkv, 3 * dp, x, din, rows.rows_all, rows.off_all, T, N, 3 * dp, din, with_colsum=True)
-        if d_w_qkv_extra is not None:
-            d_w_qkv[:, dp:3 * dp, :] += d_w_qkv_extra
-        dx = None
-        if ctx.needs_input_grad[3]:
-            w_qkv_t = w_qkv.transpose(1, 2).contiguous()                             # [T][din][3dp]
-            dx = torch.zeros(N, din, dtype=torch.float32, device=dev)
-            ops.typed_linear(dqkv, 3 * dp, rows.rows_all, rows.off_all, T, N, 3 * dp, din, w_qkv_t, 0, din * 3 * dp, None, 0, 0, [dx], din)
-            dx += dx_skip
-        return (None, None, None, dx, d_w_qkv, d_b_qkv, d_w_a, d_b_a, d_ratt, d_msg.contiguous(), d_rpri, d_skip, d_lnw, d_lnb,
-                d_rte_emb, d_rte_w, d_rte_b, d_mid_w, d_mid_b, d_out_w, d_out_b, d_oln_w, d_oln_b)
+        s = _load_named(ctx)
+        step = _Step(ctx.layer, ctx.plan, ctx.lay)
+        dagg, dx_skip, grads = (step.update_dense_bwd if ctx.dense else step.update_hgt_bwd)(s, gout.contiguous().float())
+        ds = step.attention_bwd(s, dagg)
+        scale = (s.rpri / math.sqrt(step.dk)).view(step.R, step.Hreal, 1, 1)
+        dqkv, f_k, f_v = step.qkv_bwd(s, dagg, ds, scale)
+        grads.update(step.relation_bwd(s, dagg, ds, scale))
+        d_w_kv_tables = None
+        if ctx.layer.use_RTE:
+            rte_grads, d_w_kv_tables = step.temporal_bwd(s, dagg, ds, f_k, f_v)
+            grads.update(rte_grads)
+        grads.update(step.project_bwd(s, dqkv, dx_skip, d_w_kv_tables, ctx.needs_input_grad[len(PLAIN_SLOTS) + TENSOR_SLOTS.index("x")]))
+        assert set(grads) <= set(TENSOR_SLOTS), sorted(set(grads) - set(TENSOR_SLOTS))
+        return (None,) * len(PLAIN_SLOTS) + tuple(grads.get(k) for k in TENSOR_SLOTS)
 
 
 def hgt_conv_train(layer, plan, x, packed, drop_p):
@@ -450,10 +528,9 @@ def hgt_conv_train(layer, plan, x, packed, drop_p):
         else:
             draw = lambda: torch.bernoulli(torch.full((plan.N, layer.out_dim), keep, dtype=torch.float32, device=x.device)) / keep
         masks = (draw(), draw() if dense else None)          # DenseHGTConv drops twice (conv.py:261 and conv.py:273)
-    return _HGTConvTrain.apply(layer, plan, masks, x, packed["w_qkv"], packed["b_qkv"], packed["w_a"], packed["b_a"], packed["ratt"],
-                               packed["rmsg"], packed["rpri"], packed.get("skip"), packed.get("ln_w"), packed.get("ln_b"),
-                               packed.get("rte_emb"), packed.get("rte_w"), packed.get("rte_b"), packed.get("mid_w"), packed.get("mid_b"),
-                               packed.get("out_w"), packed.get("out_b"), packed.get("out_ln_w"), packed.get("out_ln_b"))
+    inputs = dict(packed, x=x)
+    assert all(k in TENSOR_SLOTS for k, t in inputs.items() if torch.is_tensor(t)), "a packed parameter without a slot in TENSOR_SLOTS"
+    return _HGTConvTrain.apply(layer, plan, masks, *(inputs.get(k) for k in TENSOR_SLOTS))
 
 
 class TypedLinearFunction(torch.autograd.Function):
@@ -463,51 +540,32 @@ class TypedLinearFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan_rows, n_groups, precision, x, w, b):
         # plan_rows = (rows ptr, off ptr, keep-alive object); w [G][n_out][k], b [G][n_out]
-        lib = _lib.load()
         rows, off, _keep = plan_rows
         x = x.contiguous()
         n, k = x.shape
         n_out = w.shape[1]
         y = torch.zeros(n, n_out, dtype=torch.float32, device=x.device)
         wc, bc = w.contiguous(), (b.contiguous() if b is not None else None)
-        if precision in ("bf16x3", "f16x3") and n_out % 4 == 0:
-            nb = C.c_uint64()
-            _chk("hgt_split_weights_bytes", lib.hgt_split_weights_bytes(n_groups, k, n_out, C.byref(nb)))
-            tiles = torch.empty(int(nb.value), dtype=torch.uint8, device=x.device)
-            _chk("hgt_split_weights", lib.hgt_split_weights(_p(wc), n_out * k, n_groups, k, n_out, _p(tiles), _st()))
-            _chk("hgt_typed_linear_bf16x3", lib.hgt_typed_linear_bf16x3(_p(x), k, rows, off, n_groups, n, k, n_out, _p(tiles), _p(bc), n_out,
-                                                                      _p(y), 0, 0, n_out, 0, 0, _st()))
-            tiles.record_stream(torch.cuda.current_stream())
-        else:
-            _chk("hgt_typed_linear", lib.hgt_typed_linear(_p(x), k, rows, off, n_groups, n, k, n_out, _p(wc), n_out * k, _p(bc), n_out, _p(y), 0, 0,
-                                                        n_out, 0, 0, 0, _st()))
-        ctx.plan_rows, ctx.n_groups, ctx.has_bias, ctx.precision = plan_rows, n_groups, b is not None, precision
+        _typed_linear(precision in _SPLIT, x, k, rows, off, n_groups, n, k, n_out, wc, 0, n_out * k, bc, 0, n_out, [y], n_out)
+        ctx.plan_rows, ctx.n_groups, ctx.has_bias, ctx.split = plan_rows, n_groups, b is not None, precision in _SPLIT
         ctx.save_for_backward(x, wc)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         rows, off, _keep = ctx.plan_rows
         x, w = ctx.saved_tensors
         G = ctx.n_groups
         gy = gy.contiguous().float()
         n, k = x.shape
         n_out = w.shape[1]
-        dev = x.device
-        dw = torch.zeros(G, n_out, k, dtype=torch.float32, device=dev)
-        db = torch.zeros(G, n_out, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        if ctx.precision in ("bf16x3", "f16x3"):
-            _chk("hgt_typed_wgrad_bf16x3", lib.hgt_typed_wgrad_bf16x3(_p(gy), n_out, _p(x), k, rows, off, G, n, n_out, k, _p(dw), n_out * k,
-                                                                    _p(db), n_out, _st()))
-        else:
-            _chk("hgt_typed_wgrad", lib.hgt_typed_wgrad(_p(gy), n_out, _p(x), k, rows, off, G, n, n_out, k, _p(dw), n_out * k, _st()))
-            if ctx.has_bias:
-                _chk("hgt_typed_colsum", lib.hgt_typed_colsum(_p(gy), n_out, rows, off, G, n, n_out, _p(db), n_out, _st()))
+        dw, db = _wgrad(ctx.split, gy, n_out, x, k, rows, off, G, n, n_out, k, with_colsum=ctx.has_bias)
         dx = None
         if ctx.needs_input_grad[3]:
             wt = w.transpose(1, 2).contiguous()
-            dx = torch.zeros(n, k, dtype=torch.float32, device=dev)
-            _chk("hgt_typed_linear", lib.hgt_typed_linear(_p(gy), n_out, rows, off, G, n, n_out, k, _p(wt), k * n_out, 0, 0, _p(dx), 0, 0, k, 0, 0,
-                                                        0, _st()))
+            dx = torch.zeros(n, k, dtype=torch.float32, device=x.device)
+            # split=False for every precision, unlike the layer's own data gradients: this input gradient has always run on the exact
+            # fp32 kernel (the heads are 'fp32' anyway; the adapter's is asked for only when the features themselves require grad),
+            # and moving it to the split kernel would change results
+            _typed_linear(False, gy, n_out, rows, off, G, n, n_out, k, wt, 0, k * n_out, None, 0, 0, [dx], k)
         return None, None, None, dx, dw, db

@@ -11,6 +11,7 @@ import torch
 
 from oracle import hgt_oracle as O
 from pyhgt_amd import HGTConv, GNN, GraphPlan, _lib
+from pyhgt_amd.autograd import spmm_takes_items
 from pyhgt_amd.synth import synthetic_typed_graph
 
 pytestmark = pytest.mark.gpu
@@ -357,10 +358,12 @@ def test_training_path_mid_size_sampled(case):
     backward kernels that only depend on the graph size, each asserted here so that a retuned threshold fails loudly."""
     from pyhgt_amd import DenseHGTConv
     name, conv, T, R, H, d, N, E, use_norm, use_RTE, gk, (rpw, ipw, gather) = case
-    # the branch predicates: hgt_backward.hip:695 (rows per wavefront), hgt_backward.hip:656 (relation-outer items), autograd.py:139
+    # the branch predicates: node_update_bwd_impl (rows per wavefront) and LaunchOuter::run (relation-outer items) of
+    # csrc/hgt_backward.hip, autograd.spmm_takes_items over the (row stride, first column) of a layer's gather passes: agg, dQ | dK | dV
+    dp = _lib.layout_for(d, H).d_pad
     assert (32 if N >= 65536 else (8 if N >= 16384 else 2)) == rpw
     assert (2 if _max_items(N, E, T, R) < 16384 else 16) == ipw
-    assert ("items" if (N < 65536 and R < 64) else "sub_tile") == gather
+    assert {spmm_takes_items(N, E, R, ld, col) for ld, col in ((dp, 0), (3 * dp, 0), (3 * dp, dp), (3 * dp, 2 * dp))} == {gather == "items"}
     graph = _mid_graph(N, E, T, R, d, seed=N + R, **gk)
     sd = O.make_state_dict(d, d, T, R, H, use_norm, use_RTE, seed=13, dense=conv == "dense")
     cls = DenseHGTConv if conv == "dense" else HGTConv

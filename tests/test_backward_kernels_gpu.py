@@ -10,6 +10,7 @@ import torch
 
 from oracle import backward_primitives as BP
 from pyhgt_amd import GraphPlan, _lib
+from pyhgt_amd.autograd import spmm_takes_items
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -54,7 +55,7 @@ def _randn(shape, g):
 # hgt_node_update_bwd / hgt_node_update_bwd_ex
 # ------------------------------------------------------------------------------------------------------------------------------
 def nub_rows_per_wave(n_rows):
-    # mirrors node_update_bwd_impl, pyhgt_amd/csrc/hgt_backward.hip:695
+    # mirrors node_update_bwd_impl of pyhgt_amd/csrc/hgt_backward.hip
     return 32 if n_rows >= 65536 else (8 if n_rows >= 16384 else 2)
 
 
@@ -207,12 +208,12 @@ def _to_edge_ids(plan, sorted_vals, T, R):
 # hgt_relation_outer
 # ------------------------------------------------------------------------------------------------------------------------------
 def outer_items_per_wave_factor(max_items):
-    # mirrors LaunchOuter::run, pyhgt_amd/csrc/hgt_backward.hip:656: 2 (R + 1) items per wavefront below 16 384 items, else 16 (R + 1)
+    # mirrors LaunchOuter::run of pyhgt_amd/csrc/hgt_backward.hip: 2 (R + 1) items per wavefront below 16 384 items, else 16 (R + 1)
     return 2 if max_items < 16384 else 16
 
 
 def outer_form(lay):
-    # mirrors hgt_relation_outer (hgt_backward.hip:825-826) + LaunchOuter (hgt_backward.hip:651,659): the split of a head over lanes
+    # mirrors hgt_relation_outer + LaunchOuter::run of hgt_backward.hip: the split of a head over lanes
     lph = 64 // lay.heads
     vec, l2 = lay.dk_pad // lph, lph
     while vec * lay.dk_pad > 128 and vec > 1 and l2 * 2 <= 64:
@@ -305,8 +306,10 @@ SPMM_CASES = [
 
 
 def test_spmm_cases_straddle_the_gather_pass_threshold():
-    # autograd's choice between the two kernels (pyhgt_amd/autograd.py:139): hgt_edge_spmm_items below 65 536 nodes
-    assert {c[5] < 65536 for c in SPMM_CASES} == {True, False}
+    # autograd's choice between the two kernels (autograd.spmm_takes_items): hgt_edge_spmm_items below 65 536 nodes; the cases write
+    # the second d_pad-wide block of rows of 2 d_pad columns
+    takes = {spmm_takes_items(c[5], c[6], c[4], 2 * _layout(c[1], c[2]).d_pad, _layout(c[1], c[2]).d_pad) for c in SPMM_CASES}
+    assert takes == {c[5] < 65536 for c in SPMM_CASES} == {True, False}
     assert {c[7] for c in SPMM_CASES} == {True, False}
 
 

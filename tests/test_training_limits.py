@@ -7,7 +7,7 @@ import re
 import pytest
 
 from pyhgt_amd import _lib
-from pyhgt_amd.autograd import MAX_TRAIN_DK_PAD, training_supported
+from pyhgt_amd.autograd import MAX_TRAIN_DK_PAD, logits_form, outer_form, training_supported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -22,12 +22,14 @@ TOO_WIDE = [(512, 1), (1024, 2)]
 def test_wide_heads_train(d, H, dkp):
     lay = _lib.layout_for(d, H)
     assert lay.dk_pad == dkp and lay.d_pad <= 1024
+    assert outer_form(dkp) == "hgt_relation_outer_wide" and logits_form(dkp) == "mfma"
     assert training_supported(d, H) == (True, "")
 
 
 @pytest.mark.parametrize("d,H", NARROW)
 def test_narrow_heads_still_train(d, H):
     assert _lib.layout_for(d, H).dk_pad <= 64
+    assert outer_form(_lib.layout_for(d, H).dk_pad) == "hgt_relation_outer" and logits_form(_lib.layout_for(d, H).dk_pad) == "valu"
     assert training_supported(d, H) == (True, "")
 
 

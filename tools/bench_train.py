@@ -18,7 +18,8 @@ def training_step_bytes(N, E, d, H):
     """Algorithmic HBM bytes of one training step of HGTConv (4-argument form, LayerNorm on) in the same minimal-traffic convention
     as the forward's SURVEY 8(d) model: every kernel reads its inputs and writes its outputs once, every edge gathers one 4d-byte
     row per gather pass (no cache-reuse credit), ids cost 12 B per edge and pass, weights are ignored.  Kernel by kernel, in the
-    order pyhgt_amd/autograd.py enqueues them."""
+    order the steps of pyhgt_amd/autograd.py enqueue them: project, attention, aggregate, update_hgt; then update_hgt_bwd,
+    attention_bwd, qkv_bwd, relation_bwd, project_bwd."""
     Nd, EH, Eg = N * 4 * d, E * H * 4, E * (4 * d + 12)          # one fp32 feature array / one per-edge-per-head array / one gather pass
     fwd = {"project_qkv": 4 * Nd, "edge_logits": Eg + Nd + EH, "edge_softmax": 2 * EH, "edge_aggregate": Eg + EH + Nd,
            "a_linear": 2 * Nd, "node_update": 3 * Nd}
