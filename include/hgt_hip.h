@@ -616,9 +616,17 @@ typedef struct hgt_conv_args {
 #define HGT_FLAG_VALU_AGGREGATE  2   /* relation transforms of the aggregation on the vector ALU (round-1 kernel) instead of MFMA */
 #define HGT_FLAG_MFMA_LOGITS     4   /* hgt_edge_logits_mfma for every layout it covers (default: d_k >= 64 only) */
 #define HGT_FLAG_VALU_LOGITS     8   /* never hgt_edge_logits_mfma */
-#define HGT_FLAG_ITEM_AGGREGATE 16   /* hgt_edge_aggregate_items wherever it applies (the default below 65536 nodes when its scratch is at most 1 GB) */
+#define HGT_FLAG_ITEM_AGGREGATE 16   /* hgt_edge_aggregate_items wherever it applies.  It applies -- and is the default -- when ALL of these hold: a split
+                                      * precision; fewer than 65536 NODES (n_nodes: the workspace only then holds its scratch) and fewer than 65536
+                                      * targets (n_q_rows); a scratch of at most 1 GiB (hgt_edge_aggregate_items_bytes <= 1 << 30: ~986 k edges at
+                                      * 256 padded columns); fewer than 64 relations; a workspace that was sized with the scratch (options bit 0 of
+                                      * hgt_conv_workspace_bytes_ex).  Rows wider than 512 padded columns are refused by the kernel itself and take
+                                      * the sub-tile kernel.  Below 16384 targets it runs alone, from there on only where the fused kernel does not
+                                      * (rows wider than 256 padded columns, DenseHGTConv, HGT_FLAG_NO_FUSED_UPDATE).  With both size defaults at
+                                      * 65536 the flag changes nothing today. */
 #define HGT_FLAG_NO_ITEM_AGGREGATE 32 /* never hgt_edge_aggregate_items */
-#define HGT_FLAG_FUSED_ANY_SIZE 64   /* hgt_edge_aggregate_update below its default size too (>= 16384 targets) */
+#define HGT_FLAG_FUSED_ANY_SIZE 64   /* hgt_edge_aggregate_update below its default size too (default: n_q_rows >= 16384 -- targets, not nodes --, a
+                                      * split precision, HGTConv, rows of at most 256 padded columns, fewer than 64 relations) */
 #define HGT_FLAG_SINGLE_PASS 256     /* LAB builds only (ignored otherwise: the two-kernel form runs).  ABI 6: hgt_edge_single_pass_items instead of logits + item-parallel aggregation where it applies (sampled
                                       * sub-graphs, attention weights not exported).  Off by default: measured equal at c3 and 5 % slower at c5
                                       * (its two LDS tiles cap it at 4 wavefronts per CU) */
