@@ -44,6 +44,9 @@ int hgt_abi_version(void);
  * csrc/lab/ (make LAB=1) -- only then do HGT_FLAG_RING_AGGREGATE / HGT_FLAG_SINGLE_PASS select anything; the shipped library is
  * built without them and ignores both flags. */
 #define HGT_FEATURE_LAB_KERNELS 1
+/* Bit 1: the atomic-free training entry points (hgt_*_det below): every reduction of the backward pass in an order fixed by the
+ * problem sizes alone. */
+#define HGT_FEATURE_DETERMINISTIC_TRAINING 2
 int hgt_build_features(void);
 
 /* ----------------------------------------------------------------------------------------------
@@ -513,6 +516,55 @@ int hgt_typed_wgrad_bf16x3(const float* A, int64_t lda, const float* B, int64_t 
                            float* colsum, int64_t colsum_group_stride, void* stream);
 int hgt_typed_colsum(const float* A, int64_t lda, const int32_t* rows, const int32_t* group_off, int32_t n_groups, int64_t n_rows,
                      int32_t m, float* out, int64_t out_group_stride, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Bit-reproducible training (hgt_build_features() & HGT_FEATURE_DETERMINISTIC_TRAINING): a `_det` form of every entry point above
+ * that sums with fp32 atomics (the reference's `loss.backward()`, OAG/train_paper_field.py:249, leaves the order to autograd's
+ * scatter-adds; a seeded run here repeats bit for bit).  Two launches on the stream instead of atomics: stage one writes each
+ * slot's partial result with plain stores into `ws`, stage two (one small kernel) sums the slots in slot order.  The number of
+ * slots and the rows / work items of a slot are a function of the ARGUMENTS of the matching `*_det_bytes` call alone (never of the
+ * device, the occupancy or the launch order; DESIGN.md section 10 has the formulas), `*_det_bytes` = the bytes `ws` must have
+ * (possibly 0: one slot per output tile, written directly).  Contract differences to the atomic forms: the outputs are
+ * OVERWRITTEN (no caller-side zeroing; groups without rows and relations without edges get zeros), `ws` must be 16-byte aligned;
+ * ws_bytes too small -> HGT_ERR_WORKSPACE, bad arguments -> HGT_ERR_INVALID_ARG, and neither launches anything.  The results are
+ * within rounding of the atomic forms', not bit-equal to them.
+ * ---------------------------------------------------------------------------------------------- */
+/* conv.py:125-133 in reverse (both hgt_node_update_bwd and hgt_node_update_bwd_ex: skip may be NULL) */
+int hgt_node_update_bwd_det_bytes(int64_t n_rows, int32_t d, int32_t n_types, uint64_t* out);
+int hgt_node_update_bwd_det(const float* grad_out, const float* trans, const float* x, int64_t ldx, const int64_t* node_type,
+                            const float* skip, const float* ln_w, int32_t use_norm, int32_t shared_norm, const float* drop_mask,
+                            int64_t n_rows, int32_t d, int32_t n_types, float* d_trans, float* dx, int64_t ld_dx, float* d_alpha,
+                            float* d_ln_w, float* d_ln_b, void* ws, uint64_t ws_bytes, void* stream);
+/* weight / bias gradients of the typed linears (conv.py:96-97,103,125; model.py:70-76): out_group_stride >= m * n_cols */
+int hgt_typed_wgrad_det_bytes(int32_t n_groups, int64_t n_rows, int32_t m, int32_t n_cols, uint64_t* out);
+int hgt_typed_wgrad_det(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rows, const int32_t* group_off,
+                        int32_t n_groups, int64_t n_rows, int32_t m, int32_t n_cols, float* out, int64_t out_group_stride, void* ws,
+                        uint64_t ws_bytes, void* stream);
+int hgt_typed_wgrad_bf16x3_det_bytes(int32_t n_groups, int64_t n_rows, int32_t m, int32_t n_cols, uint64_t* out);
+int hgt_typed_wgrad_bf16x3_det(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rows,
+                               const int32_t* group_off, int32_t n_groups, int64_t n_rows, int32_t m, int32_t n_cols, float* out,
+                               int64_t out_group_stride, float* colsum, int64_t colsum_group_stride, void* ws, uint64_t ws_bytes,
+                               void* stream);
+int hgt_typed_colsum_det_bytes(int32_t n_groups, int64_t n_rows, int32_t m, uint64_t* out);
+int hgt_typed_colsum_det(const float* A, int64_t lda, const int32_t* rows, const int32_t* group_off, int32_t n_groups, int64_t n_rows,
+                         int32_t m, float* out, int64_t out_group_stride, void* ws, uint64_t ws_bytes, void* stream);
+/* d relation_msg / d relation_att (conv.py:98-99,104): partials per slice of the plan's item list */
+int hgt_relation_outer_det_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations, int32_t n_heads,
+                                 int32_t dk_pad, uint64_t* out);
+int hgt_relation_outer_det(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations, int32_t n_heads,
+                           int32_t dk_pad, const float* weights, const float* a_src, const float* rte_a, const float* b_dst,
+                           float* out, void* ws, uint64_t ws_bytes, void* stream);
+int hgt_relation_outer_wide_det_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations, int32_t n_heads,
+                                      int32_t dk_pad, uint64_t* out);
+int hgt_relation_outer_wide_det(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations,
+                                int32_t n_heads, int32_t dk_pad, const float* weights, const float* a_src, const float* rte_a,
+                                const float* b_dst, float* out, void* ws, uint64_t ws_bytes, void* stream);
+/* hgt_edge_spmm with the hub targets summed per piece in piece order (the hub mode of HGT_FLAG_DETERMINISTIC_HUBS); the
+ * workspace is the hub workspace: hgt_edge_spmm_det_bytes == hgt_hub_workspace_bytes_ex(.., 1) */
+int hgt_edge_spmm_det_bytes(int64_t n_edges, int32_t n_heads, int32_t dk_pad, int32_t n_relations, uint64_t* out);
+int hgt_edge_spmm_det(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations, int32_t n_heads,
+                      int32_t dk_pad, const float* weights, const float* rows, const float* rte_rows, const float* f_p,
+                      const void* f_frag, float* out, int64_t ld_out, int64_t n_q_rows, void* ws, uint64_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * One whole HGTConv.forward (conv.py:56-134, eval mode) as a single enqueue of the kernels above.

@@ -33,6 +33,7 @@ HGT_LINEAR_NO_XS = 0x200
 HGT_LINEAR_NO_TILE = 0x400
 HGT_LINEAR_TANH = 0x1000
 HGT_FEATURE_LAB_KERNELS = 1
+HGT_FEATURE_DETERMINISTIC_TRAINING = 2
 
 
 class HgtLayout(C.Structure):
@@ -157,6 +158,22 @@ SIGNATURES = {
     "hgt_typed_wgrad": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp]),
     "hgt_typed_wgrad_bf16x3": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
     "hgt_typed_colsum": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _vp]),
+    # the atomic-free forms of the backward (deterministic=True): the atomic form's arguments + (workspace, bytes) in front of the stream
+    "hgt_node_update_bwd_det_bytes": (C.c_int, [_i64, _i32, _i32, C.POINTER(_u64)]),
+    "hgt_node_update_bwd_det": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
+                                          _vp, _u64, _vp]),
+    "hgt_typed_wgrad_det_bytes": (C.c_int, [_i32, _i64, _i32, _i32, C.POINTER(_u64)]),
+    "hgt_typed_wgrad_det": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _u64, _vp]),
+    "hgt_typed_wgrad_bf16x3_det_bytes": (C.c_int, [_i32, _i64, _i32, _i32, C.POINTER(_u64)]),
+    "hgt_typed_wgrad_bf16x3_det": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _u64, _vp]),
+    "hgt_typed_colsum_det_bytes": (C.c_int, [_i32, _i64, _i32, C.POINTER(_u64)]),
+    "hgt_typed_colsum_det": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _u64, _vp]),
+    "hgt_relation_outer_det_bytes": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, C.POINTER(_u64)]),
+    "hgt_relation_outer_det": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "hgt_relation_outer_wide_det_bytes": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, C.POINTER(_u64)]),
+    "hgt_relation_outer_wide_det": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "hgt_edge_spmm_det_bytes": (C.c_int, [_i64, _i32, _i32, _i32, C.POINTER(_u64)]),
+    "hgt_edge_spmm_det": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _u64, _vp]),
     "hgt_log_softmax_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "hgt_row_dot": (C.c_int, [_vp, _vp, _i64, _i32, C.c_float, _vp, _vp]),
     "hgt_node_update": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp]),

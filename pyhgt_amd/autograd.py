@@ -27,7 +27,8 @@ from . import _lib
 from ._lib import check
 from .conv import _ptr, _stream
 
-__all__ = ["hgt_conv_train", "training_supported", "logits_form", "outer_form", "spmm_takes_items", "TypedLinearFunction", "MAX_TRAIN_DK_PAD"]
+__all__ = ["hgt_conv_train", "training_supported", "logits_form", "outer_form", "spmm_takes_items", "takes_det_route", "set_deterministic",
+           "TypedLinearFunction", "MAX_TRAIN_DK_PAD"]
 
 
 MAX_TRAIN_DK_PAD = 256      # widest (padded) head the training path covers: the matrix-core form of hgt_edge_spmm ends there
@@ -74,6 +75,36 @@ def spmm_takes_items(N, E, R, ld_out, out_col):
     return N < 65536 and E > 0 and R < 64 and ld_out % 4 == 0 and out_col % 4 == 0
 
 
+def takes_det_route(module):
+    """Does `module` (HGTConv, DenseHGTConv, GNN, Classifier, Matcher) train on the atomic-free `_det` entry points?  The one
+    predicate: its `deterministic` attribute and nothing else -- in particular not torch.use_deterministic_algorithms, which callers
+    switch on around unrelated code (a module unpickled without the attribute is a default one)."""
+    return bool(getattr(module, "deterministic", False))
+
+
+def set_deterministic(module, on=True):
+    """Set `deterministic` on every pyhgt_amd module of a model (the layers, GNN, Classifier, Matcher).  On a model built by the
+    reference's own GNN after install_into (whose constructor cannot pass the keyword) that is the layers: the reference's adapter and
+    heads are torch modules this switch does not reach.  Returns the module.  With it, a training
+    step executes no floating-point atomic and sums every reduction in an order fixed by the problem sizes: the same build, device
+    model, inputs and seed give the same bits (reproducible training)."""
+    from .conv import HGTConv
+    from .model import GNN, Classifier, Matcher
+    for m in module.modules():
+        if isinstance(m, (HGTConv, GNN, Classifier, Matcher)):
+            m.deterministic = bool(on)
+    return module
+
+
+def _det_ws(dev, name, *size_args):
+    """(pointer, bytes, tensor) of the workspace of a `_det` entry point: sized by its `<name>_bytes` host function; the caching
+    allocator hands the block to the next call when the tensor dies (stream-ordered: one workspace is live at a time)."""
+    nb = C.c_uint64()
+    check(getattr(_lib.load(), name + "_bytes")(*size_args, C.byref(nb)), name + "_bytes")
+    t = torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev)
+    return t.data_ptr(), int(nb.value), t
+
+
 # -- the typed-linear route: the layer's GEMMs and TypedLinearFunction ---------------------------------------------------------
 def _typed_linear(split, x, ldx, rows, off, n_groups, n_rows, k, n_out, W, w_off, wgs, bias, b_off, bgs, outs, block_cols, by_pos=0,
                   prologue=0):
@@ -96,10 +127,27 @@ def _typed_linear(split, x, ldx, rows, off, n_groups, n_rows, k, n_out, W, w_off
                                    by_pos, prologue, 0, _stream()), "hgt_typed_linear")
 
 
-def _wgrad(split, A, lda, B, ldb, rows, off, n_groups, n_rows, m, n_cols, with_colsum=True):
+def _wgrad(split, A, lda, B, ldb, rows, off, n_groups, n_rows, m, n_cols, with_colsum=True, det=False):
     """(dW[g] = A_g^T B_g, db[g] = column sums of A_g or None): split-bf16 x3 MFMA kernel (both from one pass) for split precisions,
-    the exact fp32 MFMA kernel + the column-sum kernel otherwise."""
+    the exact fp32 MFMA kernel + the column-sum kernel otherwise.  det: the same kernels' atomic-free forms (partials per row chunk,
+    summed in chunk order)."""
     lib = _lib.load()
+    if det:
+        dw = torch.empty(n_groups, m, n_cols, dtype=torch.float32, device=A.device)
+        db = torch.empty(n_groups, m, dtype=torch.float32, device=A.device) if with_colsum else None
+        if split:
+            wp, wb, keep = _det_ws(A.device, "hgt_typed_wgrad_bf16x3_det", n_groups, n_rows, m, n_cols)
+            check(lib.hgt_typed_wgrad_bf16x3_det(_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols,
+                                                 _ptr(db), m, wp, wb, _stream()), "hgt_typed_wgrad_bf16x3_det")
+        else:
+            wp, wb, keep = _det_ws(A.device, "hgt_typed_wgrad_det", n_groups, n_rows, m, n_cols)
+            check(lib.hgt_typed_wgrad_det(_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols, wp, wb,
+                                          _stream()), "hgt_typed_wgrad_det")
+            if with_colsum:
+                cp, cb, keep2 = _det_ws(A.device, "hgt_typed_colsum_det", n_groups, n_rows, m)
+                check(lib.hgt_typed_colsum_det(_ptr(A), lda, rows, off, n_groups, n_rows, m, _ptr(db), m, cp, cb, _stream()),
+                      "hgt_typed_colsum_det")
+        return dw, db
     dw = torch.zeros(n_groups, m, n_cols, dtype=torch.float32, device=A.device)
     db = torch.zeros(n_groups, m, dtype=torch.float32, device=A.device) if with_colsum else None
     if split:
@@ -149,6 +197,7 @@ class _Step:
         # relation transforms of every hgt_edge_spmm -- the training forward's aggregation included -- are ALWAYS split-bf16 MFMA
         # products under grad, also for precision='fp32': ~1e-5 away from the exact VALU aggregation of the inference path
         self.split = layer.precision in _SPLIT
+        self.det = takes_det_route(layer)                    # every atomic site of the step takes its `_det` entry point
         self.use_norm = bool(layer.use_norm)
         self.N, self.E = plan.N, plan.E
         self.dev = plan.device
@@ -221,6 +270,11 @@ class _Step:
                 return
             if rc != -2:      # HGT_ERR_UNSUPPORTED = nothing was launched: the sub-tile kernel below takes the pass
                 check(rc, "hgt_edge_spmm_items")
+        if self.det:      # hub targets: one partial per piece, summed in piece order
+            hp, hb, hub = _det_ws(self.dev, "hgt_edge_spmm_det", plan.E, self.H, self.dkp, self.R)
+            check(self.lib.hgt_edge_spmm_det(*self.graph(plan), self.dkp, _ptr(w), rows_ptr, _ptr(rte_rows), _ptr(f_p), _ptr(f_frag), optr,
+                                             ld_out, n_q_rows, hp, hb, _stream()), "hgt_edge_spmm_det")
+            return
         nb = C.c_uint64()
         check(self.lib.hgt_hub_workspace_bytes(plan.E, self.H, self.dkp, C.byref(nb)), "hgt_hub_workspace_bytes")
         hub = self.new(max(int(nb.value), 256), dtype=torch.uint8)
@@ -241,14 +295,28 @@ class _Step:
         return out
 
     def outer(self, plan, w, a, rte_a, b):
-        out = self.new(self.R, self.H, self.dkp, self.dkp, zero=True)
         name = outer_form(self.dkp)
+        if self.det:      # partials per slice of the plan's item list, summed in slice order (the output is overwritten)
+            out = self.new(self.R, self.H, self.dkp, self.dkp)
+            wp, wb, keep = _det_ws(self.dev, name + "_det", plan.N, plan.E, self.T, self.R, self.H, self.dkp)
+            check(getattr(self.lib, name + "_det")(*self.graph(plan), self.dkp, _ptr(w), _ptr(a), _ptr(rte_a), _ptr(b), _ptr(out), wp, wb,
+                                                   _stream()), name + "_det")
+            return out
+        out = self.new(self.R, self.H, self.dkp, self.dkp, zero=True)
         check(getattr(self.lib, name)(*self.graph(plan), self.dkp, _ptr(w), _ptr(a), _ptr(rte_a), _ptr(b), _ptr(out), _stream()), name)
         return out
 
     def drop_(self, t, mask):
         if mask is not None:
             check(self.lib.hgt_mul_inplace(_ptr(t), _ptr(mask), t.numel(), _stream()), "hgt_mul_inplace")
+
+    def node_update_bwd(self, *args):
+        """hgt_node_update_bwd_ex(*args, stream), or its atomic-free form (one partial per wavefront's row range, summed in range order)."""
+        if self.det:
+            wp, wb, keep = _det_ws(self.dev, "hgt_node_update_bwd_det", self.N, self.dout, self.T)
+            check(self.lib.hgt_node_update_bwd_det(*args, wp, wb, _stream()), "hgt_node_update_bwd_det")
+        else:
+            check(self.lib.hgt_node_update_bwd_ex(*args, _stream()), "hgt_node_update_bwd_ex")
 
     # == forward steps (the message path, conv.py:60-111, is shared by both layers) ==========================================
     def relation_images(self, p):
@@ -328,7 +396,7 @@ class _Step:
         """trans = a_linear(f(agg)), f = gelu or identity: (d agg, d w_a, d b_a)."""
         N, dp, dout = self.N, self.dp, self.dout
         a_in = torch.nn.functional.gelu(s.agg) if gelu else s.agg                  # exact erf form, conv.py:119
-        d_w_a, d_b_a = _wgrad(self.split, d_trans, dout, a_in, dp, self.rows.rows_q, self.rows.off_q, self.T, N, dout, dp)
+        d_w_a, d_b_a = _wgrad(self.split, d_trans, dout, a_in, dp, self.rows.rows_q, self.rows.off_q, self.T, N, dout, dp, det=self.det)
         del a_in
         dagg = self.new(N, dp)
         self.node_linear(d_trans, dout, dp, s.w_a.transpose(1, 2).contiguous(), dp * dout, None, 0, dagg)      # [T][dp][dout]
@@ -348,9 +416,14 @@ class _Step:
         d_lnw, d_lnb = self._ln_grads()
         d_trans, dx_skip = self.new(N, dout), self.new(N, din)
         d_alpha = self.new(T, zero=True)
-        check(self.lib.hgt_node_update_bwd(_ptr(gout), _ptr(s.trans), _ptr(s.x), din, _ptr(self.plan.node_type), _ptr(s.skip), _ptr(s.ln_w),
-                                           int(self.use_norm), _ptr(s.m1), N, dout, T, _ptr(d_trans), _ptr(dx_skip), din, _ptr(d_alpha),
-                                           _ptr(d_lnw), _ptr(d_lnb), _stream()), "hgt_node_update_bwd")
+        if self.det:
+            self.node_update_bwd(_ptr(gout), _ptr(s.trans), _ptr(s.x), din, _ptr(self.plan.node_type), _ptr(s.skip), _ptr(s.ln_w),
+                                 int(self.use_norm), 0, _ptr(s.m1), N, dout, T, _ptr(d_trans), _ptr(dx_skip), din, _ptr(d_alpha), _ptr(d_lnw),
+                                 _ptr(d_lnb))
+        else:
+            check(self.lib.hgt_node_update_bwd(_ptr(gout), _ptr(s.trans), _ptr(s.x), din, _ptr(self.plan.node_type), _ptr(s.skip), _ptr(s.ln_w),
+                                               int(self.use_norm), _ptr(s.m1), N, dout, T, _ptr(d_trans), _ptr(dx_skip), din, _ptr(d_alpha),
+                                               _ptr(d_lnw), _ptr(d_lnb), _stream()), "hgt_node_update_bwd")
         alpha = torch.sigmoid(s.skip)
         d_skip = d_alpha * alpha * (1.0 - alpha)
         dagg, d_w_a, d_b_a = self.a_linear_bwd(s, d_trans, gelu=True)
@@ -365,10 +438,10 @@ class _Step:
         d_oln_w, d_oln_b = self.new(1, dout, zero=True), self.new(1, dout, zero=True)
         d_t2 = self.new(N, dout)                                                      # gradient of out_linear's (dropped) output
         d_y1 = self.new(N, dout)                                                      # residual branch of y1
-        check(lib.hgt_node_update_bwd_ex(_ptr(gout), _ptr(s.trans2), _ptr(s.y1), dout, nt, None, _ptr(s.out_ln_w), 1, 1, _ptr(s.m2), N, dout, T,
-                                         _ptr(d_t2), _ptr(d_y1), dout, None, _ptr(d_oln_w), _ptr(d_oln_b), _stream()), "hgt_node_update_bwd_ex")
+        self.node_update_bwd(_ptr(gout), _ptr(s.trans2), _ptr(s.y1), dout, nt, None, _ptr(s.out_ln_w), 1, 1, _ptr(s.m2), N, dout, T,
+                             _ptr(d_t2), _ptr(d_y1), dout, None, _ptr(d_oln_w), _ptr(d_oln_b))
         g2 = torch.nn.functional.gelu(s.mid)
-        d_out_w, d_out_b = _wgrad(self.split, d_t2, dout, g2, 2 * dout, rows_q, off2, 1, N, dout, 2 * dout)
+        d_out_w, d_out_b = _wgrad(self.split, d_t2, dout, g2, 2 * dout, rows_q, off2, 1, N, dout, 2 * dout, det=self.det)
         del g2
         out_w_t = s.out_w.t().contiguous()                                            # [2 dout][dout]
         d_g2 = self.new(N, 2 * dout, zero=True)
@@ -376,15 +449,14 @@ class _Step:
         d_mid = torch.empty_like(d_g2)
         check(lib.hgt_gelu_bwd(_ptr(d_g2), _ptr(s.mid), _ptr(d_mid), d_mid.numel(), _stream()), "hgt_gelu_bwd")
         del d_g2
-        d_mid_w, d_mid_b = _wgrad(self.split, d_mid, 2 * dout, s.y1, dout, rows_q, off2, 1, N, 2 * dout, dout)
+        d_mid_w, d_mid_b = _wgrad(self.split, d_mid, 2 * dout, s.y1, dout, rows_q, off2, 1, N, 2 * dout, dout, det=self.det)
         mid_w_t = s.mid_w.t().contiguous()                                            # [dout][2 dout]
         d_y1b = self.new(N, dout, zero=True)
         _typed_linear(self.split, d_mid, 2 * dout, rows_q, off2, 1, N, 2 * dout, dout, mid_w_t, 0, 0, None, 0, 0, [d_y1b], dout)
         d_y1 += d_y1b
         del d_mid, d_y1b
-        check(lib.hgt_node_update_bwd_ex(_ptr(d_y1), _ptr(s.trans), _ptr(s.x), din, nt, None, _ptr(s.ln_w), int(self.use_norm), 0, _ptr(s.m1), N,
-                                         dout, T, _ptr(d_trans), _ptr(dx_skip), din, None, _ptr(d_lnw), _ptr(d_lnb), _stream()),
-              "hgt_node_update_bwd_ex")
+        self.node_update_bwd(_ptr(d_y1), _ptr(s.trans), _ptr(s.x), din, nt, None, _ptr(s.ln_w), int(self.use_norm), 0, _ptr(s.m1), N, dout, T,
+                             _ptr(d_trans), _ptr(dx_skip), din, None, _ptr(d_lnw), _ptr(d_lnb))
         dagg, d_w_a, d_b_a = self.a_linear_bwd(s, d_trans, gelu=False)
         return dagg, dx_skip, dict(w_a=d_w_a, b_a=d_b_a, ln_w=d_lnw, ln_b=d_lnb, mid_w=d_mid_w[0], mid_b=d_mid_b[0], out_w=d_out_w[0],
                                    out_b=d_out_b[0], out_ln_w=d_oln_w[0], out_ln_b=d_oln_b[0])
@@ -444,6 +516,8 @@ class _Step:
         # sources of plan_r are the original TARGETS, shifted by `tab` ids: the row pointer is shifted back
         self.spmm(plan_r, ds_r, s.qkv[0].data_ptr() - 4 * tab * dp, None, *f_k, d_tab, 0, 2 * dp, tab)
         self.spmm(plan_r, att_r, dagg.data_ptr() - 4 * tab * dp, None, *f_v, d_tab, dp, 2 * dp, tab)
+        if self.det:
+            return self.temporal_chain_det(s, d_tab)
         # tables = (emb W_rte^T + b_rte) W_{k|v}[t]^T: chain rule on [T*240, d] arrays with torch ops (tiny)
         with torch.enable_grad():
             e_, w_, b_ = (t.detach().requires_grad_(True) for t in (s.rte_emb, s.rte_w, s.rte_b))
@@ -453,10 +527,34 @@ class _Step:
             ge, gw, gb, gkv = torch.autograd.grad(tabs, [e_, w_, b_, wkv], d_tab)
         return dict(rte_emb=ge, rte_w=gw, rte_b=gb), gkv
 
+    def temporal_chain_det(self, s, d_tab):
+        """The chain rule of temporal_bwd on this library's own GEMMs instead of torch's (whose BLAS back end may split the reduction
+        dimension across workgroups and add with atomics): tables[t] = lin W_kv[t]^T, lin = emb W_rte^T + b_rte.
+        Exact fp32 kernels, like the torch ops they stand in for."""
+        T, dp, din, L = self.T, self.dp, self.din, _lib.HGT_RTE_LEN
+        rr, ro = _rte_row_lists(T, self.dev)                      # rows 0..239 per type, by position
+        rows_tl = torch.arange(T * L, dtype=torch.int32, device=self.dev)
+        one = torch.tensor([0, L], dtype=torch.int32, device=self.dev)
+        lin = self.new(L, din)
+        _typed_linear(False, s.rte_emb, din, rr.data_ptr(), ro.data_ptr(), 1, L, din, din, s.rte_w, 0, 0, s.rte_b, 0, 0, [lin], din, by_pos=1)
+        # d W_kv[t] = d_tab[t]^T lin
+        gkv, _ = _wgrad(False, d_tab, 2 * dp, lin.repeat(T, 1), din, rows_tl.data_ptr(), ro.data_ptr(), T, T * L, 2 * dp, din,
+                        with_colsum=False, det=True)
+        # d lin = sum_t d_tab[t] W_kv[t]
+        wkv_t = s.w_qkv.detach()[:, dp:3 * dp, :].transpose(1, 2).contiguous()          # [T][din][2dp]
+        d_lin_t = self.new(T * L, din)
+        _typed_linear(False, d_tab, 2 * dp, rows_tl.data_ptr(), ro.data_ptr(), T, T * L, 2 * dp, din, wkv_t, 0, din * 2 * dp, None, 0, 0,
+                      [d_lin_t], din)
+        d_lin = d_lin_t.view(T, L, din).sum(dim=0)                                       # (torch's reduce kernels sum in a fixed order)
+        gw, gb = _wgrad(False, d_lin, din, s.rte_emb.contiguous(), din, rr.data_ptr(), one.data_ptr(), 1, L, din, din, det=True)
+        ge = self.new(L, din)
+        _typed_linear(False, d_lin, din, rr.data_ptr(), one.data_ptr(), 1, L, din, din, s.rte_w.t().contiguous(), 0, 0, None, 0, 0, [ge], din)
+        return dict(rte_emb=ge, rte_w=gw[0], rte_b=gb[0]), gkv
+
     def project_bwd(self, s, dqkv, dx_skip, d_w_kv_tables, want_dx):
         """project in reverse (conv.py:96-97,103): d w_qkv, d b_qkv and, if asked for, dx (+ the skip / residual branch)."""
         T, N, dp, din, rows = self.T, self.N, self.dp, self.din, self.rows
-        d_w_qkv, d_b_qkv = _wgrad(self.split, dqkv, 3 * dp, s.x, din, rows.rows_all, rows.off_all, T, N, 3 * dp, din)
+        d_w_qkv, d_b_qkv = _wgrad(self.split, dqkv, 3 * dp, s.x, din, rows.rows_all, rows.off_all, T, N, 3 * dp, din, det=self.det)
         if d_w_kv_tables is not None:
             d_w_qkv[:, dp:3 * dp, :] += d_w_kv_tables
         grads = dict(w_qkv=d_w_qkv, b_qkv=d_b_qkv)
@@ -538,7 +636,7 @@ class TypedLinearFunction(torch.autograd.Function):
     sums, optional input gradient): the input adapter of model.GNN (model.py:70-76) and the Linear layers of the heads."""
 
     @staticmethod
-    def forward(ctx, plan_rows, n_groups, precision, x, w, b):
+    def forward(ctx, plan_rows, n_groups, precision, x, w, b, deterministic=False):
         # plan_rows = (rows ptr, off ptr, keep-alive object); w [G][n_out][k], b [G][n_out]
         rows, off, _keep = plan_rows
         x = x.contiguous()
@@ -548,6 +646,7 @@ class TypedLinearFunction(torch.autograd.Function):
         wc, bc = w.contiguous(), (b.contiguous() if b is not None else None)
         _typed_linear(precision in _SPLIT, x, k, rows, off, n_groups, n, k, n_out, wc, 0, n_out * k, bc, 0, n_out, [y], n_out)
         ctx.plan_rows, ctx.n_groups, ctx.has_bias, ctx.split = plan_rows, n_groups, b is not None, precision in _SPLIT
+        ctx.det = bool(deterministic)
         ctx.save_for_backward(x, wc)
         return y
 
@@ -559,7 +658,7 @@ class TypedLinearFunction(torch.autograd.Function):
         gy = gy.contiguous().float()
         n, k = x.shape
         n_out = w.shape[1]
-        dw, db = _wgrad(ctx.split, gy, n_out, x, k, rows, off, G, n, n_out, k, with_colsum=ctx.has_bias)
+        dw, db = _wgrad(ctx.split, gy, n_out, x, k, rows, off, G, n, n_out, k, with_colsum=ctx.has_bias, det=ctx.det)
         dx = None
         if ctx.needs_input_grad[3]:
             wt = w.transpose(1, 2).contiguous()
@@ -568,4 +667,4 @@ class TypedLinearFunction(torch.autograd.Function):
             # fp32 kernel (the heads are 'fp32' anyway; the adapter's is asked for only when the features themselves require grad),
             # and moving it to the split kernel would change results
             _typed_linear(False, gy, n_out, rows, off, G, n, n_out, k, wt, 0, k * n_out, None, 0, 0, [dx], k)
-        return None, None, None, dx, dw, db
+        return None, None, None, dx, dw, db, None

@@ -400,7 +400,7 @@ class HGTConv(nn.Module):
     """
 
     def __init__(self, in_dim, out_dim, num_types, num_relations, n_heads, dropout=0.2, use_norm=True, use_RTE=True,
-                 keep_att=False, precision=DEFAULT_PRECISION, strict=None, **kwargs):
+                 keep_att=False, precision=DEFAULT_PRECISION, strict=None, deterministic=False, **kwargs):
         super().__init__()
         self.in_dim, self.out_dim = in_dim, out_dim
         self.num_types, self.num_relations = num_types, num_relations
@@ -415,6 +415,9 @@ class HGTConv(nn.Module):
         self.precision = precision
         self.kernel_flags = 0          # hgt_conv_args.flags (HGT_FLAG_*): explicit kernel selection for A/B runs and tests
         self.strict = strict           # None = GraphPlan.STRICT; True: malformed ids raise IndexError on the very first forward
+        # bit-reproducible mode: the training step takes the atomic-free `_det` kernels (autograd.takes_det_route), inference the
+        # deterministic hub mode; opt-in only -- torch.use_deterministic_algorithms does not move it
+        self.deterministic = bool(deterministic)
         self.att = None
 
         self.k_linears = nn.ModuleList(nn.Linear(in_dim, out_dim) for _ in range(num_types))
@@ -437,13 +440,18 @@ class HGTConv(nn.Module):
 
     # -- state that is not part of the reference module: caches of packed parameters / device-side weight images ------
     EXTRA_KERNEL_FLAGS = 0      # OR-ed into every layer's kernel_flags (tests: tests/conftest.py sets it from HGT_TEST_KERNEL_FLAGS)
-    _RUNTIME_DEFAULTS = dict(keep_att=False, precision=DEFAULT_PRECISION, kernel_flags=0, strict=None, att=None, _packed=None, _packed_key=None,
+    _RUNTIME_DEFAULTS = dict(keep_att=False, precision=DEFAULT_PRECISION, kernel_flags=0, strict=None, deterministic=False, att=None,
+                             _packed=None, _packed_key=None,
                              _prepared=None, _prepared_tag=None, _prepared_valid=False, _plist=None)
 
     def _init_runtime_state(self):
         for k, v in self._RUNTIME_DEFAULTS.items():
             if k not in self.__dict__:
                 self.__dict__[k] = v
+
+    def _flags(self):
+        """kernel_flags + what `deterministic` adds for inference: the hub targets without atomics."""
+        return int(self.kernel_flags) | (_lib.HGT_FLAG_DETERMINISTIC_HUBS if self.__dict__.get("deterministic", False) else 0)
 
     def __getstate__(self):
         st = dict(self.__dict__)
@@ -650,7 +658,7 @@ class HGTConv(nn.Module):
         # (the item-parallel aggregation's scratch only where this call can take that kernel: whole-layer calls of a split precision)
         # (a caller-owned workspace may come without it: hgt_conv_forward then simply rules that kernel out)
         item_scratch = int(workspace is None and stage == 0 and prec != "fp32" and not (self.kernel_flags & _lib.HGT_FLAG_NO_ITEM_AGGREGATE))
-        options = item_scratch | (2 if (self.kernel_flags & _lib.HGT_FLAG_DETERMINISTIC_HUBS) else 0)
+        options = item_scratch | (2 if (self._flags() & _lib.HGT_FLAG_DETERMINISTIC_HUBS) else 0)
         _lib.check(lib.hgt_conv_workspace_bytes_ex(N, E, self.in_dim, self.out_dim, self.num_types, R_plan,
                                                    self.n_heads, int(self.use_RTE), options, C.byref(nbytes)), "hgt_conv_workspace_bytes_ex")
         if workspace is not None:
@@ -701,7 +709,7 @@ class HGTConv(nn.Module):
         if stage == 5:
             a.q_begin, a.q_end, a.item_begin, a.item_end = (int(v) for v in block)
         a.plan_no_hubs = int(plan.no_hubs) | (2 if plan.no_unknown_rows else 0)
-        a.flags = int(self.kernel_flags) | int(HGTConv.EXTRA_KERNEL_FLAGS)
+        a.flags = self._flags() | int(HGTConv.EXTRA_KERNEL_FLAGS)
         prep = self._prepared_buffer(x.device, n_slices, prec)          # after _pack_parameters: a re-pack has invalidated it
         a.prepared, a.prepared_bytes, a.prepared_valid = _ptr(prep), prep.numel(), int(self._prepared_valid)
         if stage == 2:
@@ -728,7 +736,7 @@ class HGTConv(nn.Module):
         n = C.c_uint64()
         _lib.check(_lib.load().hgt_conv_workspace_bytes_ex(int(n_nodes), int(n_edges), self.in_dim, self.out_dim, self.num_types,
                                                            self.num_relations * int(n_slices), self.n_heads, int(self.use_RTE),
-                                                           int(not staged) | (2 if (self.kernel_flags & _lib.HGT_FLAG_DETERMINISTIC_HUBS) else 0),
+                                                           int(not staged) | (2 if (self._flags() & _lib.HGT_FLAG_DETERMINISTIC_HUBS) else 0),
                                                            C.byref(n)), "hgt_conv_workspace_bytes_ex")
         return int(n.value)
 

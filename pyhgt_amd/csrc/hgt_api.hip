@@ -510,9 +510,9 @@ extern "C" const char* hgt_strerror(int code) {
 extern "C" int hgt_abi_version(void) { return HGT_ABI_VERSION; }
 extern "C" int hgt_build_features(void) {
 #ifdef HGT_LAB_KERNELS
-    return HGT_FEATURE_LAB_KERNELS;
+    return HGT_FEATURE_LAB_KERNELS | HGT_FEATURE_DETERMINISTIC_TRAINING;
 #else
-    return 0;
+    return HGT_FEATURE_DETERMINISTIC_TRAINING;
 #endif
 }
 

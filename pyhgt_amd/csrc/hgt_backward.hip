@@ -15,6 +15,11 @@
 //   Q|K|V = x W_qkv^T + b:             d x += [dQ|dK|dV] W_qkv (typed linear), d W_qkv / d b_qkv = typed weight gradient.
 // Everything is enqueued on the caller's stream; small parameter gradients are accumulated with fp32 atomics into
 // caller-zeroed buffers (run-to-run differences of the summation order only).
+//
+// Deterministic forms (hgt_*_det, kernels k_det_*): the same kernel bodies instantiated with DET = true write each slot's partial
+// result with plain stores into a workspace -- slot = a (group, row chunk) / a wavefront's row range / a slice of the plan's item
+// list, all fixed on the host from the problem sizes (det_* functions below) -- and k_det_reduce sums the slots in slot order.
+// No atomics, no waiting between workgroups: two launches on the stream are the ordering.
 #include "hgt_edge_common.h"
 #include "hgt_split_common.h"
 
@@ -35,18 +40,25 @@ constexpr int NUB_ROWS = 32;
 constexpr int NUB_MAXC = 8;          // columns per lane of k_node_update_bwd: d <= 512
 constexpr int NUB_MAXC_WIDE = 16;    // ... of k_node_update_bwd_wide: 512 < d <= 1024 (like MAX_PER_LANE of the forward, hgt_update.hip)
 
-template <int NUB_MAXC>
+template <int NUB_MAXC, bool DET = false>
 __device__ __forceinline__ void node_update_bwd_rows(
     const float* __restrict__ gout, const float* __restrict__ trans, const float* __restrict__ x, int64_t ldx,
     const int64_t* __restrict__ node_type, const float* __restrict__ skip, const float* __restrict__ lnw, int use_norm,
     const float* __restrict__ drop_mask, int64_t NQ, int d, int T, float* __restrict__ d_trans, float* __restrict__ dx, int64_t ld_dx,
-    float* __restrict__ d_alpha, float* __restrict__ d_lnw, float* __restrict__ d_lnb, int shared_norm, int rows_per_wave) {
+    float* __restrict__ d_alpha, float* __restrict__ d_lnw, float* __restrict__ d_lnb, int shared_norm, int rows_per_wave,
+    int64_t det_slot_stride = 0) {
+    // DET: d_lnw / d_lnb / d_alpha point into slot 0 of a zeroed workspace; this wavefront owns slot `wave` (plain read-modify-write)
     // skip == NULL: plain residual y = o + x (DenseHGTConv.update, conv.py:259,271), no gate gradient;
     // shared_norm: ONE LayerNorm for every type (out_norm, conv.py:272): its parameters / gradients are row 0 of lnw / d_lnw / d_lnb
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t r0 = wave * rows_per_wave;
     if (r0 >= NQ) return;
+    if constexpr (DET) {
+        if (d_lnw) d_lnw += wave * det_slot_stride;
+        if (d_lnb) d_lnb += wave * det_slot_stride;
+        if (d_alpha) d_alpha += wave * det_slot_stride;
+    }
     const int nc = (d + 63) / 64;
     float gw[NUB_MAXC], gb[NUB_MAXC], ga = 0.0f;
 #pragma unroll
@@ -60,15 +72,24 @@ __device__ __forceinline__ void node_update_bwd_rows(
                     const int col = c * 64 + lane;
                     if (c < nc && col < d) {
                         const int64_t lrow = shared_norm ? 0 : cur_t;
-                        unsafeAtomicAdd(&d_lnw[lrow * d + col], gw[c]);
-                        unsafeAtomicAdd(&d_lnb[lrow * d + col], gb[c]);
+                        if constexpr (DET) {
+                            d_lnw[lrow * d + col] += gw[c];
+                            d_lnb[lrow * d + col] += gb[c];
+                        } else {
+                            unsafeAtomicAdd(&d_lnw[lrow * d + col], gw[c]);
+                            unsafeAtomicAdd(&d_lnb[lrow * d + col], gb[c]);
+                        }
                     }
                     gw[c] = gb[c] = 0.0f;
                 }
             }
             if (skip) {
                 ga = wave_sum(ga);
-                if (lane == 0) unsafeAtomicAdd(&d_alpha[cur_t], ga);
+                if constexpr (DET) {
+                    if (lane == 0) d_alpha[cur_t] += ga;
+                } else {
+                    if (lane == 0) unsafeAtomicAdd(&d_alpha[cur_t], ga);
+                }
             }
             ga = 0.0f;
         }
@@ -160,8 +181,32 @@ __device__ __forceinline__ void node_update_bwd_rows(
 __global__ __launch_bounds__(256) void k_node_update_bwd(HGT_NUB_PARAMS) { node_update_bwd_rows<NUB_MAXC>(HGT_NUB_ARGS); }
 // rows of 513 .. 1024 columns (n_hid 768 / 1024): the same walk with 16 columns per lane
 __global__ __launch_bounds__(256) void k_node_update_bwd_wide(HGT_NUB_PARAMS) { node_update_bwd_rows<NUB_MAXC_WIDE>(HGT_NUB_ARGS); }
+// deterministic forms: one workspace slot per wavefront (hgt_node_update_bwd_det)
+__global__ __launch_bounds__(256) void k_det_node_update_bwd(HGT_NUB_PARAMS, int64_t det_slot_stride) {
+    node_update_bwd_rows<NUB_MAXC, true>(HGT_NUB_ARGS, det_slot_stride);
+}
+__global__ __launch_bounds__(256) void k_det_node_update_bwd_wide(HGT_NUB_PARAMS, int64_t det_slot_stride) {
+    node_update_bwd_rows<NUB_MAXC_WIDE, true>(HGT_NUB_ARGS, det_slot_stride);
+}
 #undef HGT_NUB_PARAMS
 #undef HGT_NUB_ARGS
+
+// Stage two of every deterministic form: out[seg][(i / per) * ogs + i % per] = sum of in[s][i] over the slots s of segment `seg`
+// (blockIdx.y; seg_len slots each), in slot order.  One segment = the whole sum; many slots are summed in two passes (segments of
+// DET_SEG slots into a scratch array, then the segments): still one fixed order, with enough threads to stream the partials.
+constexpr int DET_SEG = 64, DET_TWO_PASS = 128;
+__global__ __launch_bounds__(256) void k_det_reduce(const float* __restrict__ in, int n_slots, int64_t slot_stride, int64_t n_elems,
+                                                    int seg_len, float* __restrict__ out, int64_t out_seg_stride, int64_t per,
+                                                    int64_t ogs) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_elems) return;
+    const int s0 = blockIdx.y * seg_len, s1 = min(s0 + seg_len, n_slots);
+    const float* p = in + (int64_t)s0 * slot_stride + i;
+    float acc = 0.0f;
+#pragma unroll 8
+    for (int s = s0; s < s1; ++s, p += slot_stride) acc += *p;
+    out[(int64_t)blockIdx.y * out_seg_stride + (i / per) * ogs + i % per] = acc;
+}
 
 // dagg = dg * gelu'(agg), gelu = exact erf form (conv.py:119)
 __global__ void k_gelu_bwd(const float* __restrict__ dg, const float* __restrict__ agg, float* __restrict__ out, int64_t n) {
@@ -226,22 +271,41 @@ __global__ void k_head_dot(const float* __restrict__ a, const float* __restrict_
 // ---------------------------------------------------------------------------------------------
 constexpr int WG_ROWS = 2048;
 
-__global__ __launch_bounds__(256) void k_typed_wgrad(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
-                                                     const int32_t* __restrict__ rows, const int32_t* __restrict__ group_off, int n_groups,
-                                                     int M, int Nc, float* __restrict__ out, int64_t out_group_stride, int vecA, int vecB) {
+// DET: chunk `slot % det_chunks` of the det_chunks equal row chunks (a multiple of `quantum` rows) of group `slot / det_chunks`
+__device__ __forceinline__ void det_chunk_of(int slot, int det_chunks, int quantum, const int32_t* __restrict__ group_off, int& g,
+                                             int& ch, int& p0, int& p1) {
+    g = slot / det_chunks;
+    ch = slot - g * det_chunks;
+    const int gbeg = group_off[g], gend = group_off[g + 1];
+    const int per = ((gend - gbeg + det_chunks - 1) / det_chunks + quantum - 1) / quantum * quantum;
+    p0 = min(gbeg + ch * per, gend);
+    p1 = min(p0 + per, gend);
+}
+
+template <bool DET>
+__device__ __forceinline__ void typed_wgrad_body(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
+                                                 const int32_t* __restrict__ rows, const int32_t* __restrict__ group_off, int n_groups,
+                                                 int M, int Nc, float* __restrict__ out, int64_t out_group_stride, int vecA, int vecB,
+                                                 int det_chunks) {
     __shared__ float sA[64][68];
     __shared__ float sB[64][68];
     // which (group, row chunk) is this block?
     int slot = blockIdx.x, g = 0, gbeg = 0, gend = 0, before = 0;
-    for (; g < n_groups; ++g) {
-        gbeg = group_off[g];
-        gend = group_off[g + 1];
-        const int nch = (gend - gbeg + WG_ROWS - 1) / WG_ROWS;
-        if (slot < before + nch) break;
-        before += nch;
+    int p0, p1, det_ch = 0;
+    if constexpr (DET) {
+        det_chunk_of(slot, det_chunks, 64, group_off, g, det_ch, p0, p1);
+    } else {
+        for (; g < n_groups; ++g) {
+            gbeg = group_off[g];
+            gend = group_off[g + 1];
+            const int nch = (gend - gbeg + WG_ROWS - 1) / WG_ROWS;
+            if (slot < before + nch) break;
+            before += nch;
+        }
+        if (g >= n_groups) return;
+        p0 = gbeg + (slot - before) * WG_ROWS;
+        p1 = min(p0 + WG_ROWS, gend);
     }
-    if (g >= n_groups) return;
-    const int p0 = gbeg + (slot - before) * WG_ROWS, p1 = min(p0 + WG_ROWS, gend);
     const int m0 = blockIdx.y * 64, n0 = blockIdx.z * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
@@ -278,12 +342,29 @@ __global__ __launch_bounds__(256) void k_typed_wgrad(const float* __restrict__ A
         }
     }
     // C layout: col (n) = lane & 31, row (m) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-    float* o = out + (int64_t)g * out_group_stride;
+    // DET: this chunk's own [n_groups][M][Nc] slot (out = the workspace, out_group_stride = M * Nc; one chunk: out itself)
+    float* o = out + (int64_t)g * out_group_stride + (DET ? (int64_t)det_ch * n_groups * out_group_stride : 0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int m = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), n = n0 + wn + (lane & 31);
-        if (m < M && n < Nc) unsafeAtomicAdd(&o[(int64_t)m * Nc + n], acc[r]);
+        if (m < M && n < Nc) {
+            if constexpr (DET) o[(int64_t)m * Nc + n] = acc[r];
+            else unsafeAtomicAdd(&o[(int64_t)m * Nc + n], acc[r]);
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void k_typed_wgrad(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
+                                                     const int32_t* __restrict__ rows, const int32_t* __restrict__ group_off, int n_groups,
+                                                     int M, int Nc, float* __restrict__ out, int64_t out_group_stride, int vecA, int vecB) {
+    typed_wgrad_body<false>(A, lda, B, ldb, rows, group_off, n_groups, M, Nc, out, out_group_stride, vecA, vecB, 0);
+}
+__global__ __launch_bounds__(256) void k_det_typed_wgrad(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
+                                                         int64_t ldb, const int32_t* __restrict__ rows,
+                                                         const int32_t* __restrict__ group_off, int n_groups, int M, int Nc,
+                                                         float* __restrict__ out, int64_t out_group_stride, int vecA, int vecB,
+                                                         int det_chunks) {
+    typed_wgrad_body<true>(A, lda, B, ldb, rows, group_off, n_groups, M, Nc, out, out_group_stride, vecA, vecB, det_chunks);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -302,23 +383,31 @@ constexpr int WX_CS = 80;            // LDS bytes per column: 32 rows x 2 B + 16
 constexpr int WX_PLANE = WX_T * WX_CS;
 constexpr int WX_ROWS = 4096;        // rows of one group per workgroup
 
-__global__ __launch_bounds__(256) void k_typed_wgrad_x3(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
-                                                        const int32_t* __restrict__ rows, const int32_t* __restrict__ group_off,
-                                                        int n_groups, int M, int Nc, int n_mt, float* __restrict__ out,
-                                                        int64_t out_group_stride, float* __restrict__ colsum, int64_t cs_group_stride) {
+template <bool DET>
+__device__ __forceinline__ void typed_wgrad_x3_body(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
+                                                    const int32_t* __restrict__ rows, const int32_t* __restrict__ group_off,
+                                                    int n_groups, int M, int Nc, int n_mt, float* __restrict__ out,
+                                                    int64_t out_group_stride, float* __restrict__ colsum, int64_t cs_group_stride,
+                                                    int det_chunks) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[4 * WX_PLANE];   // A hi | A mid | B hi | B mid
     // tile index fastest: the workgroups that share a row chunk are neighbours in launch order (their rows meet in the L2)
     const int mt = blockIdx.x % n_mt, nt = blockIdx.x / n_mt;
     int slot = blockIdx.y, g = 0, gbeg = 0, gend = 0, before = 0;
-    for (; g < n_groups; ++g) {
-        gbeg = group_off[g];
-        gend = group_off[g + 1];
-        const int nch = (gend - gbeg + WX_ROWS - 1) / WX_ROWS;
-        if (slot < before + nch) break;
-        before += nch;
+    int p0, p1, det_ch = 0;
+    if constexpr (DET) {
+        det_chunk_of(slot, det_chunks, WX_KR, group_off, g, det_ch, p0, p1);
+    } else {
+        for (; g < n_groups; ++g) {
+            gbeg = group_off[g];
+            gend = group_off[g + 1];
+            const int nch = (gend - gbeg + WX_ROWS - 1) / WX_ROWS;
+            if (slot < before + nch) break;
+            before += nch;
+        }
+        if (g >= n_groups) return;
+        p0 = gbeg + (slot - before) * WX_ROWS;
+        p1 = min(p0 + WX_ROWS, gend);
     }
-    if (g >= n_groups) return;
-    const int p0 = gbeg + (slot - before) * WX_ROWS, p1 = min(p0 + WX_ROWS, gend);
     const int m0 = mt * WX_T, n0 = nt * WX_T;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
@@ -410,7 +499,8 @@ __global__ __launch_bounds__(256) void k_typed_wgrad_x3(const float* __restrict_
         }
     }
     // C layout of a 32 x 32 tile: col (n) = lane & 31, row (m) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-    float* o = out + (int64_t)g * out_group_stride;
+    // DET: this chunk's own [n_groups][M][Nc] / [n_groups][M] slots (out / colsum = the workspace; one chunk: the outputs themselves)
+    float* o = out + (int64_t)g * out_group_stride + (DET ? (int64_t)det_ch * n_groups * out_group_stride : 0);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -418,9 +508,38 @@ __global__ __launch_bounds__(256) void k_typed_wgrad_x3(const float* __restrict_
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), n = n0 + wn + 32 * j + (lane & 31);
-                if (m < M && n < Nc) unsafeAtomicAdd(&o[(int64_t)m * Nc + n], acc[i][j][r]);
+                if (m < M && n < Nc) {
+                    if constexpr (DET) o[(int64_t)m * Nc + n] = acc[i][j][r];
+                    else unsafeAtomicAdd(&o[(int64_t)m * Nc + n], acc[i][j][r]);
+                }
             }
-    if (colsum && nt == 0 && a_ok) unsafeAtomicAdd(&colsum[(int64_t)g * cs_group_stride + m0 + c], csum);
+    if constexpr (DET) {
+        // a column's sum sits in two threads (row octets o0 and o0 + 2 of every chunk): combined through LDS in a fixed order
+        if (colsum && nt == 0) {      // (workgroup-uniform)
+            float* s_cs = reinterpret_cast<float*>(smem);
+            __syncthreads();          // the last chunk's fragments have been read
+            if (o0 == 1) s_cs[c] = csum;
+            __syncthreads();
+            if (o0 == 0 && a_ok) colsum[((int64_t)det_ch * n_groups + g) * cs_group_stride + m0 + c] = csum + s_cs[c];
+        }
+    } else {
+        if (colsum && nt == 0 && a_ok) unsafeAtomicAdd(&colsum[(int64_t)g * cs_group_stride + m0 + c], csum);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_typed_wgrad_x3(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
+                                                        const int32_t* __restrict__ rows, const int32_t* __restrict__ group_off,
+                                                        int n_groups, int M, int Nc, int n_mt, float* __restrict__ out,
+                                                        int64_t out_group_stride, float* __restrict__ colsum, int64_t cs_group_stride) {
+    typed_wgrad_x3_body<false>(A, lda, B, ldb, rows, group_off, n_groups, M, Nc, n_mt, out, out_group_stride, colsum, cs_group_stride, 0);
+}
+__global__ __launch_bounds__(256) void k_det_typed_wgrad_x3(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
+                                                            int64_t ldb, const int32_t* __restrict__ rows,
+                                                            const int32_t* __restrict__ group_off, int n_groups, int M, int Nc, int n_mt,
+                                                            float* __restrict__ out, int64_t out_group_stride,
+                                                            float* __restrict__ colsum, int64_t cs_group_stride, int det_chunks) {
+    typed_wgrad_x3_body<true>(A, lda, B, ldb, rows, group_off, n_groups, M, Nc, n_mt, out, out_group_stride, colsum, cs_group_stride,
+                              det_chunks);
 }
 
 // out[g][c] += sum_{rows p of group g} A[rows[p]][c]    (bias gradients)
@@ -457,6 +576,35 @@ __global__ __launch_bounds__(256) void k_typed_colsum(const float* __restrict__ 
     }
 }
 
+// deterministic form: wavefront = chunk `slot % det_chunks` of group `slot / det_chunks`, its sums stored into the chunk's own
+// [n_groups][out_group_stride] slot of `out` (the workspace; one chunk: the output itself)
+__global__ __launch_bounds__(256) void k_det_typed_colsum(const float* __restrict__ A, int64_t lda, const int32_t* __restrict__ rows,
+                                                          const int32_t* __restrict__ group_off, int n_groups, int M,
+                                                          float* __restrict__ out, int64_t out_group_stride, int det_chunks) {
+    const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slot >= n_groups * det_chunks) return;
+    int g, ch, p0, p1;
+    det_chunk_of(slot, det_chunks, 1, group_off, g, ch, p0, p1);
+    const int lane = threadIdx.x & 63;
+    float* o = out + ((int64_t)ch * n_groups + g) * out_group_stride;
+    for (int c0 = 0; c0 < M; c0 += 64 * 4) {
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int p = p0; p < p1; ++p) {
+            const int64_t rid = rows[p];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = c0 + j * 64 + lane;
+                if (c < M) s[j] += A[rid * lda + c];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j * 64 + lane;
+            if (c < M) o[c] = s[j];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Relation outer products:  out[r][h][k][c] += sum_{e of relation r} w_e,h * a[src_e][h][k] * b[dst_e][h][c]
 // (d relation_msg with (w, a, b) = (att, V, dagg); d A' with (ds, K, Q)).  A wavefront takes the work items of ONE relation
@@ -464,11 +612,16 @@ __global__ __launch_bounds__(256) void k_typed_colsum(const float* __restrict__ 
 // VEC rows k of the head's block); the b row of the edge is broadcast inside the head's lanes through LDS; the dkp x dkp
 // blocks accumulate in registers over ~64 items and are flushed once with atomics.
 // ---------------------------------------------------------------------------------------------
-template <int VEC, int LPH, bool RTE>
-__global__ __launch_bounds__(256) void k_relation_outer(
-    const HgtItem* __restrict__ items, const HgtPlanHeader* __restrict__ hdr, const int32_t* __restrict__ esrc,
-    const int32_t* __restrict__ edst, const uint16_t* __restrict__ ertei, const float* __restrict__ w, const float* __restrict__ a,
-    const float* __restrict__ rte_a, const float* __restrict__ b, float* __restrict__ out, int R, int HT, int items_per_wave) {
+// DET (k_det_relation_outer*): the wavefront's blocks are STORED into its own [R][HT][dkp][dkp] slot of `out` (= the workspace;
+// slot = the wavefront's slice of the item list, slices without an item of the relation store zeros) instead of added to out.
+#define HGT_OUTER_PARAMS                                                                                                             \
+    const HgtItem *__restrict__ items, const HgtPlanHeader *__restrict__ hdr, const int32_t *__restrict__ esrc,                        \
+        const int32_t *__restrict__ edst, const uint16_t *__restrict__ ertei, const float *__restrict__ w, const float *__restrict__ a, \
+        const float *__restrict__ rte_a, const float *__restrict__ b, float *__restrict__ out, int R, int HT, int items_per_wave
+#define HGT_OUTER_ARGS items, hdr, esrc, edst, ertei, w, a, rte_a, b, out, R, HT, items_per_wave
+
+template <int VEC, int LPH, bool RTE, bool DET>
+__device__ __forceinline__ void relation_outer_body(HGT_OUTER_PARAMS) {
     constexpr int DKP = VEC * LPH, DP = 64 * VEC, H = 64 / LPH;
     __shared__ __attribute__((aligned(16))) float s_b[4][DP + 4 * (64 / LPH)];
     const int lane = threadIdx.x & 63;
@@ -481,7 +634,8 @@ __global__ __launch_bounds__(256) void k_relation_outer(
     float* bounce = s_b[wib];
     const int n_items = hdr->n_items;
     const int first = (blockIdx.x * 4 + wib) * items_per_wave;
-    if (first >= n_items) return;
+    if (!DET && first >= n_items) return;
+    if constexpr (DET) out += (int64_t)(blockIdx.x * 4 + wib) * R * HT * DKP * DKP;
     float acc[VEC][DKP];      // rows k = p*VEC + i of head h, all DKP columns
 #pragma unroll
     for (int i = 0; i < VEC; ++i)
@@ -553,25 +707,29 @@ __global__ __launch_bounds__(256) void k_relation_outer(
             }
         }
     }
-    if (any) {
+    if (any || DET) {
         float* o = out + (((int64_t)rel_sel * HT + hg * H + h) * DKP + p * VEC) * DKP;
 #pragma unroll
         for (int i = 0; i < VEC; ++i)
 #pragma unroll
-            for (int c = 0; c < DKP; ++c) unsafeAtomicAdd(&o[i * DKP + c], acc[i][c]);
+            for (int c = 0; c < DKP; ++c) {
+                if constexpr (DET) o[i * DKP + c] = acc[i][c];
+                else unsafeAtomicAdd(&o[i * DKP + c], acc[i][c]);
+            }
     }
 }
+template <int VEC, int LPH, bool RTE>
+__global__ __launch_bounds__(256) void k_relation_outer(HGT_OUTER_PARAMS) { relation_outer_body<VEC, LPH, RTE, false>(HGT_OUTER_ARGS); }
+template <int VEC, int LPH, bool RTE>
+__global__ __launch_bounds__(256) void k_det_relation_outer(HGT_OUTER_PARAMS) { relation_outer_body<VEC, LPH, RTE, true>(HGT_OUTER_ARGS); }
 
 // The same sums on the matrix cores for 32-wide heads (d_k = 32: c2, c3): the outer products of an edge batch are one
 // v_mfma_f32_32x32x2_f32 per (head, pair of edges) -- operand A = the two scaled source rows' 32 head columns, B = the two target
 // rows' -- exact fp32 products, 256 matrix-core cycles per edge instead of ~550 vector-ALU cycles (128 FMAs per lane, LDS bounce,
 // two wave barriers per edge).  The rows of a batch are parked in LDS as [edge][column] (288-float stride: the two edges of a pair
 // fall into different bank halves); the 8 head blocks accumulate in 128 registers and are flushed once per wavefront.
-template <int VEC, bool RTE>
-__global__ __launch_bounds__(256, 2) void k_relation_outer_mfma(
-    const HgtItem* __restrict__ items, const HgtPlanHeader* __restrict__ hdr, const int32_t* __restrict__ esrc,
-    const int32_t* __restrict__ edst, const uint16_t* __restrict__ ertei, const float* __restrict__ w, const float* __restrict__ a,
-    const float* __restrict__ rte_a, const float* __restrict__ b, float* __restrict__ out, int R, int HT, int items_per_wave) {
+template <int VEC, bool RTE, bool DET>
+__device__ __forceinline__ void relation_outer_mfma_body(HGT_OUTER_PARAMS) {
     constexpr int DKP = 32, LPH = DKP / VEC, DP = 64 * VEC, H = 64 / LPH, UB = 8, RS = DP + 32;   // RS: LDS row stride in floats
     static_assert(DP % 32 == 0 && H * DKP == DP, "32-wide heads");
     __shared__ __attribute__((aligned(16))) float s_rows[4][2][UB][RS];
@@ -585,7 +743,8 @@ __global__ __launch_bounds__(256, 2) void k_relation_outer_mfma(
     float (*sb)[RS] = s_rows[wib][1];
     const int n_items = hdr->n_items;
     const int first = (blockIdx.x * 4 + wib) * items_per_wave;
-    if (first >= n_items) return;
+    if (!DET && first >= n_items) return;
+    if constexpr (DET) out += (int64_t)(blockIdx.x * 4 + wib) * R * HT * DKP * DKP;
     f32x16 acc[H];
 #pragma unroll
     for (int hh = 0; hh < H; ++hh)
@@ -647,7 +806,7 @@ __global__ __launch_bounds__(256, 2) void k_relation_outer_mfma(
             }
         }
     }
-    if (any) {
+    if (any || DET) {
         // C layout of a 32 x 32 block: column c = lane & 31, row k = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
 #pragma unroll
         for (int hh = 0; hh < H; ++hh) {
@@ -655,22 +814,53 @@ __global__ __launch_bounds__(256, 2) void k_relation_outer_mfma(
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int k = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                unsafeAtomicAdd(&o[k * DKP + (lane & 31)], acc[hh][r]);
+                if constexpr (DET) o[k * DKP + (lane & 31)] = acc[hh][r];
+                else unsafeAtomicAdd(&o[k * DKP + (lane & 31)], acc[hh][r]);
             }
         }
     }
 }
+template <int VEC, bool RTE>
+__global__ __launch_bounds__(256, 2) void k_relation_outer_mfma(HGT_OUTER_PARAMS) { relation_outer_mfma_body<VEC, RTE, false>(HGT_OUTER_ARGS); }
+template <int VEC, bool RTE>
+__global__ __launch_bounds__(256, 2) void k_det_relation_outer_mfma(HGT_OUTER_PARAMS) { relation_outer_mfma_body<VEC, RTE, true>(HGT_OUTER_ARGS); }
+#undef HGT_OUTER_PARAMS
+#undef HGT_OUTER_ARGS
+
+// items of the plan per wavefront of the atomic form (a function of the plan's sizes)
+static inline int outer_items_per_wave(int64_t max_items, int R) { return (max_items < 16384 ? 2 : 16) * (R + 1); }
 
 template <int VEC, int LPH>
 struct LaunchOuter {
+    // det_ipw > 0: the deterministic form with det_ipw items per wavefront, `out` = the workspace (one slot per wavefront)
     static int run(const HgtPlanView& pv, const float* w, const float* a, const float* rte_a, const float* b, float* out, int R, int HT,
-                   hipStream_t stream) {
+                   hipStream_t stream, int det_ipw = 0) {
         if constexpr (VEC * LPH * VEC <= 128 && VEC * LPH >= 4) {
+            if (det_ipw > 0) {
+                const int64_t dwaves = (pv.L.max_items + det_ipw - 1) / det_ipw;
+                dim3 dgrid((unsigned)((dwaves + 3) / 4), (unsigned)(HT / (64 / LPH)), (unsigned)R);
+                if constexpr (VEC * LPH == 32 && VEC <= 4) {
+                    if (rte_a)
+                        k_det_relation_outer_mfma<VEC, true><<<dgrid, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, w, a,
+                                                                                       rte_a, b, out, R, HT, det_ipw);
+                    else
+                        k_det_relation_outer_mfma<VEC, false><<<dgrid, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, w, a,
+                                                                                        rte_a, b, out, R, HT, det_ipw);
+                    return HGT_OK;
+                }
+                if (rte_a)
+                    k_det_relation_outer<VEC, LPH, true><<<dgrid, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, w, a, rte_a,
+                                                                                   b, out, R, HT, det_ipw);
+                else
+                    k_det_relation_outer<VEC, LPH, false><<<dgrid, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, w, a, rte_a,
+                                                                                    b, out, R, HT, det_ipw);
+                return HGT_OK;
+            }
             // ~16 items of the selected relation per wavefront (items are ordered (tile, relation)): at c2 3 000 wavefronts for
             // 1 024 SIMDs (64 items left the chip with fewer wavefronts than SIMDs) against 25 M flush atomics
             // (sampled batches -- a few thousand 16-edge items: 16 (R + 1) items per wavefront left 13 x R wavefronts walking ~250 edges
             //  each, 565 us per call at c3 (r6 timeline of a training step); 2 (R + 1) there)
-            const int ipw = (pv.L.max_items < 16384 ? 2 : 16) * (R + 1);
+            const int ipw = outer_items_per_wave(pv.L.max_items, R);
             const int64_t waves = (pv.L.max_items + ipw - 1) / ipw;
             dim3 grid((unsigned)((waves + 3) / 4), (unsigned)(HT / (64 / LPH)), (unsigned)R);
             if constexpr (VEC * LPH == 32 && VEC <= 4) {          // 32-wide heads: matrix-core form
@@ -712,11 +902,14 @@ struct OwBatch {                      // one thread's share of a batch: 4 column
     float w[2];
 };
 
-template <bool RTE>
-__global__ __launch_bounds__(256, 2) void k_relation_outer_wide(
-    const HgtItem* __restrict__ items, const HgtPlanHeader* __restrict__ hdr, const int32_t* __restrict__ esrc,
-    const int32_t* __restrict__ edst, const uint16_t* __restrict__ ertei, const float* __restrict__ w, const float* __restrict__ a,
-    const float* __restrict__ rte_a, const float* __restrict__ b, float* __restrict__ out, int HT, int dkp, int items_per_wg) {
+#define HGT_OUTER_WIDE_PARAMS                                                                                                        \
+    const HgtItem *__restrict__ items, const HgtPlanHeader *__restrict__ hdr, const int32_t *__restrict__ esrc,                        \
+        const int32_t *__restrict__ edst, const uint16_t *__restrict__ ertei, const float *__restrict__ w, const float *__restrict__ a, \
+        const float *__restrict__ rte_a, const float *__restrict__ b, float *__restrict__ out, int HT, int dkp, int items_per_wg
+// DET (k_det_relation_outer_wide): the workgroup's block is STORED into slot blockIdx.x ([gridDim.z][HT][dkp][dkp]) of `out` (= the
+// workspace); a slice without an item of the relation stores zeros
+template <bool RTE, bool DET>
+__device__ __forceinline__ void relation_outer_wide_body(HGT_OUTER_WIDE_PARAMS) {
     __shared__ __attribute__((aligned(16))) float s_rows[2][2][OW_UB][OW_RS];      // [buffer][a | b][edge][column]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -728,7 +921,8 @@ __global__ __launch_bounds__(256, 2) void k_relation_outer_wide(
     const int64_t ld = (int64_t)HT * dkp;
     const int n_items = hdr->n_items;
     const int first = blockIdx.x * items_per_wg;
-    if (first >= n_items) return;
+    if (!DET && first >= n_items) return;
+    if constexpr (DET) out += (int64_t)blockIdx.x * gridDim.z * HT * dkp * dkp;
     const int last = min(first + items_per_wg, n_items);
     // gather role: thread = (edge slot u of the batch (and u + 8), 4 columns)
     const int u = tid >> 5, c4 = (tid & 31) * 4;
@@ -806,7 +1000,7 @@ __global__ __launch_bounds__(256, 2) void k_relation_outer_wide(
             }
         }
     }
-    if (any) {
+    if (any || DET) {
         // C layout of a 32 x 32 tile: column c = lane & 31, row k = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
         float* o = out + (((int64_t)rel_sel * HT + h) * dkp + kb * 128 + qr * 64) * dkp + cb * 128 + qc * 64;
 #pragma unroll
@@ -816,10 +1010,20 @@ __global__ __launch_bounds__(256, 2) void k_relation_outer_wide(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int k = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * er;
-                    unsafeAtomicAdd(&o[(int64_t)k * dkp + j * 32 + cc], acc[i][j][r]);
+                    if constexpr (DET) o[(int64_t)k * dkp + j * 32 + cc] = acc[i][j][r];
+                    else unsafeAtomicAdd(&o[(int64_t)k * dkp + j * 32 + cc], acc[i][j][r]);
                 }
     }
 }
+template <bool RTE>
+__global__ __launch_bounds__(256, 2) void k_relation_outer_wide(HGT_OUTER_WIDE_PARAMS) {
+    relation_outer_wide_body<RTE, false>(items, hdr, esrc, edst, ertei, w, a, rte_a, b, out, HT, dkp, items_per_wg);
+}
+template <bool RTE>
+__global__ __launch_bounds__(256, 2) void k_det_relation_outer_wide(HGT_OUTER_WIDE_PARAMS) {
+    relation_outer_wide_body<RTE, true>(items, hdr, esrc, edst, ertei, w, a, rte_a, b, out, HT, dkp, items_per_wg);
+}
+#undef HGT_OUTER_WIDE_PARAMS
 
 static inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
@@ -998,6 +1202,320 @@ extern "C" int hgt_relation_outer_wide(const void* plan, int64_t N, int64_t E, i
     else
         k_relation_outer_wide<false><<<grid, 256, 0, (hipStream_t)stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, weights, a_src,
                                                                              rte_a, b_dst, out, (int)H, (int)dk_pad, ipw);
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+// =============================================================================================
+// Deterministic forms (include/hgt_hip.h, "Bit-reproducible training").  Slot counts: pure functions of the
+// arguments of the *_det_bytes calls.  DET_FLOOR: what every workspace may take on a small problem; large problems get a
+// fraction of the bytes of the operands they read (which the caller holds anyway: the saved Q|K|V of the layer bounds them).
+// =============================================================================================
+namespace {
+
+constexpr uint64_t DET_FLOOR = 32ull << 20;
+
+// floats of a workspace of n_slots partials of n_elems floats, + the segment sums of the two-pass reduce
+inline uint64_t det_ws_floats(int64_t n_slots, uint64_t n_elems) {
+    return (uint64_t)n_slots * n_elems + (n_slots > DET_TWO_PASS ? (uint64_t)((n_slots + DET_SEG - 1) / DET_SEG) * n_elems : 0);
+}
+// the largest slot count <= want whose workspace fits `budget` bytes (at least 1)
+inline int64_t det_fit_slots(int64_t want, uint64_t n_elems, uint64_t budget) {
+    const uint64_t per = n_elems * 4;
+    int64_t s = (int64_t)(budget / (per ? per : 1));
+    if (s > DET_TWO_PASS) s = (int64_t)(budget / (per + per / DET_SEG + 1));      // the segment sums come on top
+    if (s > want) s = want;
+    return s < 1 ? 1 : s;
+}
+
+// out[(i / per) * ogs + i % per] = sum over the n_slots partials ([slot][slot_stride] floats, the first n_elems of each) in slot order;
+// scratch: the segment sums (after the partials; only read when n_slots > DET_TWO_PASS)
+void det_reduce(const float* part, int64_t n_slots, int64_t slot_stride, int64_t n_elems, float* scratch, float* out, int64_t per,
+                int64_t ogs, hipStream_t stream) {
+    if (n_elems <= 0) return;
+    const unsigned bx = nblk(n_elems, 256);
+    if (n_slots > DET_TWO_PASS) {
+        const int nseg = (int)((n_slots + DET_SEG - 1) / DET_SEG);
+        k_det_reduce<<<dim3(bx, (unsigned)nseg), 256, 0, stream>>>(part, (int)n_slots, slot_stride, n_elems, DET_SEG, scratch, n_elems, n_elems, n_elems);
+        k_det_reduce<<<dim3(bx, 1), 256, 0, stream>>>(scratch, nseg, n_elems, n_elems, nseg, out, 0, per, ogs);
+    } else {
+        k_det_reduce<<<dim3(bx, 1), 256, 0, stream>>>(part, (int)n_slots, slot_stride, n_elems, (int)n_slots, out, 0, per, ogs);
+    }
+}
+
+inline bool det_ws_bad(const void* ws, uint64_t need) { return need > 0 && (!ws || ((uintptr_t)ws & 15) != 0); }
+
+// ---- node update: wavefronts = min(rows / 4, 4096, what DET_FLOOR holds), each a range of consecutive rows
+struct DetNub { int64_t slots, rows_per_wave, slot_floats; };
+inline DetNub det_nub(int64_t n_rows, int d, int T) {
+    DetNub p;
+    p.slot_floats = 2 * (int64_t)T * d + T;               // [T][d] d_ln_w | [T][d] d_ln_b | [T] d_alpha
+    int64_t want = (n_rows + 3) / 4;
+    if (want > 4096) want = 4096;
+    const int64_t s = det_fit_slots(want < 1 ? 1 : want, (uint64_t)p.slot_floats, DET_FLOOR);
+    p.rows_per_wave = n_rows > 0 ? (n_rows + s - 1) / s : 1;
+    p.slots = n_rows > 0 ? (n_rows + p.rows_per_wave - 1) / p.rows_per_wave : 1;
+    return p;
+}
+
+// ---- typed weight gradient: `chunks` row chunks per group; budget = max(DET_FLOOR, 1/16 of the bytes of A and B).  A slot holds the
+// weight partials and (bf16 x3 form: with_colsum) the column-sum partials; chunks x groups stays inside the grid's y / x extent
+inline int64_t det_wgrad_chunks(int n_groups, int64_t n_rows, int m, int n_cols, int64_t chunk_rows, bool with_colsum) {
+    const uint64_t budget = max(DET_FLOOR, (uint64_t)n_rows * (uint64_t)(m + n_cols) * 4 / 16);
+    int64_t want = (n_rows + chunk_rows - 1) / chunk_rows;
+    if (want > 1024) want = 1024;
+    if (want > 65535 / n_groups) want = 65535 / n_groups;
+    return det_fit_slots(want < 1 ? 1 : want, (uint64_t)n_groups * m * (n_cols + (with_colsum ? 1 : 0)), budget);
+}
+// ---- column sums: chunks of >= 256 rows, at most 1024 per group, inside DET_FLOOR / 2
+inline int64_t det_colsum_chunks(int n_groups, int64_t n_rows, int m) {
+    int64_t want = (n_rows + 255) / 256;
+    if (want > 1024) want = 1024;
+    return det_fit_slots(want < 1 ? 1 : want, (uint64_t)n_groups * m, DET_FLOOR / 2);
+}
+inline uint64_t det_chunk_ws_floats(int64_t chunks, uint64_t elems) { return chunks > 1 ? det_ws_floats(chunks, elems) : 0; }
+
+// ---- relation outer products: slices of the plan's item list; budget = max(DET_FLOOR, 1/4 of the bytes of Q|K|V)
+struct DetOuter { int64_t slots; int ipw; uint64_t slot_floats; };
+inline DetOuter det_outer(int64_t N, int64_t max_items, int R, int H, int dkp, bool wide) {
+    DetOuter p;
+    p.slot_floats = (uint64_t)R * H * dkp * dkp;
+    const uint64_t budget = max(DET_FLOOR, (uint64_t)N * H * dkp * 4 * 3 / 4);
+    const int ipw0 = wide ? (max_items < 16384 ? OW_ITEMS_SMALL : OW_ITEMS_LARGE) * (R + 1) : outer_items_per_wave(max_items, R);
+    const int64_t want = max((int64_t)1, (max_items + ipw0 - 1) / ipw0);
+    // (the narrow kernels launch whole workgroups of four wavefronts = four slots: four is the least they take, also where four
+    //  partials pass the budget -- 4 R H dkp^2 floats, dkp <= 64: more than DET_FLOOR only from R H > 512 on)
+    int64_t s = det_fit_slots(want + (wide ? 0 : 3), p.slot_floats, budget);
+    if (!wide) s = max((int64_t)4, s / 4 * 4);
+    const int64_t ipw = max((int64_t)ipw0, (max_items + s - 1) / s);
+    p.ipw = (int)ipw;
+    const int64_t used = max((int64_t)1, (max_items + ipw - 1) / ipw);
+    p.slots = wide ? used : (used + 3) / 4 * 4;
+    return p;
+}
+
+}  // namespace
+
+extern "C" int hgt_node_update_bwd_det_bytes(int64_t n_rows, int32_t d, int32_t n_types, uint64_t* out) {
+    if (!out || n_rows < 0 || d <= 0 || d > 64 * NUB_MAXC_WIDE || n_types <= 0) return HGT_ERR_INVALID_ARG;
+    const DetNub p = det_nub(n_rows, d, n_types);
+    *out = n_rows == 0 ? 0 : det_ws_floats(p.slots, (uint64_t)p.slot_floats) * 4;
+    return HGT_OK;
+}
+
+extern "C" int hgt_node_update_bwd_det(const float* grad_out, const float* trans, const float* x, int64_t ldx, const int64_t* node_type,
+                                       const float* skip, const float* ln_w, int32_t use_norm, int32_t shared_norm, const float* drop_mask,
+                                       int64_t n_rows, int32_t d, int32_t n_types, float* d_trans, float* dx, int64_t ld_dx,
+                                       float* d_alpha, float* d_ln_w, float* d_ln_b, void* ws, uint64_t ws_bytes, void* stream) {
+    if (!grad_out || !trans || !x || !node_type || !d_trans || !dx || (skip && !d_alpha) || n_rows < 0 || d <= 0 ||
+        d > 64 * NUB_MAXC_WIDE || n_types <= 0)
+        return HGT_ERR_INVALID_ARG;
+    if (use_norm && (!ln_w || !d_ln_w || !d_ln_b)) return HGT_ERR_INVALID_ARG;
+    uint64_t need = 0;
+    hgt_node_update_bwd_det_bytes(n_rows, d, n_types, &need);
+    if (det_ws_bad(ws, need)) return HGT_ERR_INVALID_ARG;
+    if (ws_bytes < need) return HGT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t ln_elems = (int64_t)(shared_norm ? 1 : n_types) * d;
+    if (n_rows == 0) {      // overwritten outputs: zeros
+        if (use_norm) { (void)hipMemsetAsync(d_ln_w, 0, ln_elems * 4, st); (void)hipMemsetAsync(d_ln_b, 0, ln_elems * 4, st); }
+        if (skip) (void)hipMemsetAsync(d_alpha, 0, (size_t)n_types * 4, st);
+        HGT_CHECK_LAUNCH();
+        return HGT_OK;
+    }
+    const DetNub p = det_nub(n_rows, d, n_types);
+    float* part = (float*)ws;
+    float* scratch = part + p.slots * p.slot_floats;
+    const int64_t td = (int64_t)n_types * d;
+    (void)hipMemsetAsync(part, 0, (size_t)(p.slots * p.slot_floats) * 4, st);      // a wavefront adds to its slot once per run of one type
+    auto* kernel = d <= 64 * NUB_MAXC ? k_det_node_update_bwd : k_det_node_update_bwd_wide;
+    kernel<<<nblk(p.slots, 4), 256, 0, st>>>(grad_out, trans, x, ldx, node_type, skip, ln_w, use_norm, drop_mask, n_rows, d, n_types, d_trans,
+                                            dx, ld_dx, skip ? part + 2 * td : nullptr, use_norm ? part : nullptr,
+                                            use_norm ? part + td : nullptr, shared_norm, (int)p.rows_per_wave, p.slot_floats);
+    if (use_norm) {
+        det_reduce(part, p.slots, p.slot_floats, ln_elems, scratch, d_ln_w, ln_elems, ln_elems, st);
+        det_reduce(part + td, p.slots, p.slot_floats, ln_elems, scratch, d_ln_b, ln_elems, ln_elems, st);
+    }
+    if (skip) det_reduce(part + 2 * td, p.slots, p.slot_floats, n_types, scratch, d_alpha, n_types, n_types, st);
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+// zero the [n_groups][per] blocks of a grouped output (group stride ogs floats)
+static void det_zero_groups(float* out, int n_groups, int64_t per, int64_t ogs, hipStream_t st) {
+    (void)hipMemset2DAsync(out, (size_t)ogs * 4, 0, (size_t)per * 4, (size_t)n_groups, st);
+}
+
+extern "C" int hgt_typed_wgrad_det_bytes(int32_t n_groups, int64_t n_rows, int32_t m, int32_t n_cols, uint64_t* out) {
+    if (!out || n_groups <= 0 || n_rows < 0 || m <= 0 || n_cols <= 0) return HGT_ERR_INVALID_ARG;
+    if (n_groups > 65535) return HGT_ERR_TOO_LARGE;
+    *out = det_chunk_ws_floats(det_wgrad_chunks(n_groups, n_rows, m, n_cols, WG_ROWS, false), (uint64_t)n_groups * m * n_cols) * 4;
+    return HGT_OK;
+}
+
+extern "C" int hgt_typed_wgrad_det(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rows,
+                                   const int32_t* group_off, int32_t n_groups, int64_t n_rows, int32_t m, int32_t n_cols, float* out,
+                                   int64_t out_group_stride, void* ws, uint64_t ws_bytes, void* stream) {
+    if (!A || !B || !rows || !group_off || !out || n_groups <= 0 || n_rows < 0 || m <= 0 || n_cols <= 0 ||
+        out_group_stride < (int64_t)m * n_cols)
+        return HGT_ERR_INVALID_ARG;
+    uint64_t need = 0;
+    int rcb = hgt_typed_wgrad_det_bytes(n_groups, n_rows, m, n_cols, &need);
+    if (rcb != HGT_OK) return rcb;
+    if (det_ws_bad(ws, need)) return HGT_ERR_INVALID_ARG;
+    if (ws_bytes < need) return HGT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t per = (int64_t)m * n_cols, elems = per * n_groups;
+    if (n_rows == 0) { det_zero_groups(out, n_groups, per, out_group_stride, st); HGT_CHECK_LAUNCH(); return HGT_OK; }
+    const int64_t chunks = det_wgrad_chunks(n_groups, n_rows, m, n_cols, WG_ROWS, false);
+    const int vecA = ((lda & 3) == 0 && ((uintptr_t)A & 15) == 0), vecB = ((ldb & 3) == 0 && ((uintptr_t)B & 15) == 0);
+    float* part = chunks > 1 ? (float*)ws : out;
+    dim3 grid((unsigned)(chunks * n_groups), (unsigned)((m + 63) / 64), (unsigned)((n_cols + 63) / 64));
+    k_det_typed_wgrad<<<grid, 256, 0, st>>>(A, lda, B, ldb, rows, group_off, n_groups, m, n_cols, part, chunks > 1 ? per : out_group_stride,
+                                           vecA, vecB, (int)chunks);
+    if (chunks > 1) det_reduce(part, chunks, elems, elems, part + chunks * elems, out, per, out_group_stride, st);
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+extern "C" int hgt_typed_wgrad_bf16x3_det_bytes(int32_t n_groups, int64_t n_rows, int32_t m, int32_t n_cols, uint64_t* out) {
+    if (!out || n_groups <= 0 || n_rows < 0 || m <= 0 || n_cols <= 0) return HGT_ERR_INVALID_ARG;
+    if (n_groups > 65535) return HGT_ERR_TOO_LARGE;
+    const int64_t chunks = det_wgrad_chunks(n_groups, n_rows, m, n_cols, WX_ROWS, true);
+    // the weight partials, then the column-sum partials (always provided for: the size does not depend on the colsum argument)
+    *out = (det_chunk_ws_floats(chunks, (uint64_t)n_groups * m * n_cols) + det_chunk_ws_floats(chunks, (uint64_t)n_groups * m)) * 4;
+    return HGT_OK;
+}
+
+extern "C" int hgt_typed_wgrad_bf16x3_det(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rows,
+                                          const int32_t* group_off, int32_t n_groups, int64_t n_rows, int32_t m, int32_t n_cols,
+                                          float* out, int64_t out_group_stride, float* colsum, int64_t colsum_group_stride, void* ws,
+                                          uint64_t ws_bytes, void* stream) {
+    if (!A || !B || !rows || !group_off || !out || n_groups <= 0 || n_rows < 0 || m <= 0 || n_cols <= 0 ||
+        out_group_stride < (int64_t)m * n_cols || (colsum && colsum_group_stride < m))
+        return HGT_ERR_INVALID_ARG;
+    uint64_t need = 0;
+    int rcb = hgt_typed_wgrad_bf16x3_det_bytes(n_groups, n_rows, m, n_cols, &need);
+    if (rcb != HGT_OK) return rcb;
+    if (det_ws_bad(ws, need)) return HGT_ERR_INVALID_ARG;
+    if (ws_bytes < need) return HGT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t per = (int64_t)m * n_cols, elems = per * n_groups, cs_elems = (int64_t)m * n_groups;
+    if (n_rows == 0) {
+        det_zero_groups(out, n_groups, per, out_group_stride, st);
+        if (colsum) det_zero_groups(colsum, n_groups, m, colsum_group_stride, st);
+        HGT_CHECK_LAUNCH();
+        return HGT_OK;
+    }
+    const int64_t chunks = det_wgrad_chunks(n_groups, n_rows, m, n_cols, WX_ROWS, true);
+    const int n_mt = (m + WX_T - 1) / WX_T, n_nt = (n_cols + WX_T - 1) / WX_T;
+    float* part = chunks > 1 ? (float*)ws : out;
+    float* cs_part = chunks > 1 ? (float*)ws + det_ws_floats(chunks, (uint64_t)elems) : colsum;
+    dim3 grid((unsigned)(n_mt * n_nt), (unsigned)(chunks * n_groups));
+    k_det_typed_wgrad_x3<<<grid, 256, 0, st>>>(A, lda, B, ldb, rows, group_off, n_groups, m, n_cols, n_mt, part,
+                                              chunks > 1 ? per : out_group_stride, colsum ? cs_part : nullptr,
+                                              chunks > 1 ? (int64_t)m : colsum_group_stride, (int)chunks);
+    if (chunks > 1) {
+        det_reduce(part, chunks, elems, elems, part + chunks * elems, out, per, out_group_stride, st);
+        if (colsum) det_reduce(cs_part, chunks, cs_elems, cs_elems, cs_part + chunks * cs_elems, colsum, m, colsum_group_stride, st);
+    }
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+extern "C" int hgt_typed_colsum_det_bytes(int32_t n_groups, int64_t n_rows, int32_t m, uint64_t* out) {
+    if (!out || n_groups <= 0 || n_rows < 0 || m <= 0) return HGT_ERR_INVALID_ARG;
+    *out = det_chunk_ws_floats(det_colsum_chunks(n_groups, n_rows, m), (uint64_t)n_groups * m) * 4;
+    return HGT_OK;
+}
+
+extern "C" int hgt_typed_colsum_det(const float* A, int64_t lda, const int32_t* rows, const int32_t* group_off, int32_t n_groups,
+                                    int64_t n_rows, int32_t m, float* out, int64_t out_group_stride, void* ws, uint64_t ws_bytes,
+                                    void* stream) {
+    if (!A || !rows || !group_off || !out || n_groups <= 0 || n_rows < 0 || m <= 0 || out_group_stride < m) return HGT_ERR_INVALID_ARG;
+    uint64_t need = 0;
+    hgt_typed_colsum_det_bytes(n_groups, n_rows, m, &need);
+    if (det_ws_bad(ws, need)) return HGT_ERR_INVALID_ARG;
+    if (ws_bytes < need) return HGT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rows == 0) { det_zero_groups(out, n_groups, m, out_group_stride, st); HGT_CHECK_LAUNCH(); return HGT_OK; }
+    const int64_t chunks = det_colsum_chunks(n_groups, n_rows, m), elems = (int64_t)m * n_groups;
+    float* part = chunks > 1 ? (float*)ws : out;
+    k_det_typed_colsum<<<nblk(chunks * n_groups, 4), 256, 0, st>>>(A, lda, rows, group_off, n_groups, m, part,
+                                                                   chunks > 1 ? (int64_t)m : out_group_stride, (int)chunks);
+    if (chunks > 1) det_reduce(part, chunks, elems, elems, part + chunks * elems, out, m, out_group_stride, st);
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+static int outer_det_bytes(bool wide, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad, uint64_t* out) {
+    if (!out || N < 0 || E < 0 || T <= 0 || R <= 0 || H <= 0 || dk_pad <= 0) return HGT_ERR_INVALID_ARG;
+    if (wide ? (dk_pad != 128 && dk_pad != 256) : (64 % H != 0 || dk_pad % (64 / H) != 0)) return wide ? HGT_ERR_UNSUPPORTED : HGT_ERR_INVALID_ARG;
+    if (E == 0) { *out = 0; return HGT_OK; }
+    const DetOuter p = det_outer(N, hgt_plan_layout(N, E, T, R).max_items, R, H, dk_pad, wide);
+    *out = det_ws_floats(p.slots, p.slot_floats) * 4;
+    return HGT_OK;
+}
+extern "C" int hgt_relation_outer_det_bytes(int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad, uint64_t* out) {
+    return outer_det_bytes(false, N, E, T, R, H, dk_pad, out);
+}
+extern "C" int hgt_relation_outer_wide_det_bytes(int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad, uint64_t* out) {
+    return outer_det_bytes(true, N, E, T, R, H, dk_pad, out);
+}
+
+extern "C" int hgt_relation_outer_det(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
+                                      const float* weights, const float* a_src, const float* rte_a, const float* b_dst, float* out,
+                                      void* ws, uint64_t ws_bytes, void* stream) {
+    if (!plan || !a_src || !b_dst || !out || (E > 0 && !weights) || H <= 0 || R <= 0 || 64 % H != 0 || dk_pad <= 0) return HGT_ERR_INVALID_ARG;
+    const int lph = 64 / H;
+    if (dk_pad % lph != 0) return HGT_ERR_INVALID_ARG;
+    uint64_t need = 0;
+    int rc = outer_det_bytes(false, N, E, T, R, H, dk_pad, &need);
+    if (rc != HGT_OK) return rc;
+    if (det_ws_bad(ws, need)) return HGT_ERR_INVALID_ARG;
+    if (ws_bytes < need) return HGT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t elems = (int64_t)R * H * dk_pad * dk_pad;
+    if (E == 0) { (void)hipMemsetAsync(out, 0, (size_t)elems * 4, st); HGT_CHECK_LAUNCH(); return HGT_OK; }
+    HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
+    const DetOuter p = det_outer(N, pv.L.max_items, R, H, dk_pad, false);
+    int vec = dk_pad / lph, l2 = lph;
+    while (vec * dk_pad > 128 && vec > 1 && l2 * 2 <= 64) { vec /= 2; l2 *= 2; }
+    float* part = (float*)ws;
+    rc = dispatch_layout<LaunchOuter>(vec, l2, pv, weights, a_src, rte_a, b_dst, part, (int)R, (int)H, st, p.ipw);
+    if (rc != HGT_OK) return rc;
+    det_reduce(part, p.slots, elems, elems, part + p.slots * elems, out, elems, elems, st);
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+extern "C" int hgt_relation_outer_wide_det(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
+                                           const float* weights, const float* a_src, const float* rte_a, const float* b_dst, float* out,
+                                           void* ws, uint64_t ws_bytes, void* stream) {
+    if (!plan || !a_src || !b_dst || !out || (E > 0 && !weights) || H <= 0 || R <= 0 || dk_pad <= 0) return HGT_ERR_INVALID_ARG;
+    if (dk_pad != 128 && dk_pad != 256) return HGT_ERR_UNSUPPORTED;
+    if ((((uintptr_t)a_src | (uintptr_t)b_dst | (uintptr_t)rte_a) & 15) != 0) return HGT_ERR_INVALID_ARG;      // 16-byte row loads
+    const int64_t blocks = (int64_t)H * (dk_pad / 128) * (dk_pad / 128);
+    if (blocks > 65535 || R > 65535) return HGT_ERR_TOO_LARGE;
+    uint64_t need = 0;
+    int rc = outer_det_bytes(true, N, E, T, R, H, dk_pad, &need);
+    if (rc != HGT_OK) return rc;
+    if (det_ws_bad(ws, need)) return HGT_ERR_INVALID_ARG;
+    if (ws_bytes < need) return HGT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t elems = (int64_t)R * H * dk_pad * dk_pad;
+    if (E == 0) { (void)hipMemsetAsync(out, 0, (size_t)elems * 4, st); HGT_CHECK_LAUNCH(); return HGT_OK; }
+    HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
+    const DetOuter p = det_outer(N, pv.L.max_items, R, H, dk_pad, true);
+    float* part = (float*)ws;
+    dim3 grid((unsigned)p.slots, (unsigned)blocks, (unsigned)R);
+    if (rte_a)
+        k_det_relation_outer_wide<true><<<grid, 256, 0, st>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, weights, a_src, rte_a, b_dst,
+                                                             part, (int)H, (int)dk_pad, p.ipw);
+    else
+        k_det_relation_outer_wide<false><<<grid, 256, 0, st>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, weights, a_src, rte_a, b_dst,
+                                                              part, (int)H, (int)dk_pad, p.ipw);
+    det_reduce(part, p.slots, elems, elems, part + p.slots * elems, out, elems, elems, st);
     HGT_CHECK_LAUNCH();
     return HGT_OK;
 }

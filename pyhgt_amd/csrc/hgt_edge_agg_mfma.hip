@@ -1460,16 +1460,16 @@ int hgt_edge_aggregate_update_sel(HGT_AGGUPD_PARAMS, int64_t q_begin, int64_t q_
 
 // out[i][ld_out] = sum_rel ( sum_{e in (i,rel)} w_e rows[src_e] ) F[rel]  -- the aggregation kernel without the softmax: the edge
 // weights are given.  The backward pass is three of these (include/hgt_hip.h).
-extern "C" int hgt_edge_spmm(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
-                             const float* weights, const float* rows, const float* rte_rows, const float* f_p, const void* f_frag,
-                             float* out, int64_t ld_out, int64_t n_q_rows, void* hub_ws, void* stream) {
+static int edge_spmm_impl(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad, const float* weights,
+                          const float* rows, const float* rte_rows, const float* f_p, const void* f_frag, float* out, int64_t ld_out,
+                          int64_t n_q_rows, void* hub_ws, void* stream, bool det_hubs) {
     if (!plan || !rows || !f_p || !f_frag || !out || (E > 0 && !weights) || H <= 0 || 64 % H != 0 || dk_pad <= 0) return HGT_ERR_INVALID_ARG;
     const int64_t NQ = (n_q_rows > 0 && n_q_rows <= N) ? n_q_rows : N;
     if (NQ == 0) return HGT_OK;
     const int lph = 64 / H;
     if (dk_pad % lph != 0 || ld_out < (int64_t)H * dk_pad || (ld_out & 3) != 0) return HGT_ERR_INVALID_ARG;
     HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
-    HgtHubBuffers hb = carve_hub(hub_ws, pv, H, E);
+    HgtHubBuffers hb = det_hubs ? carve_hub(hub_ws, pv, H, E, dk_pad, R, true) : carve_hub(hub_ws, pv, H, E);
     const int sp = mfma_split_for(dk_pad / lph, lph);
     if (sp == 0) return HGT_ERR_UNSUPPORTED;
     int rc = mfma_agg_dispatch(dk_pad / lph / sp, lph * sp, false, pv, weights, rows, rte_rows, f_p, (const unsigned short*)f_frag, out,
@@ -1477,5 +1477,25 @@ extern "C" int hgt_edge_spmm(const void* plan, int64_t N, int64_t E, int32_t T, 
     if (rc != HGT_OK) return rc;
     HGT_CHECK_LAUNCH();
     return HGT_OK;
+}
+extern "C" int hgt_edge_spmm(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
+                             const float* weights, const float* rows, const float* rte_rows, const float* f_p, const void* f_frag,
+                             float* out, int64_t ld_out, int64_t n_q_rows, void* hub_ws, void* stream) {
+    return edge_spmm_impl(plan, N, E, T, R, H, dk_pad, weights, rows, rte_rows, f_p, f_frag, out, ld_out, n_q_rows, hub_ws, stream, false);
+}
+// hgt_edge_spmm with the hub targets summed per piece in piece order (the deterministic hub mode of the aggregation): ws of
+// hgt_edge_spmm_det_bytes = hgt_hub_workspace_bytes_ex(.., 1) bytes
+extern "C" int hgt_edge_spmm_det_bytes(int64_t n_edges, int32_t n_heads, int32_t dk_pad, int32_t n_relations, uint64_t* out) {
+    return hgt_hub_workspace_bytes_ex(n_edges, n_heads, dk_pad, n_relations, 1, out);
+}
+extern "C" int hgt_edge_spmm_det(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
+                                 const float* weights, const float* rows, const float* rte_rows, const float* f_p, const void* f_frag,
+                                 float* out, int64_t ld_out, int64_t n_q_rows, void* ws, uint64_t ws_bytes, void* stream) {
+    uint64_t need = 0;
+    int rc = hgt_edge_spmm_det_bytes(E, H, dk_pad, R, &need);
+    if (rc != HGT_OK) return rc;
+    if (!ws || ((uintptr_t)ws & 15) != 0) return HGT_ERR_INVALID_ARG;
+    if (ws_bytes < need) return HGT_ERR_WORKSPACE;
+    return edge_spmm_impl(plan, N, E, T, R, H, dk_pad, weights, rows, rte_rows, f_p, f_frag, out, ld_out, n_q_rows, ws, stream, true);
 }
 #endif   // main translation unit

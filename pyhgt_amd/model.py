@@ -22,8 +22,9 @@ __all__ = ["GNN", "Classifier", "Matcher"]
 
 class GNN(nn.Module):
     def __init__(self, in_dim, n_hid, num_types, num_relations, n_heads, n_layers, dropout=0.2, conv_name='hgt',
-                 prev_norm=False, last_norm=False, use_RTE=True):
+                 prev_norm=False, last_norm=False, use_RTE=True, deterministic=False):
         super().__init__()
+        self.deterministic = bool(deterministic)      # bit-reproducible training (autograd.set_deterministic reaches the layers too)
         self.gcs = nn.ModuleList()
         self.num_types = num_types
         self.in_dim = in_dim
@@ -37,6 +38,9 @@ class GNN(nn.Module):
                                     use_norm=last_norm, use_RTE=use_RTE))
         self._packed = None
         self._packed_key = None
+        if deterministic:
+            for gc in self.gcs:
+                gc.base_conv.deterministic = True
 
     def __getstate__(self):
         st = dict(self.__dict__)
@@ -111,11 +115,11 @@ class GNN(nn.Module):
         if torch.is_grad_enabled() and (node_feature.requires_grad or any(p.requires_grad for p in self.parameters())):
             # training / differentiable path: the adapter through TypedLinearFunction (typed weight
             # gradient kernels), tanh + dropout as in model.py:70-76, then the layers' own autograd path
-            from .autograd import TypedLinearFunction
+            from .autograd import TypedLinearFunction, takes_det_route
             w = torch.stack([lin.weight for lin in self.adapt_ws]).float()
             b = torch.stack([lin.bias for lin in self.adapt_ws]).float()
             h = TypedLinearFunction.apply((rows.rows_all, rows.off_all, plan), self.num_types, conv0.precision,
-                                          node_feature.float(), w, b)
+                                          node_feature.float(), w, b, takes_det_route(self))
             h = self.drop(torch.tanh(h))        # rows of a type no adapter claims stay 0 (model.py:70)
             for gc in self.gcs:
                 h = gc.base_conv(h, node_type, edge_index, edge_type, edge_time, plan=plan)
@@ -158,7 +162,12 @@ class GNN(nn.Module):
         return h
 
 
-def _dense_linear(x, weight, bias, scale=1.0):
+def _det(module):
+    from .autograd import takes_det_route      # (lazily, like GNN.forward: autograd imports conv, not model)
+    return takes_det_route(module)
+
+
+def _dense_linear(x, weight, bias, scale=1.0, deterministic=False):
     """y = (x @ weight^T + bias) * scale on the exact fp32 MFMA typed-linear kernel (one group = every row)."""
     lib = _lib.load()
     if not x.is_cuda:
@@ -172,7 +181,7 @@ def _dense_linear(x, weight, bias, scale=1.0):
         off = torch.tensor([0, n], dtype=torch.int32, device=x.device)
         w = (weight.float() * scale).unsqueeze(0)
         b = (bias.float() * scale).unsqueeze(0) if bias is not None else None
-        return TypedLinearFunction.apply((rows.data_ptr(), off.data_ptr(), (rows, off)), 1, "fp32", xx, w, b)
+        return TypedLinearFunction.apply((rows.data_ptr(), off.data_ptr(), (rows, off)), 1, "fp32", xx, w, b, deterministic)
     x = x.detach().float().contiguous()
     n, k = x.shape
     n_out = weight.size(0)
@@ -189,13 +198,14 @@ def _dense_linear(x, weight, bias, scale=1.0):
 class Classifier(nn.Module):
     """model.py:3-14: log_softmax(linear(x).squeeze(), dim=-1) on the seed rows."""
 
-    def __init__(self, n_hid, n_out):
+    def __init__(self, n_hid, n_out, deterministic=False):
         super().__init__()
+        self.deterministic = bool(deterministic)
         self.n_hid, self.n_out = n_hid, n_out
         self.linear = nn.Linear(n_hid, n_out)
 
     def forward(self, x):
-        tx = _dense_linear(x.reshape(-1, self.n_hid), self.linear.weight, self.linear.bias)
+        tx = _dense_linear(x.reshape(-1, self.n_hid), self.linear.weight, self.linear.bias, deterministic=_det(self))
         if tx.requires_grad:
             return torch.log_softmax(tx, dim=-1).reshape(*x.shape[:-1], self.n_out).squeeze()      # model.py:11, under autograd
         out = torch.empty_like(tx)
@@ -210,8 +220,9 @@ class Matcher(nn.Module):
     """model.py:16-49: scaled dot product between projected node pairs (link prediction), with the reference's
     inference-time cache of the projected candidates."""
 
-    def __init__(self, n_hid):
+    def __init__(self, n_hid, deterministic=False):
         super().__init__()
+        self.deterministic = bool(deterministic)
         self.left_linear = nn.Linear(n_hid, n_hid)
         self.right_linear = nn.Linear(n_hid, n_hid)
         self.sqrt_hd = math.sqrt(n_hid)
@@ -219,11 +230,11 @@ class Matcher(nn.Module):
         self.cache = None
 
     def forward(self, x, y, infer=False, pair=False):
-        ty = _dense_linear(y, self.right_linear.weight, self.right_linear.bias)
+        ty = _dense_linear(y, self.right_linear.weight, self.right_linear.bias, deterministic=_det(self))
         if infer and self.cache is not None:
             tx = self.cache
         else:
-            tx = _dense_linear(x, self.left_linear.weight, self.left_linear.bias)
+            tx = _dense_linear(x, self.left_linear.weight, self.left_linear.bias, deterministic=_det(self))
             if infer:
                 self.cache = tx
         if pair and (tx.requires_grad or ty.requires_grad):
@@ -234,7 +245,7 @@ class Matcher(nn.Module):
                        "hgt_row_dot")
             return out
         # tx @ ty^T / sqrt(n_hid): the typed-linear kernel with ty as the "weight" and no bias
-        return _dense_linear(tx, ty / self.sqrt_hd, None)
+        return _dense_linear(tx, ty / self.sqrt_hd, None, deterministic=_det(self))
 
     def __repr__(self):
         return '{}(n_hid={})'.format(self.__class__.__name__, self.n_hid)

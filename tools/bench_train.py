@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Training-step timing of one HGTConv at BASELINE.json configs[1]: forward + backward through
 pyhgt_amd/autograd.py against the inference forward, plan (and transposed plan) cached.  Sizes from the environment: HGT_TRAIN_N,
-HGT_TRAIN_E (nodes, edges), HGT_TRAIN_D, HGT_TRAIN_H (width, heads); HGT_TRAIN_NO_SMALL=1 skips the sampled-batch part."""
+HGT_TRAIN_E (nodes, edges), HGT_TRAIN_D, HGT_TRAIN_H (width, heads); HGT_TRAIN_NO_SMALL=1 skips the sampled-batch part.
+--deterministic (or HGT_TRAIN_DETERMINISTIC=1) times the bit-reproducible mode (deterministic=True on every module)."""
 import json
 import os
 import sys
@@ -46,6 +47,9 @@ def minimal_backward_bytes(N, E, d, H):
             "Q|K|V weight gradients + dx (read x, dQ|dK|dV; write dx)": 8 * Nd}
 
 
+DETERMINISTIC = "--deterministic" in sys.argv or os.environ.get("HGT_TRAIN_DETERMINISTIC", "0") not in ("", "0")
+
+
 def sampled_batches(dev):
     """Training step (forward + backward, dropout on) at the sizes the reference's scripts actually step on (round-5 review, task 8):
     the c3 surrogate (one layer, d = 256) and the c5 / published ogbn-mag surrogates (whole GNN), wall-clock us per step."""
@@ -67,7 +71,7 @@ def sampled_batches(dev):
 
     batch = synthetic_sampled_batch("mag", n_seed=128, width=128, depth=6, feat_dim=256, mean_degree=4.0, seed=3)
     x, nt, tm, ei, et, _, ed = [t.to(dev) if torch.is_tensor(t) else t for t in to_torch_layout(*batch)]
-    layer = HGTConv(256, 256, 4, len(ed), 8, 0.2, True, True).to(dev).train()
+    layer = HGTConv(256, 256, 4, len(ed), 8, 0.2, True, True, deterministic=DETERMINISTIC).to(dev).train()
     plan = GraphPlan(nt, ei, et, tm, 4, len(ed))
     xg = x.clone().requires_grad_(True)
     res["c3_layer"] = {"N": int(nt.numel()), "E": int(et.numel()), "d": 256,
@@ -79,7 +83,7 @@ def sampled_batches(dev):
         batch = synthetic_sampled_batch(c["schema"], n_seed=c["n_seed"], width=c["width"], depth=c["depth"], feat_dim=c["feat_dim"],
                                         mean_degree=c["mean_degree"], seed=c["seed"])
         x, nt, tm, ei, et, _, ed = [t.to(dev) if torch.is_tensor(t) else t for t in to_torch_layout(*batch)]
-        gnn = GNN(c["in_dim"], c["n_hid"], c["T"], len(ed), c["H"], c["L"], 0.2, "hgt", c["norm"], c["norm"], True).to(dev).train()
+        gnn = GNN(c["in_dim"], c["n_hid"], c["T"], len(ed), c["H"], c["L"], 0.2, "hgt", c["norm"], c["norm"], True, deterministic=DETERMINISTIC).to(dev).train()
         res[key] = {"N": int(nt.numel()), "E": int(et.numel()), "n_hid": c["n_hid"], "layers": c["L"],
                     "fwd_bwd_us": step_us(lambda: gnn(x, nt, tm, ei, et), list(gnn.parameters()))}
     return res
@@ -91,7 +95,7 @@ def main():
     N, E, d, T, R, H = (int(os.environ.get("HGT_TRAIN_N", 1000000)), int(os.environ.get("HGT_TRAIN_E", 10000000)),
                         int(os.environ.get("HGT_TRAIN_D", 256)), 4, 8, int(os.environ.get("HGT_TRAIN_H", 8)))
     x, nt, ei, et, tm = [t.to(dev) for t in synthetic_typed_graph(N, E, d, T, R, seed=1)]
-    layer = HGTConv(d, d, T, R, H, 0.2, True, False).to(dev)
+    layer = HGTConv(d, d, T, R, H, 0.2, True, False, deterministic=DETERMINISTIC).to(dev)
     plan = GraphPlan(nt, ei, et, None, T, R)
     res = {}
     layer.eval()
@@ -121,6 +125,7 @@ def main():
         torch.cuda.synchronize()
         res["training_" + phase] = (time.perf_counter() - t0) / iters * 1e3
     res["N"], res["E"], res["d"], res["H"] = N, E, d, H
+    res["deterministic"] = DETERMINISTIC
     res["peak_mem_gb"] = torch.cuda.max_memory_allocated() / 2 ** 30
     fwd_b, bwd_b = training_step_bytes(N, E, d, H)
     bf, bb = sum(fwd_b.values()), sum(bwd_b.values())
