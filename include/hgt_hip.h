@@ -404,6 +404,17 @@ int hgt_row_dot(const float* x, const float* y, int64_t n_rows, int32_t d, float
 
 /* row gather used to pack halo rows for the multi-GPU exchange: out[i] = x[idx[i]] */
 int hgt_gather_rows(const float* x, int64_t ldx, const int32_t* idx, int64_t n, int32_t d, float* out, void* stream);
+/* The inverse of hgt_gather_rows with an addition: gradients of halo rows return to the rows' owners (pyhgt_amd.dist,
+ * HaloPlan.return_grads).  src [*, ld_src] holds the received rows in the order of the rank's send list; rows int32[n_rows] the
+ * DISTINCT destination rows that receive something, ptr int32[n_rows + 1] / pos int32[ptr[n_rows]] the CSR list of the source rows of
+ * each (HaloPlan.return_index):
+ *   dst[rows[i]][0..d) += src[pos[ptr[i]]] + ... + src[pos[ptr[i+1]-1]], added one after the other in that order, starting
+ * from dst's value; rows[] holds DISTINCT row ids, so no two wavefronts write one row: no atomics, bits fixed by the lists.
+ * Plain fp32 adds.  Any d >= 1 (ld_src, ld_dst >= d): 16-byte accesses where d, both leading dimensions and both pointers allow it,
+ * scalar ones otherwise.  Rows not listed (and listed rows with an empty range) are not touched.  No allocation, no synchronisation;
+ * n_rows == 0 returns HGT_OK without a launch (additive export at ABI 8). */
+int hgt_scatter_add_rows(const float* src, int64_t ld_src, const int32_t* rows, const int32_t* ptr, const int32_t* pos,
+                         int64_t n_rows, int32_t d, float* dst, int64_t ld_dst, void* stream);
 /* The same rows in a 24-bit transport format (sign, 8 exponent, 15 mantissa bits, round to nearest: relative error <= 2^-16;
  * 3*d bytes per row, d % 4 == 0) and its inverse: the multi-GPU exchange is bound by the links, and halo rows only feed the
  * K/V projections. */

@@ -199,9 +199,12 @@ class _Step:
         self.split = layer.precision in _SPLIT
         self.det = takes_det_route(layer)                    # every atomic site of the step takes its `_det` entry point
         self.use_norm = bool(layer.use_norm)
-        self.N, self.E = plan.N, plan.E
+        # N nodes carry K / V; the first NQ of them are the targets (they alone carry Q, an aggregate, an update and an output row).
+        # NQ < N: a rank of a destination partition, whose rows [NQ, N) are source-only halo rows (pyhgt_amd/dist.py)
+        self.N, self.NQ, self.E = plan.N, plan.NQ, plan.E
         self.dev = plan.device
         self.rows = plan.row_lists()
+        self.halo = plan.halo_row_lists() if self.NQ < self.N else None      # (rows, offsets, count): the typed list of rows [NQ, N)
         self._scratch = {}
 
     def new(self, *shape, zero=False, dtype=torch.float32):
@@ -213,7 +216,7 @@ class _Step:
 
     def node_linear(self, x, k, n_out, W, wgs, bias, bgs, out, prologue=0):
         """out = prologue(x) W[type]^T + b[type] over the target rows of a known type (the others stay unwritten)."""
-        _typed_linear(self.split, x, k, self.rows.rows_q, self.rows.off_q, self.T, self.N, k, n_out, W, 0, wgs, bias, 0, bgs, [out], n_out,
+        _typed_linear(self.split, x, k, self.rows.rows_q, self.rows.off_q, self.T, self.NQ, k, n_out, W, 0, wgs, bias, 0, bgs, [out], n_out,
                       prologue=prologue)
 
     # -- relation matrices ------------------------------------------------------------------------------------
@@ -313,7 +316,7 @@ class _Step:
     def node_update_bwd(self, *args):
         """hgt_node_update_bwd_ex(*args, stream), or its atomic-free form (one partial per wavefront's row range, summed in range order)."""
         if self.det:
-            wp, wb, keep = _det_ws(self.dev, "hgt_node_update_bwd_det", self.N, self.dout, self.T)
+            wp, wb, keep = _det_ws(self.dev, "hgt_node_update_bwd_det", self.NQ, self.dout, self.T)
             check(self.lib.hgt_node_update_bwd_det(*args, wp, wb, _stream()), "hgt_node_update_bwd_det")
         else:
             check(self.lib.hgt_node_update_bwd_ex(*args, _stream()), "hgt_node_update_bwd_ex")
@@ -324,12 +327,27 @@ class _Step:
         return att_t, msg_p, self.frags(msg_p)
 
     def project(self, x, p):
-        """Q|K|V once per node (conv.py:96-97,103)."""
-        dp, din = self.dp, self.din
-        qkv = self.new(3, self.N, dp)
-        _typed_linear(self.split, x, din, self.rows.rows_all, self.rows.off_all, self.T, self.N, din, 3 * dp, p.w_qkv, 0, 3 * dp * din,
-                      p.b_qkv, 0, 3 * dp, [qkv[0], qkv[1], qkv[2]], dp)
+        """Q|K|V once per node (conv.py:96-97,103), as one array [Q: NQ rows; K: N rows; V: N rows] (qkv_views).  Source-only rows
+        get K|V alone: the 2 dp weight rows behind Q's, over the typed list of the rows [NQ, N)."""
+        dp, din, N, NQ = self.dp, self.din, self.N, self.NQ
+        qkv = self.new(NQ + 2 * N, dp)
+        Q, K, V = self.qkv_views(qkv)
+        if NQ == N:
+            _typed_linear(self.split, x, din, self.rows.rows_all, self.rows.off_all, self.T, N, din, 3 * dp, p.w_qkv, 0, 3 * dp * din,
+                          p.b_qkv, 0, 3 * dp, [Q, K, V], dp)
+            return qkv
+        _typed_linear(self.split, x, din, self.rows.rows_q, self.rows.off_q, self.T, NQ, din, 3 * dp, p.w_qkv, 0, 3 * dp * din,
+                      p.b_qkv, 0, 3 * dp, [Q, K, V], dp)
+        h_rows, h_off, n_h = self.halo
+        if n_h:
+            _typed_linear(self.split, x, din, h_rows.data_ptr(), h_off.data_ptr(), self.T, n_h, din, 2 * dp, p.w_qkv, dp * din, 3 * dp * din,
+                          p.b_qkv, dp, 3 * dp, [K, V], dp)
         return qkv
+
+    def qkv_views(self, qkv):
+        """(Q [NQ, dp], K [N, dp], V [N, dp]) of project's array."""
+        N, NQ = self.N, self.NQ
+        return qkv[:NQ], qkv[NQ:NQ + N], qkv[NQ + N:]
 
     def temporal_tables(self, p):
         """(rte_k, rte_v): K / V images of the 240 temporal rows per source type (conv.py:91-92,298-299 hoisted off the edges)."""
@@ -352,13 +370,13 @@ class _Step:
 
     def aggregate(self, att, V, rte_v, msg_p, msg_f):
         """agg = sum_r (sum_e att_e v_e) M_r (conv.py:104,109-111 + scatter-add)."""
-        agg = self.new(self.N, self.dp)
-        self.spmm(self.plan, att, V.data_ptr(), rte_v, msg_p, msg_f, agg, 0, self.dp, self.N)
+        agg = self.new(self.NQ, self.dp)
+        self.spmm(self.plan, att, V.data_ptr(), rte_v, msg_p, msg_f, agg, 0, self.dp, self.NQ)
         return agg
 
     def a_linear(self, agg, p, mask, gelu):
         """drop(a_linear(gelu(agg))) (HGTConv, conv.py:119-125) or drop(a_linear(agg)) (DenseHGTConv, conv.py:259-261)."""
-        trans = self.new(self.N, self.dout)
+        trans = self.new(self.NQ, self.dout)
         self.node_linear(agg, self.dp, self.dout, p.w_a, self.dout * self.dp, p.b_a, self.dout, trans, prologue=int(gelu))
         self.drop_(trans, mask)
         return trans
@@ -366,14 +384,14 @@ class _Step:
     def update_hgt(self, p, x, agg, m1, m2):
         """HGTConv (conv.py:119-133): a_linear(gelu(agg)) -> dropout -> gated skip -> LayerNorm.  Returns (out, what the backward keeps)."""
         trans = self.a_linear(agg, p, m1, gelu=True)
-        out = self.new(self.N, self.dout)
+        out = self.new(self.NQ, self.dout)
         check(self.lib.hgt_node_update(_ptr(trans), _ptr(x), self.din, _ptr(self.plan.node_type), _ptr(p.skip), _ptr(p.ln_w), _ptr(p.ln_b),
-                                       int(self.use_norm), self.N, self.dout, self.T, _ptr(out), _stream()), "hgt_node_update")
+                                       int(self.use_norm), self.NQ, self.dout, self.T, _ptr(out), _stream()), "hgt_node_update")
         return out, dict(trans=trans)
 
     def update_dense(self, p, x, agg, m1, m2):
         """DenseHGTConv (conv.py:250-274): y1 = LN_t(drop(a_linear(agg)) + x); out = out_norm(drop(out_linear(gelu(mid_linear(y1)))) + y1)."""
-        lib, N, T, dout, nt = self.lib, self.N, self.T, self.dout, _ptr(self.plan.node_type)
+        lib, N, T, dout, nt = self.lib, self.NQ, self.T, self.dout, _ptr(self.plan.node_type)      # N: the targets
         trans = self.a_linear(agg, p, m1, gelu=False)
         y1 = self.new(N, dout)
         check(lib.hgt_node_update_ex(_ptr(trans), _ptr(x), self.din, nt, None, _ptr(p.ln_w), _ptr(p.ln_b), int(self.use_norm), 0, N, dout, T,
@@ -394,7 +412,7 @@ class _Step:
     # == backward steps ======================================================================================================
     def a_linear_bwd(self, s, d_trans, gelu):
         """trans = a_linear(f(agg)), f = gelu or identity: (d agg, d w_a, d b_a)."""
-        N, dp, dout = self.N, self.dp, self.dout
+        N, dp, dout = self.NQ, self.dp, self.dout      # N: the targets
         a_in = torch.nn.functional.gelu(s.agg) if gelu else s.agg                  # exact erf form, conv.py:119
         d_w_a, d_b_a = _wgrad(self.split, d_trans, dout, a_in, dp, self.rows.rows_q, self.rows.off_q, self.T, N, dout, dp, det=self.det)
         del a_in
@@ -412,7 +430,7 @@ class _Step:
 
     def update_hgt_bwd(self, s, gout):
         """update_hgt in reverse (conv.py:125-133): (d agg, the skip branch of dx, gradients by slot name)."""
-        N, T, din, dout = self.N, self.T, self.din, self.dout
+        N, T, din, dout = self.NQ, self.T, self.din, self.dout      # N: the targets
         d_lnw, d_lnb = self._ln_grads()
         d_trans, dx_skip = self.new(N, dout), self.new(N, din)
         d_alpha = self.new(T, zero=True)
@@ -431,7 +449,7 @@ class _Step:
 
     def update_dense_bwd(self, s, gout):
         """update_dense in reverse (conv.py:250-274): (d agg, the residual branch of dx, gradients by slot name)."""
-        lib, N, T, din, dout, nt = self.lib, self.N, self.T, self.din, self.dout, _ptr(self.plan.node_type)
+        lib, N, T, din, dout, nt = self.lib, self.NQ, self.T, self.din, self.dout, _ptr(self.plan.node_type)      # N: the targets
         rows_q, off2 = self.rows.rows_q, s.off2.data_ptr()
         d_lnw, d_lnb = self._ln_grads()
         d_trans, dx_skip = self.new(N, dout), self.new(N, din)
@@ -464,10 +482,10 @@ class _Step:
     def attention_bwd(self, s, dagg):
         """d s, the gradient of the logits in plan order (conv.py:98-111): d att = <dagg_i M^T, v_e>, rho = <dagg, agg> per head, then the
         softmax backward."""
-        plan, N, E, H = self.plan, self.N, self.E, self.H
+        plan, N, E, H = self.plan, self.NQ, self.E, self.H      # N: the targets
         ones_pri = torch.full((self.R, self.Hreal), math.sqrt(self.dk), dtype=torch.float32, device=self.dev)      # pri / sqrt(dk) == 1
         m_t, _ = self.pack(s.rmsg, s.rmsg, ones_pri)                                  # m_t[r,h,c,k] = M[r,h,k,c]
-        d_att = self.logits(plan, dagg, s.qkv[2], s.rte_v, m_t)
+        d_att = self.logits(plan, dagg, self.qkv_views(s.qkv)[2], s.rte_v, m_t)
         rho = self.new(N, H)
         check(self.lib.hgt_head_dot(_ptr(dagg), _ptr(s.agg), N, H, self.dkp, _ptr(rho), _stream()), "hgt_head_dot")
         ds = self.new(E, H)
@@ -479,13 +497,13 @@ class _Step:
         """dqkv [N, 3 dp] by three gather passes: dQ over the plan, dK and dV over the transposed plan.  Also returns the
         (matrices, fragments) of the dK and of the dV pass, which temporal_bwd runs again grouped by table row."""
         plan, dp, N = self.plan, self.dp, self.N
-        Q, K = s.qkv[0], s.qkv[1]
+        Q, K, _ = self.qkv_views(s.qkv)
         a_s = s.ratt * scale                                                         # A[k][c] * pri / sqrt(dk)
         dqkv = self.new(N, 3 * dp, zero=True)
         # dQ_i = sum_r (sum_e ds_e k_e) . (A s)           [out = in . F, F[k][c] = A[k][c] s]
         _, f_q = self.pack(s.ratt, a_s, s.rpri)
-        self.spmm(plan, ds, K.data_ptr(), s.rte_k, f_q, self.frags(f_q), dqkv, 0, 3 * dp, N)
-        # transposed graph: dK_j = sum_r (sum_e ds_e q_i) . (A s)^T,  dV_j = sum_r (sum_e att_e dagg_i) . M^T
+        self.spmm(plan, ds, K.data_ptr(), s.rte_k, f_q, self.frags(f_q), dqkv, 0, 3 * dp, self.NQ)
+        # transposed graph (every node a target, the sources are the original targets: Q and dagg have NQ rows): dK_j = sum_r (sum_e ds_e q_i) . (A s)^T,  dV_j = sum_r (sum_e att_e dagg_i) . M^T
         plan_t = plan.transposed()
         ds_t = self.to_sorted(plan_t, self.to_edge_ids(plan, ds))
         att_tr = self.to_sorted(plan_t, self.to_edge_ids(plan, s.att))
@@ -500,8 +518,9 @@ class _Step:
     def relation_bwd(self, s, dagg, ds, scale):
         """Gradients of relation_msg / relation_att / relation_pri: two outer products over the edges + the pri / att chain rule."""
         plan, Hr, dk = self.plan, self.Hreal, self.dk
-        d_msg = self.outer(plan, s.att, s.qkv[2], s.rte_v, dagg)[:, :Hr, :dk, :dk]      # d relation_msg[r,h,k,c]
-        o_att = self.outer(plan, ds, s.qkv[1], s.rte_k, s.qkv[0])[:, :Hr, :dk, :dk]     # sum ds_e k_e[k] q_i[c]
+        Q, K, V = self.qkv_views(s.qkv)
+        d_msg = self.outer(plan, s.att, V, s.rte_v, dagg)[:, :Hr, :dk, :dk]      # d relation_msg[r,h,k,c]
+        o_att = self.outer(plan, ds, K, s.rte_k, Q)[:, :Hr, :dk, :dk]     # sum ds_e k_e[k] q_i[c]
         return dict(rmsg=d_msg.contiguous(), ratt=o_att * scale, rpri=(o_att * s.ratt).sum(dim=(2, 3)) / math.sqrt(dk))
 
     def temporal_bwd(self, s, dagg, ds, f_k, f_v):
@@ -514,7 +533,7 @@ class _Step:
         att_r = self.to_sorted(plan_r, self.to_edge_ids(plan, s.att))
         d_tab = self.new(tab, 2 * dp, zero=True)
         # sources of plan_r are the original TARGETS, shifted by `tab` ids: the row pointer is shifted back
-        self.spmm(plan_r, ds_r, s.qkv[0].data_ptr() - 4 * tab * dp, None, *f_k, d_tab, 0, 2 * dp, tab)
+        self.spmm(plan_r, ds_r, self.qkv_views(s.qkv)[0].data_ptr() - 4 * tab * dp, None, *f_k, d_tab, 0, 2 * dp, tab)
         self.spmm(plan_r, att_r, dagg.data_ptr() - 4 * tab * dp, None, *f_v, d_tab, dp, 2 * dp, tab)
         if self.det:
             return self.temporal_chain_det(s, d_tab)
@@ -553,7 +572,9 @@ class _Step:
 
     def project_bwd(self, s, dqkv, dx_skip, d_w_kv_tables, want_dx):
         """project in reverse (conv.py:96-97,103): d w_qkv, d b_qkv and, if asked for, dx (+ the skip / residual branch)."""
-        T, N, dp, din, rows = self.T, self.N, self.dp, self.din, self.rows
+        T, N, NQ, dp, din, rows = self.T, self.N, self.NQ, self.dp, self.din, self.rows
+        if NQ < N:
+            return self.project_bwd_rect(s, dqkv, dx_skip, d_w_kv_tables, want_dx)
         d_w_qkv, d_b_qkv = _wgrad(self.split, dqkv, 3 * dp, s.x, din, rows.rows_all, rows.off_all, T, N, 3 * dp, din, det=self.det)
         if d_w_kv_tables is not None:
             d_w_qkv[:, dp:3 * dp, :] += d_w_kv_tables
@@ -563,6 +584,32 @@ class _Step:
             dx = self.new(N, din, zero=True)
             _typed_linear(self.split, dqkv, 3 * dp, rows.rows_all, rows.off_all, T, N, 3 * dp, din, w_qkv_t, 0, din * 3 * dp, None, 0, 0, [dx], din)
             dx += dx_skip
+            grads["x"] = dx
+        return grads
+
+    def project_bwd_rect(self, s, dqkv, dx_skip, d_w_kv_tables, want_dx):
+        """project_bwd with source-only rows: the targets' GEMMs read all 3 dp columns of dqkv, those of the rows [NQ, N) its K|V
+        block alone (their Q block is zero), and the skip / residual branch exists on the targets only."""
+        T, N, NQ, dp, din, rows = self.T, self.N, self.NQ, self.dp, self.din, self.rows
+        h_rows, h_off, n_h = self.halo
+        d_kv = dqkv[:, dp:]                                                          # [N, 2dp] view, leading dimension 3dp
+        d_w_qkv, d_b_qkv = _wgrad(self.split, dqkv, 3 * dp, s.x, din, rows.rows_q, rows.off_q, T, NQ, 3 * dp, din, det=self.det)
+        if n_h:
+            d_w_h, d_b_h = _wgrad(self.split, d_kv, 3 * dp, s.x, din, h_rows.data_ptr(), h_off.data_ptr(), T, n_h, 2 * dp, din, det=self.det)
+            d_w_qkv[:, dp:3 * dp, :] += d_w_h
+            d_b_qkv[:, dp:3 * dp] += d_b_h
+        if d_w_kv_tables is not None:
+            d_w_qkv[:, dp:3 * dp, :] += d_w_kv_tables
+        grads = dict(w_qkv=d_w_qkv, b_qkv=d_b_qkv)
+        if want_dx:
+            dx = self.new(N, din, zero=True)
+            w_qkv_t = s.w_qkv.transpose(1, 2).contiguous()                           # [T][din][3dp]
+            _typed_linear(self.split, dqkv, 3 * dp, rows.rows_q, rows.off_q, T, NQ, 3 * dp, din, w_qkv_t, 0, din * 3 * dp, None, 0, 0, [dx], din)
+            if n_h:
+                w_kv_t = s.w_qkv[:, dp:3 * dp, :].transpose(1, 2).contiguous()       # [T][din][2dp]
+                _typed_linear(self.split, d_kv, 3 * dp, h_rows.data_ptr(), h_off.data_ptr(), T, n_h, 2 * dp, din, w_kv_t, 0, din * 2 * dp,
+                              None, 0, 0, [dx], din)
+            dx[:NQ] += dx_skip
             grads["x"] = dx
         return grads
 
@@ -581,8 +628,9 @@ class _HGTConvTrain(torch.autograd.Function):
         att_t, msg_p, msg_f = step.relation_images(p)
         qkv = step.project(x, p)
         rte_k, rte_v = step.temporal_tables(p) if layer.use_RTE else (None, None)
-        att, layer.att = step.attention(qkv[0], qkv[1], rte_k, att_t)
-        agg = step.aggregate(att, qkv[2], rte_v, msg_p, msg_f)
+        Q, K, V = step.qkv_views(qkv)
+        att, layer.att = step.attention(Q, K, rte_k, att_t)
+        agg = step.aggregate(att, V, rte_v, msg_p, msg_f)
         m1, m2 = drop_masks if drop_masks is not None else (None, None)
         out, kept = (step.update_dense if dense else step.update_hgt)(p, x, agg, m1, m2)
         ctx.layer, ctx.plan, ctx.lay, ctx.dense = layer, plan, step.lay, dense
@@ -611,20 +659,25 @@ class _HGTConvTrain(torch.autograd.Function):
 
 def hgt_conv_train(layer, plan, x, packed, drop_p):
     """Training-mode forward of `layer` (HGTConv or DenseHGTConv) through the autograd Function.  `packed` =
-    layer._pack_parameters(grad=True); drop_p = dropout probability of conv.py:125 / 261,273 (0 in eval mode)."""
-    if plan.NQ != plan.N:
-        raise NotImplementedError("pyhgt_amd: the backward pass covers single-GPU graphs (n_q_rows == n_nodes)")
+    layer._pack_parameters(grad=True); drop_p = dropout probability of conv.py:125 / 261,273 (0 in eval mode).
+    plan.NQ < plan.N: nodes [0, NQ) are targets, nodes [NQ, N) source-only rows (a rank of a destination partition): the output is
+    [NQ, out_dim], x.grad [N, in_dim] with the K / V paths alone on the rows [NQ, N)."""
+    if not 0 <= plan.NQ <= plan.N:
+        raise ValueError("pyhgt_amd: the plan's n_q_rows must lie in [0, n_nodes]")
     ok, reason = training_supported(layer.out_dim, layer.n_heads)
     if not ok:      # said HERE instead of failing inside loss.backward()
         raise NotImplementedError("pyhgt_amd: " + reason)
+    if plan.NQ == 0 and plan.N > 0:
+        # (the edge kernels read n_q_rows = 0 as "all rows"; a step without targets has no output and no gradient anyway)
+        raise ValueError("pyhgt_amd: a training step needs at least one target row (n_q_rows == 0 of %d nodes)" % plan.N)
     dense = "mid_w" in packed
     masks = None
     if drop_p > 0.0:
         keep = 1.0 - drop_p
         if keep <= 0.0:      # nn.Dropout(p=1) yields zeros (not 0/0)
-            draw = lambda: torch.zeros((plan.N, layer.out_dim), dtype=torch.float32, device=x.device)
+            draw = lambda: torch.zeros((plan.NQ, layer.out_dim), dtype=torch.float32, device=x.device)
         else:
-            draw = lambda: torch.bernoulli(torch.full((plan.N, layer.out_dim), keep, dtype=torch.float32, device=x.device)) / keep
+            draw = lambda: torch.bernoulli(torch.full((plan.NQ, layer.out_dim), keep, dtype=torch.float32, device=x.device)) / keep
         masks = (draw(), draw() if dense else None)          # DenseHGTConv drops twice (conv.py:261 and conv.py:273)
     inputs = dict(packed, x=x)
     assert all(k in TENSOR_SLOTS for k, t in inputs.items() if torch.is_tensor(t)), "a packed parameter without a slot in TENSOR_SLOTS"

@@ -262,6 +262,24 @@ class GraphPlan:
         _lib.check(_lib.load().hgt_plan_row_lists(self.ptr, self.N, self.E, self.T, self.R, C.byref(pr)), "hgt_plan_row_lists")
         return pr
 
+    def halo_row_lists(self):
+        """(rows int32, offsets int32[T+1], count) of the source-only rows [NQ, N) grouped by node type, in the form the typed linears
+        take: the training step projects K|V alone for them (pyhgt_amd/autograd.py).  Rows of a type outside [0, T) are left out (no
+        projection: their edges are unclaimed, conv.py:68-69).  Built on first use with torch ops (one host synchronisation per plan:
+        the count), like HaloPlan.chunk_row_lists, and kept with the plan."""
+        if getattr(self, "_halo_rows", None) is None:
+            T = self.T
+            t = self.node_type[self.NQ:]
+            valid = (t >= 0) & (t < T)
+            key = torch.where(valid, t, torch.full_like(t, T))
+            order = torch.argsort(key, stable=True)
+            off = torch.zeros(T + 1, dtype=torch.int64, device=t.device)
+            off[1:] = torch.cumsum(torch.bincount(key, minlength=T + 1)[:T], 0)
+            n_valid = int(valid.sum())
+            rows = (self.NQ + order[:n_valid]).to(torch.int32).contiguous()
+            self._halo_rows = (rows, off.to(torch.int32).contiguous(), n_valid)
+        return self._halo_rows
+
     def tile_items(self):
         """Host copy (synchronises; once per graph) of the plan's per-tile item table: the logits work items of destination tile
         t are [table[t], table[t + 1]).  Returns (int64 tensor [n_tiles + 1] on the CPU, targets per tile).  pyhgt_amd.dist uses
@@ -588,7 +606,9 @@ class HGTConv(nn.Module):
                 phase_events=None, stage=0, proj=None, workspace=None, slices=None, block=None, out=None, proj_c24=None):
         """node_inp f32[N,in_dim], node_type i64[N], edge_index i64[2,E] (row 0 = source, row 1 =
         target; any strides), edge_type i64[E], edge_time i64[E] (needed iff use_RTE).
-        Returns f32[N,out_dim] (or [n_q_rows,out_dim] when only the first n_q_rows nodes are targets).
+        Returns f32[N,out_dim] (or [n_q_rows,out_dim] when only the first n_q_rows nodes are targets; under grad that is the
+        training step of a rank of a destination partition: node_inp.grad is [N, in_dim], with the K / V paths alone on the
+        source-only rows [n_q_rows, N)).
 
         stage / proj: staged execution for pyhgt_amd.dist (hgt_conv_args.stage): 1 = projections of the own rows,
         2 = K|V of the rows in proj = (rows int32[n], offsets int32[T+1]) (one call per received halo chunk),
@@ -609,9 +629,10 @@ class HGTConv(nn.Module):
             raise RuntimeError("pyhgt_amd.HGTConv runs only on a ROCm GPU tensor; there is no CPU fallback "
                                "(the CPU oracle lives under oracle/ and is test infrastructure)")
         needs_grad = torch.is_grad_enabled() and (node_inp.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if needs_grad and (stage != 0 or n_q_rows is not None):
-            raise RuntimeError("pyhgt_amd: the backward pass covers HGTConv / DenseHGTConv on a single GPU (SURVEY.md section 8f-2); "
-                               "staged multi-GPU forwards run under torch.no_grad() only")
+        if needs_grad and stage != 0:
+            # (n_q_rows under grad at stage 0 is the rectangular training step of a destination partition: pyhgt_amd/autograd.py)
+            raise RuntimeError("pyhgt_amd: the backward pass covers whole-layer calls (stage 0) of HGTConv / DenseHGTConv, with or "
+                               "without n_q_rows (SURVEY.md section 8f-2); staged multi-GPU forwards run under torch.no_grad() only")
         if node_inp.dtype != torch.float32:
             raise TypeError("node_inp must be float32 (the reference layer is fp32-only, conv.py:68-69)")
         if self.in_dim != self.out_dim:
@@ -638,6 +659,8 @@ class HGTConv(nn.Module):
         strict = GraphPlan.STRICT if self.strict is None else self.strict
         plan.raise_if_bad(wait=bool(strict) and plan._bad is None, ignore_time=not self.use_RTE)
         NQ, E = plan.NQ, plan.E
+        if needs_grad and n_q_rows is not None and int(n_q_rows) != NQ:      # (the training step takes its targets from the plan)
+            raise ValueError("n_q_rows=%d, but the plan was built with n_q_rows=%d" % (int(n_q_rows), NQ))
         if needs_grad and not self.training and not HGTConv._warned_eval_grad:
             HGTConv._warned_eval_grad = True
             import warnings

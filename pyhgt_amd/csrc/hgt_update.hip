@@ -84,6 +84,48 @@ __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ x
     }
 }
 
+// Inverse of k_gather_rows with an addition: the gradients of halo rows come home (pyhgt_amd/dist.py, HaloPlan.return_grads).
+// One wavefront per DESTINATION row: rows[] holds distinct ids, so no two wavefronts write one row -- no atomics, and the sum of a row
+// is dst + src[pos[p0]] + src[pos[p0 + 1]] + ... added one after the other in list order: the bits are fixed by the lists.
+// Streaming: every byte is touched once (a 1 KB row = one 16-byte load per lane); what hides the latency is rows in flight, so the
+// loads of up to four contributing rows are issued before the first add, and 4-wavefront workgroups leave the CU full of them.
+// Plain fp32 adds: nothing here can contract to an FMA (there is no multiply).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_scatter_add_rows(const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rows,
+                                                          const int32_t* __restrict__ ptr, const int32_t* __restrict__ pos,
+                                                          int64_t n_rows, int d, float* __restrict__ dst, int64_t ld_dst) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n_rows) return;
+    const int p0 = ptr[i], p1 = ptr[i + 1];
+    if (p1 <= p0) return;      // nothing to add: the row keeps its bits (no load-store round trip)
+    float* __restrict__ o = dst + (int64_t)rows[i] * ld_dst;
+    if (VEC) {
+        for (int c = lane * 4; c < d; c += 256) {
+            float4 acc = *reinterpret_cast<const float4*>(o + c);
+            int p = p0;
+            for (; p + 4 <= p1; p += 4) {
+                float4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(src + (int64_t)pos[p + u] * ld_src + c);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
+            }
+            for (; p < p1; ++p) {
+                const float4 v = *reinterpret_cast<const float4*>(src + (int64_t)pos[p] * ld_src + c);
+                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+            }
+            *reinterpret_cast<float4*>(o + c) = acc;
+        }
+    } else {
+        for (int c = lane; c < d; c += 64) {
+            float acc = o[c];
+            for (int p = p0; p < p1; ++p) acc += src[(int64_t)pos[p] * ld_src + c];
+            o[c] = acc;
+        }
+    }
+}
+
 // 24-bit transport format of halo rows (sign, 8 exponent bits, 15 mantissa bits, round to nearest; relative error <= 2^-16):
 // 4 floats -> 3 dwords.  The multi-GPU exchange is bound by the xGMI links, so a quarter fewer bytes is a quarter less time;
 // halo rows only feed the K/V projections, whose split-bf16 operands carry 16 mantissa bits anyway.
@@ -270,6 +312,19 @@ extern "C" int hgt_gather_rows(const float* x, int64_t ldx, const int32_t* idx, 
     if (n == 0) return HGT_OK;
     if (!x || !idx || !out || d <= 0 || n < 0) return HGT_ERR_INVALID_ARG;
     k_gather_rows<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, ldx, idx, n, d, out);
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+extern "C" int hgt_scatter_add_rows(const float* src, int64_t ld_src, const int32_t* rows, const int32_t* ptr, const int32_t* pos,
+                                    int64_t n_rows, int32_t d, float* dst, int64_t ld_dst, void* stream) {
+    if (n_rows == 0) return HGT_OK;
+    if (!src || !rows || !ptr || !pos || !dst || d <= 0 || n_rows < 0 || ld_src < d || ld_dst < d) return HGT_ERR_INVALID_ARG;
+    if (n_rows > (int64_t)4 * 0x7fffffff) return HGT_ERR_INVALID_ARG;
+    const bool vec = (d & 3) == 0 && (ld_src & 3) == 0 && (ld_dst & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+    const unsigned grid = (unsigned)((n_rows + 3) / 4);
+    if (vec) k_scatter_add_rows<true><<<grid, 256, 0, (hipStream_t)stream>>>(src, ld_src, rows, ptr, pos, n_rows, d, dst, ld_dst);
+    else k_scatter_add_rows<false><<<grid, 256, 0, (hipStream_t)stream>>>(src, ld_src, rows, ptr, pos, n_rows, d, dst, ld_dst);
     HGT_CHECK_LAUNCH();
     return HGT_OK;
 }

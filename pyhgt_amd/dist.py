@@ -44,6 +44,14 @@ bucket in the workspace.  Kept for layers the blocked schedule does not cover an
 
 "pipelined" (round 1): the exchange overlaps the projections only; the edge phase waits for the last chunk (stages 1/2/3).  The
 fallback for every layer (exact fp32 precision, DenseHGTConv, rows wider than 256 columns).
+
+Training (PartitionedGraph.forward under grad; one schedule in every mode).  The exchange is an autograd Function
+(HaloExchangeFunction) in front of the layer's rectangular training step (autograd.py: targets [0, n_own), source-only rows behind
+them).  The step's x.grad has n_local rows; its halo part belongs to rows other ranks own and returns along the SAME all-to-alls
+with send and receive splits swapped (HaloPlan.return_grads: the halo rows already lie in wire order, nothing is packed).  A row
+several peers hold receives several contributions: hgt_scatter_add_rows adds them into the owner's dx, one wavefront per
+destination row, in (chunk, peer) order -- no float atomics, so a rank's gradients stay bit-reproducible under deterministic=True.
+all_reduce_grads sums the parameter gradients over the ranks.
 """
 import torch
 import torch.distributed as dist
@@ -336,8 +344,9 @@ class HaloPlan:
         return torch.where(claimed, self.edge_buckets() * num_relations + edge_type,
                            torch.full_like(edge_type, (self.n_chunks + 1) * num_relations))
 
-    def _transfer(self, recv, send, c, async_op):
-        """The all-to-all of chunk c (or, emulating, a device copy of as many bytes)."""
+    def _transfer(self, recv, send, c, async_op, reverse=False):
+        """The all-to-all of chunk c (or, emulating, a device copy of as many bytes).  reverse: the same collective with send and
+        receive splits swapped -- what a rank received as halo rows goes back to the rows' owners (return_grads)."""
         if getattr(self, "emulate", None) is not None:
             n = min(recv.size(0), send.size(0))
             if n:
@@ -351,7 +360,8 @@ class HaloPlan:
             return _Done() if async_op else None
         if not self.chunk_live[c]:
             return None
-        return _all_to_all(recv, send, list(self.recv_chunk_splits[c]), list(self.send_chunk_splits[c]), self.group, async_op=async_op)
+        splits = (self.recv_chunk_splits[c], self.send_chunk_splits[c])
+        return _all_to_all(recv, send, list(splits[reverse]), list(splits[not reverse]), self.group, async_op=async_op)
 
     def exchange_chunk(self, c, x_own, x_local, pack=None, async_op=False, compress=False, expand=True):
         """One chunk of the exchange: pack the rows of chunk c the peers need, all-to-all them into the halo rows of chunk c.
@@ -422,11 +432,115 @@ class HaloPlan:
         return x_local
 
 
+    # -- the way back: gradients of halo rows return to the rows' owners (training; module docstring) ------------------------------
+    def return_index(self, device=None):
+        """(rows, ptr, pos), int32, built once from send_rows: rows = the distinct own rows any peer holds as a halo row, ascending;
+        pos[ptr[i] : ptr[i + 1]] = the positions of rows[i] in the send list, ascending -- (chunk, peer) order, the FIXED order in
+        which return_grads adds the peers' contributions.  Pure index arithmetic (runs on CPU tensors as well)."""
+        device = self.send_rows.device if device is None else torch.device(device)
+        cache = self.__dict__.setdefault("_return_index", {})
+        hit = cache.get(str(device))
+        if hit is None:
+            sr = self.send_rows.to(torch.int64)
+            pos = torch.argsort(sr, stable=True)                      # by row; positions ascend within a row
+            rows, counts = torch.unique_consecutive(sr[pos], return_counts=True)
+            ptr = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=sr.device)
+            ptr[1:] = torch.cumsum(counts, 0)
+            hit = cache[str(device)] = tuple(t.to(torch.int32).contiguous().to(device) for t in (rows, ptr, pos))
+        return hit
+
+    def return_grads(self, d_local, d_own, reduce=None):
+        """d_own[r] += the gradients the peers hold for my row r.  d_local [n_local, d] is this rank's gradient of its local rows:
+        its halo part already lies in wire order, so chunk c's rows are sent as they are through the forward's all-to-all with
+        send and receive splits swapped (issued back to back, like the forward's), into a persistent [len(send_rows), d] buffer
+        whose row i belongs to own row send_rows[i]; then ONE hgt_scatter_add_rows call adds the buffer's rows into d_own in the
+        order of return_index -- no atomics, the same bits every time.  `reduce(recv, rows, ptr, pos, d_own)` replaces the kernel
+        (CPU tensors, as pack= does for the forward).  Returns d_own."""
+        if d_local.dim() != 2 or d_local.size(0) != self.n_local or d_own.size(0) != self.n_own or d_own.size(1) != d_local.size(1):
+            raise ValueError("return_grads takes d_local [n_local, d] and d_own [n_own, d]")
+        if reduce is None and not d_local.is_cuda:
+            raise RuntimeError("pyhgt_amd.dist: the halo gradients are added by the HIP kernel hgt_scatter_add_rows; CPU tensors need "
+                               "an explicit reduce fn")
+        d_local = d_local.contiguous()
+        d = d_local.size(1)
+        key = ("ret", d, str(d_local.device), d_local.dtype)
+        bufs = self.__dict__.setdefault("_bufs", {})
+        recv = bufs.get(key)
+        if recv is None:
+            recv = bufs[key] = torch.empty(self.send_rows.numel(), d, dtype=d_local.dtype, device=d_local.device)
+        pending = []
+        for c in range(self.n_chunks):
+            send = d_local[self.n_own + self.recv_chunk_off[c]:self.n_own + self.recv_chunk_off[c + 1]]
+            work = self._transfer(recv[self.send_chunk_off[c]:self.send_chunk_off[c + 1]], send, c, True, reverse=True)
+            if work is not None:
+                pending.append(work)
+        for work in pending:
+            work.wait()
+        rows, ptr, pos = self.return_index(d_own.device)
+        if reduce is not None:
+            reduce(recv, rows, ptr, pos, d_own)
+        elif rows.numel():
+            if d_own.dtype != torch.float32 or recv.dtype != torch.float32 or d_own.stride(1) != 1:
+                raise TypeError("return_grads adds float32 rows")
+            _lib.check(_lib.load().hgt_scatter_add_rows(recv.data_ptr(), recv.stride(0), rows.data_ptr(), ptr.data_ptr(), pos.data_ptr(),
+                                                        rows.numel(), d, d_own.data_ptr(), d_own.stride(0),
+                                                        torch.cuda.current_stream().cuda_stream), "hgt_scatter_add_rows")
+        return d_own
+
+
+class HaloExchangeFunction(torch.autograd.Function):
+    """x_own [n_own, d] -> x_local [n_local, d] = [own rows ; halo rows] through the chunked exchange (fp32 rows), differentiable:
+    the backward is d_own = d_local[:n_own] plus what HaloPlan.return_grads brings home from the ranks that hold my rows.
+    pack / reduce: the CPU stand-ins of the two HIP kernels (HaloPlan.exchange, HaloPlan.return_grads)."""
+
+    @staticmethod
+    def forward(ctx, halo, x_own, pack=None, reduce=None):
+        x_own = x_own.contiguous()
+        x_local = x_own.new_empty(halo.n_local, x_own.size(1))
+        x_local[:halo.n_own].copy_(x_own)
+        halo.exchange(x_local[:halo.n_own], x_local, pack=pack)
+        ctx.halo, ctx.reduce = halo, reduce
+        return x_local
+
+    @staticmethod
+    def backward(ctx, d_local):
+        halo = ctx.halo
+        d_local = d_local.contiguous()
+        d_own = d_local[:halo.n_own].clone()
+        halo.return_grads(d_local, d_own, reduce=ctx.reduce)
+        return None, d_own, None, None
+
+
+def all_reduce_grads(module, group=None):
+    """Sum every parameter's .grad over the ranks: one flat buffer, one all_reduce (host-staged under gloo).  A parameter without a
+    gradient on this rank counts as zero (a rank without targets, or without rows of a type); afterwards every parameter that
+    requires grad holds the sum.  The order in which the collective library adds the ranks' buffers is its own business."""
+    params = [p for p in module.parameters() if p.requires_grad]
+    if not params:
+        return
+    flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+    if _host_staged(flat, group):
+        host = flat.cpu()
+        dist.all_reduce(host, group=group)
+        flat.copy_(host)
+    else:
+        dist.all_reduce(flat, group=group)
+    off = 0
+    for p in params:
+        g = flat[off:off + p.numel()].view_as(p).to(p.dtype)
+        off += p.numel()
+        if p.grad is None:
+            p.grad = g.clone()
+        else:
+            p.grad.copy_(g)
+
+
 MODES = ("blocked", "bucketed", "pipelined")
 
 
 class PartitionedGraph:
     """One rank's share of a destination-partitioned typed graph + the per-layer forward (module docstring: schedules)."""
+    _warned_compress = False
 
     def __init__(self, node_type_own, src_global, dst_local, edge_type, edge_time, num_types, num_relations,
                  nodes_per_rank, rank, world, group=None, node_offsets=None, n_chunks=None, halo=None, compress=False, bucketed=None,
@@ -444,6 +558,7 @@ class PartitionedGraph:
         if node_offsets is None:
             node_offsets = [nodes_per_rank * r for r in range(world + 1)]
         n_own = int(node_offsets[rank + 1]) - int(node_offsets[rank])
+        self.node_offsets = [int(o) for o in node_offsets]
         if n_chunks is None:
             n_chunks = 8 if mode == "blocked" else 4
         self.mode = mode
@@ -535,7 +650,31 @@ class PartitionedGraph:
             return "bucketed"
         return "pipelined"
 
+    def forward_train(self, layer, x_own):
+        """The differentiable step (forward() under grad): the exchange as an autograd Function, then the layer's rectangular
+        training step on [own rows ; halo rows].  One schedule in every mode -- nothing overlaps the exchange here -- and fp32 rows
+        on the links (compress=True says so once).  Every rank must own targets: a rank without any has no step to differentiate,
+        and its backward would not enter the collectives the others enter.  The check reads the partition's offsets, which all
+        ranks share, so EVERY rank raises, before anything is in flight."""
+        empty = [r for r in range(len(self.node_offsets) - 1) if self.node_offsets[r + 1] <= self.node_offsets[r]]
+        if empty:
+            raise RuntimeError("pyhgt_amd.dist: training needs targets on every rank, but rank(s) %s own none (node_offsets %s); "
+                               "partition over fewer ranks" % (empty, self.node_offsets))
+        if self.compress and not PartitionedGraph._warned_compress:
+            PartitionedGraph._warned_compress = True
+            import warnings
+            warnings.warn("pyhgt_amd.dist: compress=True applies to inference; under grad the halo rows (and their gradients) travel "
+                          "as fp32 rows", stacklevel=3)
+        x_local = HaloExchangeFunction.apply(self.halo, x_own.float())
+        return layer(x_local, self.node_type_local, self.edge_index, self.edge_type, self.edge_time, plan=self.plan, n_q_rows=self.n_own)
+
     def forward(self, layer, x_own, phase_events=None):
+        """One layer on this rank's targets: [n_own, out_dim].  Under grad (x_own or a parameter of the layer requires it) the
+        differentiable step runs (forward_train): layers chain through autograd, the output of one call is the x_own of the next."""
+        if torch.is_grad_enabled() and (x_own.requires_grad or any(p.requires_grad for p in layer.parameters())):
+            if phase_events is not None:
+                raise ValueError("phase_events instrument the inference schedules; the training step records none")
+            return self.forward_train(layer, x_own)
         d = x_own.size(1)
         mode = self.layer_mode(layer)
         bucketed = (mode == "bucketed")

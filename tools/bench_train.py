@@ -2,7 +2,10 @@
 """Training-step timing of one HGTConv at BASELINE.json configs[1]: forward + backward through
 pyhgt_amd/autograd.py against the inference forward, plan (and transposed plan) cached.  Sizes from the environment: HGT_TRAIN_N,
 HGT_TRAIN_E (nodes, edges), HGT_TRAIN_D, HGT_TRAIN_H (width, heads); HGT_TRAIN_NO_SMALL=1 skips the sampled-batch part.
---deterministic (or HGT_TRAIN_DETERMINISTIC=1) times the bit-reproducible mode (deterministic=True on every module)."""
+--deterministic (or HGT_TRAIN_DETERMINISTIC=1) times the bit-reproducible mode (deterministic=True on every module).
+--emulate-world W [--out FILE]: instead, the training step of ONE rank of a W-rank destination partition on one GPU, the recipe of
+bench.py --emulate-world (exact receive side, mirrored send side, the all-to-alls replaced by device copies of as many bytes):
+forward, backward and, inside the backward, the return of the halo gradients, of one layer; the JSON line is appended to FILE."""
 import json
 import os
 import sys
@@ -89,8 +92,74 @@ def sampled_batches(dev):
     return res
 
 
+def emulated_rank_step(dev, W, out_path=None, iters=5):
+    """One layer's training step of rank 0 of W (sizes of BASELINE.json configs[3] per rank, like bench.py --emulate-world): medians
+    of `iters` steps from events on the compute stream.  return_ms is HaloPlan.return_grads inside the backward (the reverse
+    transfers, emulated by device copies, + hgt_scatter_add_rows); link time is not part of any figure."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from pyhgt_amd.dist import HaloPlan, PartitionedGraph, target_blocks
+    Nl, El, d, T, R, H, blocks = (int(os.environ.get("HGT_TRAIN_N", 1000000)), int(os.environ.get("HGT_TRAIN_E", 10000000)),
+                                  int(os.environ.get("HGT_TRAIN_D", 256)), 4, 8, int(os.environ.get("HGT_TRAIN_H", 8)), 8)
+    share, nt_g = bench.configs3_share(dev, W, 0, Nl, El, T, R, False, 0.0, 0.0, keep_global_types=True)
+    n_own = int(share["node_type_own"].numel())
+    bounds = target_blocks(share["dst_local"], n_own, blocks)
+    eblock = torch.searchsorted(torch.tensor(bounds[1:], device=dev), share["dst_local"], right=True).clamp(max=blocks - 1)
+    hp = HaloPlan(share["node_type_own"], share["src_global"], share["node_offsets"], 0, W, n_chunks=blocks, edge_block=eblock,
+                  emulate={"node_type_global": nt_g})
+    del nt_g, eblock
+    pg = PartitionedGraph(None, None, share["dst_local"], share["edge_type"], None, T, R, Nl, 0, W, node_offsets=share["node_offsets"],
+                          halo=hp, mode="blocked", n_chunks=blocks)
+    torch.manual_seed(0)
+    layer = HGTConv(d, d, T, R, H, 0.2, True, False, precision="bf16x3", deterministic=DETERMINISTIC).to(dev).train()
+    x_own = torch.randn(n_own, d, device=dev, generator=torch.Generator(device=dev).manual_seed(7)).requires_grad_(True)
+    g = torch.randn(n_own, d, device=dev)
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    marks = {}
+    real_return = hp.return_grads
+
+    def timed_return(*a, **k):      # events around the return path, on the stream the backward runs on
+        marks["r0"], marks["r1"] = ev(), ev()
+        marks["r0"].record()
+        out = real_return(*a, **k)
+        marks["r1"].record()
+        return out
+    hp.return_grads = timed_return
+    rows = []
+    for it in range(2 + iters):
+        e0, e1, e2 = ev(), ev(), ev()
+        e0.record()
+        out = pg.forward(layer, x_own)
+        e1.record()
+        out.backward(g)
+        e2.record()
+        torch.cuda.synchronize()
+        if it >= 2:
+            rows.append((e0.elapsed_time(e1), e1.elapsed_time(e2), marks["r0"].elapsed_time(marks["r1"])))
+        layer.zero_grad(set_to_none=True)
+        x_own.grad = None
+    med = lambda i: sorted(r[i] for r in rows)[len(rows) // 2]
+    res = {"emulated_world": W, "rank": 0, "own_rows": n_own, "halo_rows": int(hp.n_halo), "returned_rows": int(hp.send_rows.numel()),
+           "edges": int(share["dst_local"].numel()), "d": d, "H": H, "precision": "bf16x3", "deterministic": DETERMINISTIC,
+           "training_forward_ms": round(med(0), 3), "backward_ms": round(med(1), 3), "return_ms": round(med(2), 3),
+           "steps": iters, "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+           "note": "forward = exchange (device copies) + rectangular step; backward includes return_ms = reverse transfers (device "
+                   "copies) + hgt_scatter_add_rows; medians of events on the compute stream"}
+    line = json.dumps(res)
+    print(line)
+    if out_path:
+        with open(out_path, "a") as f:
+            f.write(line + "\n")
+    return res
+
+
 def main():
     dev = "cuda:0"
+    if "--emulate-world" in sys.argv:
+        W = int(sys.argv[sys.argv.index("--emulate-world") + 1])
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+        emulated_rank_step(dev, W, out)
+        return
     # HGT_TRAIN_D / HGT_TRAIN_H: layer width and head count (defaults: configs[1]; 768 / 8 and 1024 / 8 are the wide-head layouts)
     N, E, d, T, R, H = (int(os.environ.get("HGT_TRAIN_N", 1000000)), int(os.environ.get("HGT_TRAIN_E", 10000000)),
                         int(os.environ.get("HGT_TRAIN_D", 256)), 4, 8, int(os.environ.get("HGT_TRAIN_H", 8)))
