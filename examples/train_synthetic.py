@@ -20,7 +20,7 @@ from pyhgt_amd.sampled import synthetic_sampled_batch, to_device_graph  # noqa: 
 
 
 def run(schema="mag", steps=30, conv="hgt", n_hid=128, n_heads=8, n_layers=2, n_classes=16, batch_size=128, lr=2e-3, seed=0,
-        device="cuda:0", verbose=True, deterministic=False):
+        device="cuda:0", verbose=True, deterministic=False, recompute=False):
     torch.manual_seed(seed)      # (already seeds the parameters and the dropout masks; deterministic=True makes the gradients repeat too)
     feat_dim = 129 if schema == "mag" else 256
     batches = []
@@ -35,6 +35,9 @@ def run(schema="mag", steps=30, conv="hgt", n_hid=128, n_heads=8, n_layers=2, n_
     T, R = len(batches[0][0][5]), len(batches[0][0][6])
     gnn = GNN(feat_dim, n_hid, T, R, n_heads, n_layers, dropout=0.2, conv_name=conv, prev_norm=True, last_norm=True, use_RTE=True).to(device)
     head = Classifier(n_hid, n_classes).to(device)
+    if recompute:          # memory-lean: the layers keep neither Q|K|V, the a_linear output nor the dropout masks for the backward
+        import pyhgt_amd
+        pyhgt_amd.set_recompute(gnn, True)
     if deterministic:      # every reduction of the backward in a fixed order: two runs with one seed give the same bits
         import pyhgt_amd
         pyhgt_amd.set_deterministic(gnn, True), pyhgt_amd.set_deterministic(head, True)
@@ -67,6 +70,7 @@ if __name__ == "__main__":
     ap.add_argument("--n-hid", type=int, default=int(os.environ.get("HGT_TRAIN_D", 128)), help="hidden width (e.g. 768 with 8 heads)")
     ap.add_argument("--n-heads", type=int, default=int(os.environ.get("HGT_TRAIN_H", 8)))
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible training: atomic-free backward, torch seeded with --seed")
+    ap.add_argument("--recompute", action="store_true", help="memory-lean training: Q|K|V and the dropout masks are recomputed in the backward")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
-    run(a.schema, a.steps, a.conv, n_hid=a.n_hid, n_heads=a.n_heads, seed=a.seed, deterministic=a.deterministic)
+    run(a.schema, a.steps, a.conv, n_hid=a.n_hid, n_heads=a.n_heads, seed=a.seed, deterministic=a.deterministic, recompute=a.recompute)

@@ -733,6 +733,20 @@ int hgt_conv_prepared_bytes(int32_t in_dim, int32_t out_dim, int32_t n_types, in
                             int32_t use_rte, uint64_t* out_host);
 int hgt_conv_forward(const hgt_conv_args* args_host, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Counter-based dropout (csrc/hgt_dropout.hip; the recompute mode of the training step, pyhgt_amd/autograd.py): the mask of
+ * nn.Dropout (conv.py:125 / 261,273) as a pure function of (seed, offset, keep, element index), so that a training step keeps a
+ * seed instead of a float mask and writes the mask again in its backward.  Added under ABI 8 (new symbols only).
+ *   generator Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = the 64-bit value offset + i / 4 in counter words 0 and
+ *   1 (words 2, 3 zero); element i takes output word i % 4 and is kept iff word < (uint32)(keep * 2^32).
+ *   hgt_dropout_mask   m[i] = kept ? 1.0f / keep : 0
+ *   hgt_dropout_apply  x[i] *= that float: bit-identical to hgt_mul_inplace(x, m)
+ * keep >= 1: every element kept with factor 1; keep <= 0: zeros (Dropout(p = 1)).  Any alignment of the pointer (16-byte aligned
+ * arrays move 16 bytes per lane).  n == 0 -> HGT_OK without a runtime call; NULL pointer, n < 0, keep NaN -> HGT_ERR_INVALID_ARG.
+ * ---------------------------------------------------------------------------------------------- */
+int hgt_dropout_mask(float* m, int64_t n, uint64_t seed, uint64_t offset, float keep, void* stream);
+int hgt_dropout_apply(float* x, int64_t n, uint64_t seed, uint64_t offset, float keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

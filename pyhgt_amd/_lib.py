@@ -187,6 +187,9 @@ SIGNATURES = {
     "hgt_conv_workspace_bytes_ex": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_u64)]),
     "hgt_conv_prepared_bytes": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_u64)]),
     "hgt_conv_forward": (C.c_int, [C.POINTER(HgtConvArgs), _vp]),
+    # counter-based dropout (csrc/hgt_dropout.hip): (array, n, seed, offset, keep, stream)
+    "hgt_dropout_mask": (C.c_int, [_vp, _i64, _u64, _u64, C.c_float, _vp]),
+    "hgt_dropout_apply": (C.c_int, [_vp, _i64, _u64, _u64, C.c_float, _vp]),
 }
 
 _lib = None

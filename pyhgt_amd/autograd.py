@@ -19,6 +19,7 @@ There is no CPU or eager fallback: CPU tensors raise.
 """
 import ctypes as C
 import math
+from collections import namedtuple
 from types import SimpleNamespace
 
 import torch
@@ -28,7 +29,7 @@ from ._lib import check
 from .conv import _ptr, _stream
 
 __all__ = ["hgt_conv_train", "training_supported", "logits_form", "outer_form", "spmm_takes_items", "takes_det_route", "set_deterministic",
-           "TypedLinearFunction", "MAX_TRAIN_DK_PAD"]
+           "takes_recompute", "set_recompute", "TypedLinearFunction", "MAX_TRAIN_DK_PAD"]
 
 
 MAX_TRAIN_DK_PAD = 256      # widest (padded) head the training path covers: the matrix-core form of hgt_edge_spmm ends there
@@ -94,6 +95,41 @@ def set_deterministic(module, on=True):
         if isinstance(m, (HGTConv, GNN, Classifier, Matcher)):
             m.deterministic = bool(on)
     return module
+
+
+def takes_recompute(module):
+    """Does `module` train in the memory-lean mode (its `recompute` attribute and nothing else; a module unpickled without the
+    attribute is a default one)?  Only the layers act on it: the adapter and the heads keep nothing that could be recomputed."""
+    return bool(getattr(module, "recompute", False))
+
+
+def set_recompute(module, on=True):
+    """Set `recompute` on every pyhgt_amd module of a model (the layers, GNN, Classifier, Matcher), like set_deterministic.  Returns
+    the module.  With it a layer's training forward keeps neither Q|K|V, the a_linear output (HGTConv) nor its dropout masks between
+    forward and backward: the backward projects Q|K|V again, runs a_linear again and writes the masks again from the layer call's
+    seed (hgt_dropout_mask) -- the same kernels on the same inputs, hence the same bits as the tensors the default mode keeps
+    (memory-lean training).  The masks themselves come from the counter-based generator of csrc/hgt_dropout.hip
+    instead of torch.bernoulli: a seeded run repeats, but draws other masks than the default mode does."""
+    from .conv import HGTConv
+    from .model import GNN, Classifier, Matcher
+    for m in module.modules():
+        if isinstance(m, (HGTConv, GNN, Classifier, Matcher)):
+            m.recompute = bool(on)
+    return module
+
+
+# Dropout of the recompute mode.  One 64-bit seed per layer call; dropout site s of the call (0: the a_linear output, conv.py:125 /
+# 261; 1: DenseHGTConv's out_linear output, conv.py:273) is hgt_dropout_apply / hgt_dropout_mask at (seed, s << DROP_SITE_SHIFT, keep):
+# a site covers at most 2^31 elements = 2^29 counter values, so the counter ranges of two sites never meet.
+DROP_SITE_SHIFT = 40
+_DropSite = namedtuple("_DropSite", "seed offset keep")
+
+
+class _CounterDropout(namedtuple("_CounterDropout", "seed keep offsets")):
+    """(seed, keep, offsets): what a layer call in recompute mode keeps of its dropout, and `layer.last_dropout_state`."""
+
+    def site(self, s):
+        return _DropSite(self.seed, self.offsets[s], self.keep) if s < len(self.offsets) else None
 
 
 def _det_ws(dev, name, *size_args):
@@ -310,8 +346,19 @@ class _Step:
         return out
 
     def drop_(self, t, mask):
-        if mask is not None:
+        """t *= mask: a float mask tensor, or a _DropSite of the recompute mode (the mask is generated on the fly)."""
+        if isinstance(mask, _DropSite):
+            check(self.lib.hgt_dropout_apply(_ptr(t), t.numel(), mask.seed, mask.offset, mask.keep, _stream()), "hgt_dropout_apply")
+        elif mask is not None:
             check(self.lib.hgt_mul_inplace(_ptr(t), _ptr(mask), t.numel(), _stream()), "hgt_mul_inplace")
+
+    def drop_mask(self, site):
+        """The [NQ, out_dim] float mask drop_ applied at `site` (None: no dropout), written again for the backward kernels."""
+        if site is None:
+            return None
+        m = self.new(self.NQ, self.dout)
+        check(self.lib.hgt_dropout_mask(_ptr(m), m.numel(), site.seed, site.offset, site.keep, _stream()), "hgt_dropout_mask")
+        return m
 
     def node_update_bwd(self, *args):
         """hgt_node_update_bwd_ex(*args, stream), or its atomic-free form (one partial per wavefront's row range, summed in range order)."""
@@ -631,19 +678,49 @@ class _HGTConvTrain(torch.autograd.Function):
         Q, K, V = step.qkv_views(qkv)
         att, layer.att = step.attention(Q, K, rte_k, att_t)
         agg = step.aggregate(att, V, rte_v, msg_p, msg_f)
-        m1, m2 = drop_masks if drop_masks is not None else (None, None)
+        # drop_masks: None, (m1, m2) float masks, or the _CounterDropout of the recompute mode (sites instead of tensors)
+        ctx.drop = drop_masks if isinstance(drop_masks, _CounterDropout) else None
+        if ctx.drop is not None:
+            m1, m2 = ctx.drop.site(0), ctx.drop.site(1)
+        else:
+            m1, m2 = drop_masks if drop_masks is not None else (None, None)
         out, kept = (step.update_dense if dense else step.update_hgt)(p, x, agg, m1, m2)
         ctx.layer, ctx.plan, ctx.lay, ctx.dense = layer, plan, step.lay, dense
-        _save_named(ctx, dict(x=x, w_qkv=p.w_qkv, w_a=p.w_a, ratt=p.ratt, rmsg=p.rmsg, rpri=p.rpri, skip=p.skip, ln_w=p.ln_w,
-                              rte_emb=p.rte_emb, rte_w=p.rte_w, rte_b=p.rte_b, mid_w=p.mid_w, out_w=p.out_w, out_ln_w=p.out_ln_w,
-                              qkv=qkv, att=att, agg=agg, rte_k=rte_k, rte_v=rte_v, m1=m1, m2=m2, **kept))
+        ctx.recompute = takes_recompute(layer)
+        saved = dict(x=x, w_qkv=p.w_qkv, w_a=p.w_a, ratt=p.ratt, rmsg=p.rmsg, rpri=p.rpri, skip=p.skip, ln_w=p.ln_w,
+                     rte_emb=p.rte_emb, rte_w=p.rte_w, rte_b=p.rte_b, mid_w=p.mid_w, out_w=p.out_w, out_ln_w=p.out_ln_w,
+                     qkv=qkv, att=att, agg=agg, rte_k=rte_k, rte_v=rte_v, m1=m1, m2=m2, **kept)
+        if ctx.recompute:
+            # not kept: Q|K|V, the masks and HGTConv's a_linear output (DenseHGTConv's feeds y1, which stays).  The recomputation reads
+            # b_qkv and b_a, which the default mode lets go: instead of the packed arrays (new memory) the bias PARAMETERS they were
+            # packed from are saved (they live anyway, and torch checks their version counters like any saved tensor's)
+            saved.update(qkv=None, m1=None, m2=None)
+            if not dense:
+                saved.update(trans=None)
+            saved.update({"bias_%s%d" % (k, t): b for k, bs in layer._bias_parameters().items() for t, b in enumerate(bs)})
+        _save_named(ctx, saved)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         s = _load_named(ctx)
         step = _Step(ctx.layer, ctx.plan, ctx.lay)
+        if ctx.recompute:
+            # what the forward did not keep, by the forward's own steps on the forward's inputs (the same kernels, hence the same bits),
+            # each dropped after its last consumer.  `s` is rebuilt per call: a second backward (retain_graph) recomputes again
+            drop = ctx.drop
+            with torch.no_grad():
+                s.b_qkv, s.b_a = ctx.layer._pack_biases({k: [getattr(s, "bias_%s%d" % (k, t)) for t in range(step.T)] for k in "qkva"},
+                                                        ctx.lay)
+            if not ctx.dense:
+                s.trans = step.a_linear(s.agg, s, drop and drop.site(0), gelu=True)
+            s.m1, s.m2 = (step.drop_mask(drop.site(0)), step.drop_mask(drop.site(1))) if drop else (None, None)
         dagg, dx_skip, grads = (step.update_dense_bwd if ctx.dense else step.update_hgt_bwd)(s, gout.contiguous().float())
+        if ctx.recompute:
+            s.m1 = s.m2 = None
+            if not ctx.dense:
+                s.trans = None
+            s.qkv = step.project(s.x, s)
         ds = step.attention_bwd(s, dagg)
         scale = (s.rpri / math.sqrt(step.dk)).view(step.R, step.Hreal, 1, 1)
         dqkv, f_k, f_v = step.qkv_bwd(s, dagg, ds, scale)
@@ -652,6 +729,8 @@ class _HGTConvTrain(torch.autograd.Function):
         if ctx.layer.use_RTE:
             rte_grads, d_w_kv_tables = step.temporal_bwd(s, dagg, ds, f_k, f_v)
             grads.update(rte_grads)
+        if ctx.recompute:
+            s.qkv = None
         grads.update(step.project_bwd(s, dqkv, dx_skip, d_w_kv_tables, ctx.needs_input_grad[len(PLAIN_SLOTS) + TENSOR_SLOTS.index("x")]))
         assert set(grads) <= set(TENSOR_SLOTS), sorted(set(grads) - set(TENSOR_SLOTS))
         return (None,) * len(PLAIN_SLOTS) + tuple(grads.get(k) for k in TENSOR_SLOTS)
@@ -672,13 +751,20 @@ def hgt_conv_train(layer, plan, x, packed, drop_p):
         raise ValueError("pyhgt_amd: a training step needs at least one target row (n_q_rows == 0 of %d nodes)" % plan.N)
     dense = "mid_w" in packed
     masks = None
-    if drop_p > 0.0:
+    if drop_p > 0.0 and takes_recompute(layer):
+        # one 64-bit seed per layer call from torch's CPU generator (torch.manual_seed governs it; no device synchronisation);
+        # DenseHGTConv drops twice (conv.py:261 and conv.py:273).  keep <= 0: hgt_dropout_* write zeros, like the rule below
+        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) & (2 ** 64 - 1)
+        masks = _CounterDropout(seed, float(1.0 - drop_p), tuple(s << DROP_SITE_SHIFT for s in range(2 if dense else 1)))
+    elif drop_p > 0.0:
         keep = 1.0 - drop_p
         if keep <= 0.0:      # nn.Dropout(p=1) yields zeros (not 0/0)
             draw = lambda: torch.zeros((plan.NQ, layer.out_dim), dtype=torch.float32, device=x.device)
         else:
             draw = lambda: torch.bernoulli(torch.full((plan.NQ, layer.out_dim), keep, dtype=torch.float32, device=x.device)) / keep
         masks = (draw(), draw() if dense else None)          # DenseHGTConv drops twice (conv.py:261 and conv.py:273)
+    if takes_recompute(layer):      # (seed, keep, offsets) of this call's dropout, for whoever wants its masks again; None: no dropout
+        layer.last_dropout_state = tuple(masks) if masks is not None else None
     inputs = dict(packed, x=x)
     assert all(k in TENSOR_SLOTS for k, t in inputs.items() if torch.is_tensor(t)), "a packed parameter without a slot in TENSOR_SLOTS"
     return _HGTConvTrain.apply(layer, plan, masks, *(inputs.get(k) for k in TENSOR_SLOTS))

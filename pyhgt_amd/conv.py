@@ -418,7 +418,7 @@ class HGTConv(nn.Module):
     """
 
     def __init__(self, in_dim, out_dim, num_types, num_relations, n_heads, dropout=0.2, use_norm=True, use_RTE=True,
-                 keep_att=False, precision=DEFAULT_PRECISION, strict=None, deterministic=False, **kwargs):
+                 keep_att=False, precision=DEFAULT_PRECISION, strict=None, deterministic=False, recompute=False, **kwargs):
         super().__init__()
         self.in_dim, self.out_dim = in_dim, out_dim
         self.num_types, self.num_relations = num_types, num_relations
@@ -436,6 +436,10 @@ class HGTConv(nn.Module):
         # bit-reproducible mode: the training step takes the atomic-free `_det` kernels (autograd.takes_det_route), inference the
         # deterministic hub mode; opt-in only -- torch.use_deterministic_algorithms does not move it
         self.deterministic = bool(deterministic)
+        # memory-lean training: the training forward keeps neither Q|K|V, the a_linear output nor the dropout masks; the backward
+        # computes them again (autograd.takes_recompute).  Opt-in; inference does not look at it
+        self.recompute = bool(recompute)
+        self.last_dropout_state = None      # recompute mode: (seed, keep, offsets) of the last training forward's dropout
         self.att = None
 
         self.k_linears = nn.ModuleList(nn.Linear(in_dim, out_dim) for _ in range(num_types))
@@ -458,8 +462,8 @@ class HGTConv(nn.Module):
 
     # -- state that is not part of the reference module: caches of packed parameters / device-side weight images ------
     EXTRA_KERNEL_FLAGS = 0      # OR-ed into every layer's kernel_flags (tests: tests/conftest.py sets it from HGT_TEST_KERNEL_FLAGS)
-    _RUNTIME_DEFAULTS = dict(keep_att=False, precision=DEFAULT_PRECISION, kernel_flags=0, strict=None, deterministic=False, att=None,
-                             _packed=None, _packed_key=None,
+    _RUNTIME_DEFAULTS = dict(keep_att=False, precision=DEFAULT_PRECISION, kernel_flags=0, strict=None, deterministic=False, recompute=False,
+                             last_dropout_state=None, att=None, _packed=None, _packed_key=None,
                              _prepared=None, _prepared_tag=None, _prepared_valid=False, _plist=None)
 
     def _init_runtime_state(self):
@@ -528,6 +532,34 @@ class HGTConv(nn.Module):
         a.skip = _ptr(pk["skip"])
 
     # ------------------------------------------------------------------------------------------
+    def _pad_head_rows(self, w, lay):
+        """[dout, *] -> [dp, *]: each head's dk rows followed by dkp-dk zero rows, then HL-H all-zero heads (HL = the layout's head
+        count: H rounded up to a power of two)."""
+        H, dk, dkp, dp, HL = self.n_heads, lay.d_k, lay.dk_pad, lay.d_pad, lay.heads
+        if dkp == dk and HL == H:
+            return w
+        tail = w.shape[1:]
+        w = w.reshape(H, dk, *tail)
+        if dkp != dk:
+            w = torch.cat([w, w.new_zeros(H, dkp - dk, *tail)], dim=1)
+        if HL != H:
+            w = torch.cat([w, w.new_zeros(HL - H, dkp, *tail)], dim=0)
+        return w.reshape(dp, *tail)
+
+    def _bias_parameters(self):
+        """The bias parameters by type, as _pack_biases takes them.  The recompute mode of the training step keeps THESE (they live
+        anyway) instead of the packed arrays and packs them again in its backward (pyhgt_amd/autograd.py)."""
+        return dict(q=[m.bias for m in self.q_linears], k=[m.bias for m in self.k_linears], v=[m.bias for m in self.v_linears],
+                    a=[m.bias for m in self.a_linears])
+
+    def _pack_biases(self, b, lay):
+        """(b_qkv [T][3 dp], b_a [T][dout]) of hgt_conv_args from the per-type biases of _bias_parameters (pure data movement)."""
+        pad = lambda w: self._pad_head_rows(w, lay)
+        b_qkv = torch.stack([torch.cat([pad(b["q"][t]), pad(b["k"][t]), pad(b["v"][t])], 0)
+                             for t in range(self.num_types)]).float().contiguous()
+        b_a = torch.stack(list(b["a"])).float().contiguous()
+        return b_qkv, b_a
+
     def _pack_parameters(self, grad=False):
         """Stack the per-type Linear / LayerNorm parameters into the contiguous, head-padded arrays
         hgt_conv_forward takes (pure data movement; cached until a parameter changes).  grad=True: built with autograd
@@ -549,25 +581,15 @@ class HGTConv(nn.Module):
         HL = lay.heads            # heads of the layout: H rounded up to a power of two; the extra heads are all-zero
         T, din, dout = self.num_types, self.in_dim, self.out_dim
 
-        def pad_rows(w):          # [dout, *] -> [dp, *] (each head's dk rows followed by dkp-dk zero rows, then HL-H zero heads)
-            if dkp == dk and HL == H:
-                return w
-            tail = w.shape[1:]
-            w = w.reshape(H, dk, *tail)
-            if dkp != dk:
-                w = torch.cat([w, w.new_zeros(H, dkp - dk, *tail)], dim=1)
-            if HL != H:
-                w = torch.cat([w, w.new_zeros(HL - H, dkp, *tail)], dim=0)
-            return w.reshape(dp, *tail)
+        def pad_rows(w):
+            return self._pad_head_rows(w, lay)
 
         det = (lambda t: t) if grad else (lambda t: t.detach())
         with torch.set_grad_enabled(bool(grad)):
             w_qkv = torch.stack([torch.cat([pad_rows(self.q_linears[t].weight), pad_rows(self.k_linears[t].weight),
                                             pad_rows(self.v_linears[t].weight)], 0) for t in range(T)]).float().contiguous()
-            b_qkv = torch.stack([torch.cat([pad_rows(self.q_linears[t].bias), pad_rows(self.k_linears[t].bias),
-                                            pad_rows(self.v_linears[t].bias)], 0) for t in range(T)]).float().contiguous()
             w_a = torch.stack([pad_rows(self.a_linears[t].weight.t()).t() for t in range(T)]).float().contiguous()
-            b_a = torch.stack([self.a_linears[t].bias for t in range(T)]).float().contiguous()
+            b_qkv, b_a = self._pack_biases(self._bias_parameters(), lay)
             ln_w = ln_b = None
             if self.use_norm:
                 ln_w = torch.stack([self.norms[t].weight for t in range(T)]).float().contiguous()

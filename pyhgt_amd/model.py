@@ -22,9 +22,10 @@ __all__ = ["GNN", "Classifier", "Matcher"]
 
 class GNN(nn.Module):
     def __init__(self, in_dim, n_hid, num_types, num_relations, n_heads, n_layers, dropout=0.2, conv_name='hgt',
-                 prev_norm=False, last_norm=False, use_RTE=True, deterministic=False):
+                 prev_norm=False, last_norm=False, use_RTE=True, deterministic=False, recompute=False):
         super().__init__()
         self.deterministic = bool(deterministic)      # bit-reproducible training (autograd.set_deterministic reaches the layers too)
+        self.recompute = bool(recompute)              # memory-lean training of the layers (autograd.set_recompute)
         self.gcs = nn.ModuleList()
         self.num_types = num_types
         self.in_dim = in_dim
@@ -41,6 +42,9 @@ class GNN(nn.Module):
         if deterministic:
             for gc in self.gcs:
                 gc.base_conv.deterministic = True
+        if recompute:
+            for gc in self.gcs:
+                gc.base_conv.recompute = True
 
     def __getstate__(self):
         st = dict(self.__dict__)

@@ -5,7 +5,10 @@ HGT_TRAIN_E (nodes, edges), HGT_TRAIN_D, HGT_TRAIN_H (width, heads); HGT_TRAIN_N
 --deterministic (or HGT_TRAIN_DETERMINISTIC=1) times the bit-reproducible mode (deterministic=True on every module).
 --emulate-world W [--out FILE]: instead, the training step of ONE rank of a W-rank destination partition on one GPU, the recipe of
 bench.py --emulate-world (exact receive side, mirrored send side, the all-to-alls replaced by device copies of as many bytes):
-forward, backward and, inside the backward, the return of the halo gradients, of one layer; the JSON line is appended to FILE."""
+forward, backward and, inside the backward, the return of the halo gradients, of one layer; the JSON line is appended to FILE.
+--recompute [--out FILE]: instead, the memory-lean mode (recompute=True) against the default mode in ONE process: the layer step of
+the sizes above in both modes, alternating (5 warm-ups, median of 20, events on the compute stream), hgt_dropout_apply against
+hgt_mul_inplace at n = 2^28, and torch.cuda.max_memory_allocated() of a four-layer step in each mode; FILE is written as JSON."""
 import json
 import os
 import sys
@@ -153,8 +156,106 @@ def emulated_rank_step(dev, W, out_path=None, iters=5):
     return res
 
 
+def recompute_compare(dev, out_path=None, warmup=5, iters=20):
+    """The memory-lean training mode against the default one (see the module docstring)."""
+    from pyhgt_amd import _lib
+    N, E, d, T, R, H = (int(os.environ.get("HGT_TRAIN_N", 1000000)), int(os.environ.get("HGT_TRAIN_E", 10000000)),
+                        int(os.environ.get("HGT_TRAIN_D", 256)), 4, 8, int(os.environ.get("HGT_TRAIN_H", 8)))
+    x, nt, ei, et, tm = [t.to(dev) for t in synthetic_typed_graph(N, E, d, T, R, seed=1)]
+    plan = GraphPlan(nt, ei, et, None, T, R)
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    med = lambda v: sorted(v)[len(v) // 2]
+    torch.manual_seed(0)
+    layers = {m: HGTConv(d, d, T, R, H, 0.2, True, False, deterministic=DETERMINISTIC, recompute=(m == "recompute")).to(dev).train()
+              for m in ("default", "recompute")}
+    layers["recompute"].load_state_dict(layers["default"].state_dict())
+    xg = x.clone().requires_grad_(True)
+    g = torch.randn(N, d, device=dev)
+    rows = {m: [] for m in layers}
+    for it in range(warmup + iters):
+        for m, layer in layers.items():                            # the two modes alternate: both see the same clocks
+            e0, e1, e2 = ev(), ev(), ev()
+            e0.record()
+            out = layer(xg, nt, ei, et, None, plan=plan)
+            e1.record()
+            out.backward(g)
+            e2.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                rows[m].append((e0.elapsed_time(e1), e1.elapsed_time(e2), e0.elapsed_time(e2)))
+            layer.zero_grad(set_to_none=True)
+            xg.grad = None
+            del out
+    res = {"N": N, "E": E, "d": d, "H": H, "dropout": 0.2, "deterministic": DETERMINISTIC, "warmup": warmup, "steps": iters}
+    for m in layers:
+        res[m] = {k: round(med([r[i] for r in rows[m]]), 3) for i, k in enumerate(("forward_ms", "backward_ms", "step_ms"))}
+        res[m]["step_ms_min_max"] = [round(min(r[2] for r in rows[m]), 3), round(max(r[2] for r in rows[m]), 3)]
+    res["step_ratio_recompute_over_default"] = round(res["recompute"]["step_ms"] / res["default"]["step_ms"], 4)
+    del layers, xg, g
+    # peak memory of a four-layer step, one mode after the other
+    for m in ("default", "recompute"):
+        stack = [HGTConv(d, d, T, R, H, 0.2, True, False, deterministic=DETERMINISTIC, recompute=(m == "recompute")).to(dev).train()
+                 for _ in range(4)]
+        xg = x.clone().requires_grad_(True)
+        for it in range(2):
+            if it == 1:
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+            h = xg
+            for layer in stack:
+                h = layer(h, nt, ei, et, None, plan=plan)
+            torch.cuda.synchronize()
+            kept = torch.cuda.memory_allocated()
+            h.backward(torch.ones_like(h))
+            torch.cuda.synchronize()
+            for layer in stack:
+                layer.zero_grad(set_to_none=True)
+            xg.grad = None
+            del h
+        res[m]["four_layer_step"] = {"max_memory_allocated_gb": round(torch.cuda.max_memory_allocated() / 1e9, 3),
+                                     "kept_after_forward_gb": round((kept - base) / 1e9, 3),
+                                     "allocated_before_gb": round(base / 1e9, 3)}
+        del stack, xg
+    del x, nt, ei, et, tm, plan
+    GraphPlan.clear_cache()
+    torch.cuda.empty_cache()
+    # the dropout kernel alone: apply (reads and writes x) against mul_inplace (reads x and a mask, writes x)
+    lib, n = _lib.load(), 1 << 28
+    st = torch.cuda.current_stream().cuda_stream
+    a = torch.randn(n, device=dev)
+    mask = torch.empty(n, device=dev)
+    _lib.check(lib.hgt_dropout_mask(mask.data_ptr(), n, 12345, 0, 0.8, st), "hgt_dropout_mask")
+    calls = {"hgt_dropout_apply": lambda: lib.hgt_dropout_apply(a.data_ptr(), n, 12345, 0, 0.8, st),
+             "hgt_mul_inplace": lambda: lib.hgt_mul_inplace(a.data_ptr(), mask.data_ptr(), n, st),
+             "hgt_dropout_mask": lambda: lib.hgt_dropout_mask(mask.data_ptr(), n, 12345, 0, 0.8, st)}
+    times = {k: [] for k in calls}
+    for it in range(warmup + iters):
+        for k, fn in calls.items():
+            e0, e1 = ev(), ev()
+            e0.record()
+            _lib.check(fn(), k)
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                times[k].append(e0.elapsed_time(e1))
+    moved = {"hgt_dropout_apply": 8 * n, "hgt_mul_inplace": 12 * n, "hgt_dropout_mask": 4 * n}
+    res["dropout_kernels"] = {"n": n, **{k: {"ms": round(med(v), 4), "gb_per_s": round(moved[k] / (med(v) * 1e-3) / 1e9, 1)}
+                                         for k, v in times.items()}}
+    res["dropout_kernels"]["apply_over_mul_inplace"] = round(med(times["hgt_dropout_apply"]) / med(times["hgt_mul_inplace"]), 4)
+    line = json.dumps(res, indent=1)
+    print(line)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return res
+
+
 def main():
     dev = "cuda:0"
+    if "--recompute" in sys.argv:
+        recompute_compare(dev, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+        return
     if "--emulate-world" in sys.argv:
         W = int(sys.argv[sys.argv.index("--emulate-world") + 1])
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
