@@ -3,7 +3,11 @@
 OAG/train_paper_field.py:218-279): sampled batch -> to_device_graph (instead of to_torch + .to(device)) -> GNN -> Classifier
 -> nll_loss -> backward -> optimizer step, on sampler-shaped synthetic batches (the datasets are not available offline).
 
-    python examples/train_synthetic.py [--schema mag|oag] [--steps 30] [--conv hgt|dense_hgt] [--n-hid 128] [--n-heads 8]
+    python examples/train_synthetic.py [--schema mag|oag] [--steps 30] [--conv hgt|dense_hgt] [--n-hid 128] [--n-heads 8] [--stack B]
+
+--stack B: B sampled batches per optimizer step, stacked on the device into one block-diagonal graph (stack_device_graphs): one
+forward and one backward for the launch count of one batch.  It is ONE optimizer step over B batches (a B times larger batch),
+and its dropout masks are drawn over the stacked rows: another draw than B separate steps'.
 
 Everything on the hot path runs on the HIP kernels of pyhgt_amd (forward and backward); torch supplies the optimizer, the loss
 and the autograd boundary."""
@@ -16,22 +20,28 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyhgt_amd import GNN, Classifier  # noqa: E402
-from pyhgt_amd.sampled import synthetic_sampled_batch, to_device_graph  # noqa: E402
+from pyhgt_amd.sampled import stack_device_graphs, synthetic_sampled_batch, to_device_graph  # noqa: E402
 
 
 def run(schema="mag", steps=30, conv="hgt", n_hid=128, n_heads=8, n_layers=2, n_classes=16, batch_size=128, lr=2e-3, seed=0,
-        device="cuda:0", verbose=True, deterministic=False, recompute=False):
+        device="cuda:0", verbose=True, deterministic=False, recompute=False, stack=1):
     torch.manual_seed(seed)      # (already seeds the parameters and the dropout masks; deterministic=True makes the gradients repeat too)
     feat_dim = 129 if schema == "mag" else 256
     batches = []
-    for b in range(4):      # a small pool of sampled batches, cycled like an epoch of pre-sampled jobs (train_ogbn_mag.py:82-104)
+    for b in range(4 * stack):      # a small pool of sampled batches, cycled like an epoch of pre-sampled jobs (train_ogbn_mag.py:82-104)
         fe, ti, el, graph = synthetic_sampled_batch(schema, n_seed=batch_size, width=64, depth=4, feat_dim=feat_dim, mean_degree=6.0,
                                                     seed=seed * 100 + b)
-        dg = to_device_graph(fe, ti, el, graph, device=device)
+        dg = to_device_graph(fe, ti, el, graph, device=device, plan=stack == 1)      # pieces that are only stacked need no plan
         g = torch.Generator().manual_seed(b)
         proj = torch.randn(feat_dim, n_classes, generator=g)
         labels = (dg[0][:batch_size].cpu() @ proj).argmax(dim=1).to(device)     # a learnable synthetic task on the seed papers
-        batches.append((dg, labels))
+        batches.append((dg, labels, slice(0, batch_size)))
+    if stack > 1:          # B batches -> one graph; its seed rows are the pieces' first batch_size papers
+        groups = [batches[i:i + stack] for i in range(0, len(batches), stack)]
+        batches = []
+        for grp in groups:
+            sg = stack_device_graphs([dg for dg, _, _ in grp])
+            batches.append((sg, torch.cat([y for _, y, _ in grp]), torch.cat([sg.rows(b, "paper", range(batch_size)) for b in range(len(grp))])))
     T, R = len(batches[0][0][5]), len(batches[0][0][6])
     gnn = GNN(feat_dim, n_hid, T, R, n_heads, n_layers, dropout=0.2, conv_name=conv, prev_norm=True, last_norm=True, use_RTE=True).to(device)
     head = Classifier(n_hid, n_classes).to(device)
@@ -44,10 +54,10 @@ def run(schema="mag", steps=30, conv="hgt", n_hid=128, n_heads=8, n_layers=2, n_
     opt = torch.optim.AdamW(list(gnn.parameters()) + list(head.parameters()), lr=lr)
     losses, t0 = [], time.perf_counter()
     for step in range(steps):
-        (x, nt, tm, ei, et, _, _), y = batches[step % len(batches)]
+        (x, nt, tm, ei, et, _, _), y, seeds = batches[step % len(batches)]
         gnn.train(), head.train()
         rep = gnn(x, nt, tm, ei, et)
-        loss = torch.nn.functional.nll_loss(head(rep[:batch_size]), y)
+        loss = torch.nn.functional.nll_loss(head(rep[seeds]), y)
         opt.zero_grad()
         loss.backward()
         torch.nn.utils.clip_grad_norm_(gnn.parameters(), 0.5)
@@ -72,5 +82,6 @@ if __name__ == "__main__":
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible training: atomic-free backward, torch seeded with --seed")
     ap.add_argument("--recompute", action="store_true", help="memory-lean training: Q|K|V and the dropout masks are recomputed in the backward")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--stack", type=int, default=1, help="sampled batches per optimizer step, stacked on the device into one graph")
     a = ap.parse_args()
-    run(a.schema, a.steps, a.conv, n_hid=a.n_hid, n_heads=a.n_heads, seed=a.seed, deterministic=a.deterministic, recompute=a.recompute)
+    run(a.schema, a.steps, a.conv, n_hid=a.n_hid, n_heads=a.n_heads, seed=a.seed, deterministic=a.deterministic, recompute=a.recompute, stack=a.stack)

@@ -747,6 +747,33 @@ int hgt_conv_forward(const hgt_conv_args* args_host, void* stream);
 int hgt_dropout_mask(float* m, int64_t n, uint64_t seed, uint64_t offset, float keep, void* stream);
 int hgt_dropout_apply(float* x, int64_t n, uint64_t seed, uint64_t offset, float keep, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Stacking sampled batches (csrc/hgt_stack.hip; pyhgt_amd.sampled.stack_device_graphs): B graphs that are each in
+ * hgt_plan_from_sorted form become one block-diagonal graph in the same form.  Added under ABI 8 (new symbols only).
+ *   in   src / dst / edge_time   int32[E_tot], the pieces' arrays one after the other, ids LOCAL to the piece (edge_time may be NULL;
+ *                                then edge_time_out must be NULL too)
+ *        rel_ptr                 int32[B][R+1], piece-relative;   type_off  int32[B][T+1]
+ *        edge_off_host / node_off_host   HOST int64[B+1]: where piece b starts in the concatenation ([0] = 0, [B] = E_tot / N_tot);
+ *                                they travel as kernel arguments (B <= HGT_STACK_MAX_PIECES, HGT_ERR_UNSUPPORTED beyond)
+ *   out  src_out / dst_out / edge_time_out int32[E_tot], rel_ptr_out int32[R+1], type_off_out int32[T+1]: the stacked graph.
+ *        Stacked node id = type_off_out[t] + (nodes of type t in the pieces before b) + serial inside the piece's type t;
+ *        inside a relation the edges are ordered by target type, then piece, then the piece's own order (targets non-decreasing).
+ *        node_map int32[N_tot] / edge_map int32[E_tot]: stacked position -> position in the concatenation (permutations; node_map
+ *        is a row list for hgt_gather_rows).
+ *   tmp  hgt_stack_tmp_bytes(B, T, R) bytes of device scratch (HGT_ERR_WORKSPACE if smaller).
+ * Three launches, no sort, no atomic, no allocation, no synchronisation.  Every store is bounds-checked and the maps are permutations
+ * whatever the arrays hold; a piece that is not in the required form (targets not sorted inside a relation, ids outside the piece,
+ * rel_ptr / type_off not spanning it) yields a stacked graph on which hgt_plan_from_sorted sets bad_index (ids written as -1,
+ * rel_ptr_out[R] = -1).  Bad arguments -> a negative code and no launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_STACK_MAX_PIECES 256
+int hgt_stack_tmp_bytes(int32_t n_pieces, int32_t n_types, int32_t n_relations, uint64_t* bytes_host);
+int hgt_stack_sorted(const int32_t* src, const int32_t* dst, const int32_t* edge_time, const int32_t* rel_ptr,
+                     const int32_t* type_off, const int64_t* edge_off_host, const int64_t* node_off_host, int32_t n_pieces,
+                     int32_t n_types, int32_t n_relations, int32_t* src_out, int32_t* dst_out, int32_t* edge_time_out,
+                     int32_t* rel_ptr_out, int32_t* type_off_out, int32_t* node_map, int32_t* edge_map, void* tmp,
+                     uint64_t tmp_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

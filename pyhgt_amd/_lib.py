@@ -34,6 +34,7 @@ HGT_LINEAR_NO_TILE = 0x400
 HGT_LINEAR_TANH = 0x1000
 HGT_FEATURE_LAB_KERNELS = 1
 HGT_FEATURE_DETERMINISTIC_TRAINING = 2
+HGT_STACK_MAX_PIECES = 256
 
 
 class HgtLayout(C.Structure):
@@ -190,6 +191,11 @@ SIGNATURES = {
     # counter-based dropout (csrc/hgt_dropout.hip): (array, n, seed, offset, keep, stream)
     "hgt_dropout_mask": (C.c_int, [_vp, _i64, _u64, _u64, C.c_float, _vp]),
     "hgt_dropout_apply": (C.c_int, [_vp, _i64, _u64, _u64, C.c_float, _vp]),
+    # stacking sampled batches (csrc/hgt_stack.hip): (src, dst, time, rel_ptr[B][R+1], type_off[B][T+1], edge_off_host, node_off_host,
+    # B, T, R, src_out, dst_out, time_out, rel_ptr_out, type_off_out, node_map, edge_map, tmp, tmp_bytes, stream)
+    "hgt_stack_tmp_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_u64)]),
+    "hgt_stack_sorted": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _u64, _vp]),
 }
 
 _lib = None

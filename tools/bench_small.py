@@ -3,9 +3,15 @@
 sampled sub-graphs).  The datasets are not available offline, so the inputs are sampler-shaped synthetic batches with the
 layout facts of the reference pipeline (pyhgt_amd.sampled.synthetic_sampled_batch: type-contiguous ids, `self` runs first,
 target-sorted runs, edge_time in [111, 129], min in-degree 1), handed over once through `to_torch`'s wire format
-(hgt_plan_build: radix sorts) and once through the device-side hand-off (to_device_graph -> hgt_plan_from_sorted)."""
+(hgt_plan_build: radix sorts) and once through the device-side hand-off (to_device_graph -> hgt_plan_from_sorted).
+
+--stack B[,B...] [--out FILE]: instead, stacked batches (pyhgt_amd.sampled.stack_device_graphs): for every B, B pieces of the c3
+shape (one layer) and of the c5 shape (2-layer GNN) run as ONE block-diagonal graph against the same B pieces run one after the
+other, in one process, alternating, medians of 5 windows: us per piece and layer for both, and the time of stack_device_graphs
+itself (hgt_stack_sorted + feature gather + plan).  The JSON goes to stdout and, with --out, to FILE."""
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -30,8 +36,69 @@ def timeit(fn, iters=200, warm=20):
 PRECS = tuple(os.environ.get("HGT_SMALL_PRECS", "bf16x3,f16x3,fp32").split(","))      # e.g. HGT_SMALL_PRECS=f16x3 under rocprofv3
 
 
+def alternating(fns, iters, warm=10, windows=5):
+    """Median us per call of every function, the timed windows of the functions interleaved (window 1 of each, window 2 ...)."""
+    for fn in fns:
+        for _ in range(warm):
+            fn()
+    samples = [[] for _ in fns]
+    for _ in range(windows):
+        for i, fn in enumerate(fns):
+            samples[i].append(timeit(fn, iters=iters, warm=2))
+    return [statistics.median(v) for v in samples]
+
+
+def stack_bench(dev, Bs, out_path=None, precs=("bf16x3", "f16x3")):
+    from pyhgt_amd.sampled import stack_device_graphs
+    GraphPlan.CACHE_SIZE = 2 * max(Bs) + 8          # the pieces' plans and the stacks' stay registered
+    res = {"stack": list(Bs), "unit": "us per piece and layer (median of 5 alternating windows)"}
+    shapes = {"c3": dict(schema="mag", n_seed=128, width=128, depth=6, feat_dim=256, mean_degree=4.0, seed=3, layers=1),
+              "c5": dict(schema="oag", n_seed=256, width=128, depth=6, feat_dim=1169, mean_degree=1.2, seed=5, layers=2)}
+    for key, c in shapes.items():
+        pieces = [to_device_graph(*synthetic_sampled_batch(c["schema"], n_seed=c["n_seed"], width=c["width"], depth=c["depth"],
+                                                           feat_dim=c["feat_dim"], mean_degree=c["mean_degree"], seed=c["seed"] + i),
+                                  device=dev) for i in range(max(Bs))]
+        T, R, L = len(pieces[0][5]), len(pieces[0][6]), c["layers"]
+        res[key] = {"N_piece": int(pieces[0][1].numel()), "E_piece": int(pieces[0][4].numel())}
+        stacks = {B: stack_device_graphs(pieces[:B]) for B in Bs}
+        for B in Bs:
+            res[key]["B%d" % B] = {"N": int(stacks[B][1].numel()), "E": int(stacks[B][4].numel()),
+                                   "stack_device_graphs_us": timeit(lambda: stack_device_graphs(pieces[:B]), iters=50, warm=5)}
+        for prec in precs:
+            if key == "c3":
+                model = HGTConv(256, 256, T, R, 8, 0.2, True, True, precision=prec).eval().to(dev)
+                call = lambda g: model(g[0], g[1], g[3], g[4], g[2], plan=g.plan)
+            else:
+                model = GNN(1169, 400, T, R, 8, 2, prev_norm=True, last_norm=True, use_RTE=True).eval().to(dev)
+                for gc in model.gcs:
+                    gc.base_conv.precision = prec
+                call = lambda g: model(g[0], g[1], g[2], g[3], g[4])
+            with torch.no_grad():
+                for B in Bs:
+                    S, part = stacks[B], pieces[:B]
+                    us_stacked, us_loop = alternating([lambda: call(S), lambda: [call(g) for g in part]], iters=max(10, 100 // B))
+                    r = res[key]["B%d" % B]
+                    r[prec + "_stacked_us"], r[prec + "_loop_us"] = us_stacked / (B * L), us_loop / (B * L)
+                    print("%s x %2d  N=%6d E=%7d %-6s: stacked %7.1f us / piece and layer, one after the other %7.1f, stack_device_graphs "
+                          "%.0f us" % (key, B, r["N"], r["E"], prec, r[prec + "_stacked_us"], r[prec + "_loop_us"], r["stack_device_graphs_us"]),
+                          flush=True)
+        del pieces, stacks
+        GraphPlan.clear_cache()
+        torch.cuda.empty_cache()
+    line = json.dumps(res)
+    print(line)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return res
+
+
 def main():
     dev = "cuda:0"
+    if "--stack" in sys.argv:
+        Bs = [int(v) for v in sys.argv[sys.argv.index("--stack") + 1].split(",")]
+        stack_bench(dev, Bs, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+        return
     res = {}
     # configs[2] surrogate: ogbn-mag sampled sub-graph (sample_depth 6, sample_width 128), T=4 R=9 (incl. self), d=256 H=8
     batch = synthetic_sampled_batch("mag", n_seed=128, width=128, depth=6, feat_dim=256, mean_degree=4.0, seed=3)

@@ -8,7 +8,10 @@ bench.py --emulate-world (exact receive side, mirrored send side, the all-to-all
 forward, backward and, inside the backward, the return of the halo gradients, of one layer; the JSON line is appended to FILE.
 --recompute [--out FILE]: instead, the memory-lean mode (recompute=True) against the default mode in ONE process: the layer step of
 the sizes above in both modes, alternating (5 warm-ups, median of 20, events on the compute stream), hgt_dropout_apply against
-hgt_mul_inplace at n = 2^28, and torch.cuda.max_memory_allocated() of a four-layer step in each mode; FILE is written as JSON."""
+hgt_mul_inplace at n = 2^28, and torch.cuda.max_memory_allocated() of a four-layer step in each mode; FILE is written as JSON.
+--stack B[,B...] [--out FILE]: instead, the sampled-size training step (c3 layer, c5 2-layer GNN; forward + backward, dropout on) on
+B stacked batches (pyhgt_amd.sampled.stack_device_graphs) against the same B batches stepped one after the other, in one process,
+alternating, medians of 5 windows: ms per piece."""
 import json
 import os
 import sys
@@ -92,6 +95,69 @@ def sampled_batches(dev):
         gnn = GNN(c["in_dim"], c["n_hid"], c["T"], len(ed), c["H"], c["L"], 0.2, "hgt", c["norm"], c["norm"], True, deterministic=DETERMINISTIC).to(dev).train()
         res[key] = {"N": int(nt.numel()), "E": int(et.numel()), "n_hid": c["n_hid"], "layers": c["L"],
                     "fwd_bwd_us": step_us(lambda: gnn(x, nt, tm, ei, et), list(gnn.parameters()))}
+    return res
+
+
+def stacked_step(dev, Bs, out_path=None):
+    """ms per piece of the sampled-size training step (forward + backward, dropout on, gradients dropped) on B stacked batches and on
+    the same B batches one after the other; windows of the two interleaved, median of 5."""
+    import statistics
+    from pyhgt_amd import GNN
+    from pyhgt_amd.sampled import stack_device_graphs, synthetic_sampled_batch, to_device_graph
+    GraphPlan.CACHE_SIZE = 2 * max(Bs) + 8
+    res = {"stack": list(Bs), "unit": "ms per piece (median of 5 alternating windows)", "deterministic": DETERMINISTIC}
+    shapes = {"c3_layer": dict(schema="mag", n_seed=128, width=128, depth=6, feat_dim=256, mean_degree=4.0, seed=3),
+              "c5_gnn2": dict(schema="oag", n_seed=256, width=128, depth=6, feat_dim=1169, mean_degree=1.2, seed=5)}
+
+    def window(fn, params, iters):
+        for it in range(2 + iters):
+            if it == 2:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            for out in fn():
+                out.backward(torch.ones_like(out))
+            for p_ in params:
+                p_.grad = None
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters * 1e3
+
+    for key, c in shapes.items():
+        pieces = [to_device_graph(*synthetic_sampled_batch(c["schema"], n_seed=c["n_seed"], width=c["width"], depth=c["depth"],
+                                                           feat_dim=c["feat_dim"], mean_degree=c["mean_degree"], seed=c["seed"] + i),
+                                  device=dev) for i in range(max(Bs))]
+        T, R = len(pieces[0][5]), len(pieces[0][6])
+        if key == "c3_layer":
+            model = HGTConv(256, 256, T, R, 8, 0.2, True, True, deterministic=DETERMINISTIC).to(dev).train()
+            call = lambda g, x: model(x, g[1], g[3], g[4], g[2], plan=g.plan)
+            leaf = lambda g: g[0].clone().requires_grad_(True)          # dx is part of the layer step, as in sampled_batches()
+        else:
+            model = GNN(1169, 400, T, R, 8, 2, 0.2, "hgt", False, False, True, deterministic=DETERMINISTIC).to(dev).train()
+            call = lambda g, x: model(x, g[1], g[2], g[3], g[4])
+            leaf = lambda g: g[0]
+        params = list(model.parameters())
+        res[key] = {"N_piece": int(pieces[0][1].numel()), "E_piece": int(pieces[0][4].numel())}
+        for B in Bs:
+            S, part = stack_device_graphs(pieces[:B]), pieces[:B]
+            xS, xs = leaf(S), [leaf(g) for g in part]
+            fns = [lambda: [call(S, xS)], lambda: [call(g, x) for g, x in zip(part, xs)]]
+            leaves = [x for x in [xS] + xs if x.requires_grad]
+            samples = [[], []]
+            for _ in range(5):
+                for i, fn in enumerate(fns):
+                    samples[i].append(window(fn, params + leaves, max(4, 32 // B)))
+            r = res[key]["B%d" % B] = {"N": int(S[1].numel()), "E": int(S[4].numel()),
+                                       "stacked_ms": statistics.median(samples[0]) / B, "loop_ms": statistics.median(samples[1]) / B}
+            print("%s x %2d  N=%6d E=%7d: training step stacked %.3f ms / piece, one after the other %.3f" % (key, B, r["N"], r["E"],
+                                                                                                          r["stacked_ms"], r["loop_ms"]), flush=True)
+            del S
+        del pieces, model
+        GraphPlan.clear_cache()
+        torch.cuda.empty_cache()
+    line = json.dumps(res)
+    print(line)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
     return res
 
 
@@ -255,6 +321,10 @@ def main():
     dev = "cuda:0"
     if "--recompute" in sys.argv:
         recompute_compare(dev, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+        return
+    if "--stack" in sys.argv:
+        stacked_step(dev, [int(v) for v in sys.argv[sys.argv.index("--stack") + 1].split(",")],
+                     sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
         return
     if "--emulate-world" in sys.argv:
         W = int(sys.argv[sys.argv.index("--emulate-world") + 1])
