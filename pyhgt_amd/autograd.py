@@ -5,7 +5,7 @@ ogbn-mag/train_ogbn_mag.py:172).  Here a `torch.autograd.Function` wraps the HIP
 node-level algebra as the inference path (typed Q|K|V projections once per node, target-side relation transforms, softmax
 over in-edges, relation-wise aggregation on the matrix cores), run kernel by kernel so that Q, K, V, the attention weights,
 the aggregate and the a_linear output stay available; the backward strings together the kernels of
-csrc/hgt_backward.hip + the forward kernels on the transposed graph (the derivation is in that file's header).
+csrc/hgt_bwd_*.hip + the forward kernels on the transposed graph (the derivation is in the header of csrc/hgt_bwd_update.hip).
 
 Layout of this file: TENSOR_SLOTS (the one statement of the Function's input order), the kernel-choice predicates, the typed-linear
 route (_typed_linear / _wgrad, shared with TypedLinearFunction), _Step (the per-call context: kernel wrappers, then the named steps
@@ -141,6 +141,22 @@ def _det_ws(dev, name, *size_args):
     return t.data_ptr(), int(nb.value), t
 
 
+def _reduce_call(det, dev, name, size_args, *args, det_name=None):
+    """A backward step with a reduction: `name`(*args, stream) on the atomic route; on the det route `name`_det (or det_name) with the
+    same leading arguments + the workspace that `..._det_bytes`(*size_args) asks for.  The outputs follow _reduce_out."""
+    if det:
+        det_name = det_name or name + "_det"
+        wp, wb, keep = _det_ws(dev, det_name, *size_args)
+        check(getattr(_lib.load(), det_name)(*args, wp, wb, _stream()), det_name)
+    else:
+        check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
+def _reduce_out(det, dev, *shape):
+    """Output of a _reduce_call: the atomic route accumulates into a zeroed tensor, the det route overwrites an empty one."""
+    return (torch.empty if det else torch.zeros)(*shape, dtype=torch.float32, device=dev)
+
+
 # -- the typed-linear route: the layer's GEMMs and TypedLinearFunction ---------------------------------------------------------
 def _typed_linear(split, x, ldx, rows, off, n_groups, n_rows, k, n_out, W, w_off, wgs, bias, b_off, bgs, outs, block_cols, by_pos=0,
                   prologue=0):
@@ -167,33 +183,16 @@ def _wgrad(split, A, lda, B, ldb, rows, off, n_groups, n_rows, m, n_cols, with_c
     """(dW[g] = A_g^T B_g, db[g] = column sums of A_g or None): split-bf16 x3 MFMA kernel (both from one pass) for split precisions,
     the exact fp32 MFMA kernel + the column-sum kernel otherwise.  det: the same kernels' atomic-free forms (partials per row chunk,
     summed in chunk order)."""
-    lib = _lib.load()
-    if det:
-        dw = torch.empty(n_groups, m, n_cols, dtype=torch.float32, device=A.device)
-        db = torch.empty(n_groups, m, dtype=torch.float32, device=A.device) if with_colsum else None
-        if split:
-            wp, wb, keep = _det_ws(A.device, "hgt_typed_wgrad_bf16x3_det", n_groups, n_rows, m, n_cols)
-            check(lib.hgt_typed_wgrad_bf16x3_det(_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols,
-                                                 _ptr(db), m, wp, wb, _stream()), "hgt_typed_wgrad_bf16x3_det")
-        else:
-            wp, wb, keep = _det_ws(A.device, "hgt_typed_wgrad_det", n_groups, n_rows, m, n_cols)
-            check(lib.hgt_typed_wgrad_det(_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols, wp, wb,
-                                          _stream()), "hgt_typed_wgrad_det")
-            if with_colsum:
-                cp, cb, keep2 = _det_ws(A.device, "hgt_typed_colsum_det", n_groups, n_rows, m)
-                check(lib.hgt_typed_colsum_det(_ptr(A), lda, rows, off, n_groups, n_rows, m, _ptr(db), m, cp, cb, _stream()),
-                      "hgt_typed_colsum_det")
-        return dw, db
-    dw = torch.zeros(n_groups, m, n_cols, dtype=torch.float32, device=A.device)
-    db = torch.zeros(n_groups, m, dtype=torch.float32, device=A.device) if with_colsum else None
+    dev, sizes = A.device, (n_groups, n_rows, m, n_cols)
+    dw = _reduce_out(det, dev, n_groups, m, n_cols)
+    db = _reduce_out(det, dev, n_groups, m) if with_colsum else None
+    wgrad_args = (_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols)
     if split:
-        check(lib.hgt_typed_wgrad_bf16x3(_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols,
-                                         _ptr(db), m, _stream()), "hgt_typed_wgrad_bf16x3")
+        _reduce_call(det, dev, "hgt_typed_wgrad_bf16x3", sizes, *wgrad_args, _ptr(db), m)
     else:
-        check(lib.hgt_typed_wgrad(_ptr(A), lda, _ptr(B), ldb, rows, off, n_groups, n_rows, m, n_cols, _ptr(dw), m * n_cols, _stream()),
-              "hgt_typed_wgrad")
+        _reduce_call(det, dev, "hgt_typed_wgrad", sizes, *wgrad_args)
         if with_colsum:
-            check(lib.hgt_typed_colsum(_ptr(A), lda, rows, off, n_groups, n_rows, m, _ptr(db), m, _stream()), "hgt_typed_colsum")
+            _reduce_call(det, dev, "hgt_typed_colsum", sizes[:3], _ptr(A), lda, rows, off, n_groups, n_rows, m, _ptr(db), m)
     return dw, db
 
 
@@ -334,15 +333,11 @@ class _Step:
         return out
 
     def outer(self, plan, w, a, rte_a, b):
-        name = outer_form(self.dkp)
-        if self.det:      # partials per slice of the plan's item list, summed in slice order (the output is overwritten)
-            out = self.new(self.R, self.H, self.dkp, self.dkp)
-            wp, wb, keep = _det_ws(self.dev, name + "_det", plan.N, plan.E, self.T, self.R, self.H, self.dkp)
-            check(getattr(self.lib, name + "_det")(*self.graph(plan), self.dkp, _ptr(w), _ptr(a), _ptr(rte_a), _ptr(b), _ptr(out), wp, wb,
-                                                   _stream()), name + "_det")
-            return out
-        out = self.new(self.R, self.H, self.dkp, self.dkp, zero=True)
-        check(getattr(self.lib, name)(*self.graph(plan), self.dkp, _ptr(w), _ptr(a), _ptr(rte_a), _ptr(b), _ptr(out), _stream()), name)
+        """out[r][h] = sum over the edges of relation r of w_e a[src_e][h]^T b[dst_e][h]  (det: partials per slice of the plan's item
+        list, summed in slice order)."""
+        out = _reduce_out(self.det, self.dev, self.R, self.H, self.dkp, self.dkp)
+        _reduce_call(self.det, self.dev, outer_form(self.dkp), (plan.N, plan.E, self.T, self.R, self.H, self.dkp), *self.graph(plan), self.dkp,
+                     _ptr(w), _ptr(a), _ptr(rte_a), _ptr(b), _ptr(out))
         return out
 
     def drop_(self, t, mask):
@@ -362,11 +357,7 @@ class _Step:
 
     def node_update_bwd(self, *args):
         """hgt_node_update_bwd_ex(*args, stream), or its atomic-free form (one partial per wavefront's row range, summed in range order)."""
-        if self.det:
-            wp, wb, keep = _det_ws(self.dev, "hgt_node_update_bwd_det", self.NQ, self.dout, self.T)
-            check(self.lib.hgt_node_update_bwd_det(*args, wp, wb, _stream()), "hgt_node_update_bwd_det")
-        else:
-            check(self.lib.hgt_node_update_bwd_ex(*args, _stream()), "hgt_node_update_bwd_ex")
+        _reduce_call(self.det, self.dev, "hgt_node_update_bwd_ex", (self.NQ, self.dout, self.T), *args, det_name="hgt_node_update_bwd_det")
 
     # == forward steps (the message path, conv.py:60-111, is shared by both layers) ==========================================
     def relation_images(self, p):
@@ -481,14 +472,9 @@ class _Step:
         d_lnw, d_lnb = self._ln_grads()
         d_trans, dx_skip = self.new(N, dout), self.new(N, din)
         d_alpha = self.new(T, zero=True)
-        if self.det:
-            self.node_update_bwd(_ptr(gout), _ptr(s.trans), _ptr(s.x), din, _ptr(self.plan.node_type), _ptr(s.skip), _ptr(s.ln_w),
-                                 int(self.use_norm), 0, _ptr(s.m1), N, dout, T, _ptr(d_trans), _ptr(dx_skip), din, _ptr(d_alpha), _ptr(d_lnw),
-                                 _ptr(d_lnb))
-        else:
-            check(self.lib.hgt_node_update_bwd(_ptr(gout), _ptr(s.trans), _ptr(s.x), din, _ptr(self.plan.node_type), _ptr(s.skip), _ptr(s.ln_w),
-                                               int(self.use_norm), _ptr(s.m1), N, dout, T, _ptr(d_trans), _ptr(dx_skip), din, _ptr(d_alpha),
-                                               _ptr(d_lnw), _ptr(d_lnb), _stream()), "hgt_node_update_bwd")
+        self.node_update_bwd(_ptr(gout), _ptr(s.trans), _ptr(s.x), din, _ptr(self.plan.node_type), _ptr(s.skip), _ptr(s.ln_w),
+                             int(self.use_norm), 0, _ptr(s.m1), N, dout, T, _ptr(d_trans), _ptr(dx_skip), din, _ptr(d_alpha), _ptr(d_lnw),
+                             _ptr(d_lnb))
         alpha = torch.sigmoid(s.skip)
         d_skip = d_alpha * alpha * (1.0 - alpha)
         dagg, d_w_a, d_b_a = self.a_linear_bwd(s, d_trans, gelu=True)

@@ -359,7 +359,7 @@ def test_training_path_mid_size_sampled(case):
     from pyhgt_amd import DenseHGTConv
     name, conv, T, R, H, d, N, E, use_norm, use_RTE, gk, (rpw, ipw, gather) = case
     # the branch predicates: node_update_bwd_impl (rows per wavefront) and LaunchOuter::run (relation-outer items) of
-    # csrc/hgt_backward.hip, autograd.spmm_takes_items over the (row stride, first column) of a layer's gather passes: agg, dQ | dK | dV
+    # csrc/hgt_bwd_*.hip, autograd.spmm_takes_items over the (row stride, first column) of a layer's gather passes: agg, dQ | dK | dV
     dp = _lib.layout_for(d, H).d_pad
     assert (32 if N >= 65536 else (8 if N >= 16384 else 2)) == rpw
     assert (2 if _max_items(N, E, T, R) < 16384 else 16) == ipw

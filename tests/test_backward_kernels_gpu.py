@@ -55,7 +55,7 @@ def _randn(shape, g):
 # hgt_node_update_bwd / hgt_node_update_bwd_ex
 # ------------------------------------------------------------------------------------------------------------------------------
 def nub_rows_per_wave(n_rows):
-    # mirrors node_update_bwd_impl of pyhgt_amd/csrc/hgt_backward.hip
+    # mirrors nub_plan of pyhgt_amd/csrc/hgt_bwd_update.hip
     return 32 if n_rows >= 65536 else (8 if n_rows >= 16384 else 2)
 
 
@@ -208,12 +208,12 @@ def _to_edge_ids(plan, sorted_vals, T, R):
 # hgt_relation_outer
 # ------------------------------------------------------------------------------------------------------------------------------
 def outer_items_per_wave_factor(max_items):
-    # mirrors LaunchOuter::run of pyhgt_amd/csrc/hgt_backward.hip: 2 (R + 1) items per wavefront below 16 384 items, else 16 (R + 1)
+    # mirrors outer_items_per_wave of pyhgt_amd/csrc/hgt_bwd_outer.hip: 2 (R + 1) items per wavefront below 16 384 items, else 16 (R + 1)
     return 2 if max_items < 16384 else 16
 
 
 def outer_form(lay):
-    # mirrors hgt_relation_outer + LaunchOuter::run of hgt_backward.hip: the split of a head over lanes
+    # mirrors outer_lane_split of hgt_bwd_outer.hip: the split of a head over lanes
     lph = 64 // lay.heads
     vec, l2 = lay.dk_pad // lph, lph
     while vec * lay.dk_pad > 128 and vec > 1 and l2 * 2 <= 64:

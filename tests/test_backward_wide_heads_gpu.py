@@ -28,8 +28,8 @@ _grads_close = BG._grads_close
 # hgt_relation_outer_wide
 # ------------------------------------------------------------------------------------------------------------------------------
 def wide_items_per_workgroup_factor(max_items):
-    # mirrors hgt_relation_outer_wide (pyhgt_amd/csrc/hgt_backward.hip): 8 (R + 1) items per workgroup below 16 384 plan items, else
-    # 64 (R + 1) -- four wavefronts x the 2 / 16 of LaunchOuter::run
+    # mirrors outer_wide_items_per_wg (pyhgt_amd/csrc/hgt_bwd_outer.hip): 8 (R + 1) items per workgroup below 16 384 plan items, else
+    # 64 (R + 1) -- four wavefronts x the 2 / 16 of outer_items_per_wave
     return 8 if max_items < 16384 else 64
 
 

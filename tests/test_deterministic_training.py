@@ -253,13 +253,15 @@ def _hipcc():
 
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc is absent")
 def test_no_float_atomics_and_no_scratch_in_the_det_kernels(tmp_path):
-    """csrc/hgt_backward.hip -> gfx950 assembly with the Makefile's flags (as tools/lab/isa.sh does); every kernel whose name
-    carries k_det_ must be free of global / flat / buffer atomics and of scratch."""
-    out = tmp_path / "hgt_backward.s"
+    """csrc/hgt_bwd_{update,wgrad,outer}.hip -> gfx950 assembly with the Makefile's flags (as tools/lab/isa.sh does), taken together;
+    every kernel whose name carries k_det_ must be free of global / flat / buffer atomics and of scratch."""
     csrc = os.path.join(ROOT, "pyhgt_amd", "csrc")
-    subprocess.run([_hipcc()] + _makefile_flags() + ["-S", "--cuda-device-only", "hgt_backward.hip", "-o", str(out)], cwd=csrc, check=True,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = out.read_text()
+    asm = ""
+    for part in ("hgt_bwd_update", "hgt_bwd_wgrad", "hgt_bwd_outer"):
+        out = tmp_path / (part + ".s")
+        subprocess.run([_hipcc()] + _makefile_flags() + ["-S", "--cuda-device-only", part + ".hip", "-o", str(out)], cwd=csrc, check=True,
+                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        asm += out.read_text()
     # kernel bodies: "<symbol>:" ... ".Lfunc_end"; resources: the .amdhsa_kernel blocks / metadata
     bodies = dict(re.findall(r"^(_Z\w*k_det_\w+):[^\n]*\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M))
     expected = ["k_det_node_update_bwd", "k_det_node_update_bwd_wide", "k_det_reduce", "k_det_typed_wgrad", "k_det_typed_wgrad_x3",
@@ -273,7 +275,7 @@ def test_no_float_atomics_and_no_scratch_in_the_det_kernels(tmp_path):
         assert not re.search(r"^\s*scratch_(load|store)", body, flags=re.M), "%s touches scratch" % sym
         desc = re.search(r"\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % re.escape(sym), asm, flags=re.S).group(1)
         assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", desc), "%s has a private segment" % sym
-    # the yardstick bites: the atomic forms in the same file do execute float atomics
+    # the yardstick bites: the atomic forms in the same files do execute float atomics
     atomic_bodies = dict(re.findall(r"^(_Z\w*k_typed_wgrad\w*):[^\n]*\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M))
     assert atomic_bodies and all(re.search(r"global_atomic_add_f32|global_atomic_pk_add", b) for b in atomic_bodies.values())
     # budgets of the wide outer product: 112 / 100 VGPRs, 40 KiB of LDS, like the kernel it mirrors
