@@ -258,6 +258,10 @@ int hgt_relation_pack(const float* relation_att, const float* relation_msg, cons
  *                      hgt_edge_softmax is only needed to materialise att for hgt_att_export.
  *   hgt_att_export     att_out[original edge id][h] = att[p][h]   (self.att, conv.py:108)
  * rte_k / rte_v: [n_types*240][d_pad] tables or NULL.
+ * n_edges == 0: the per-edge arrays (logits, logits_att, att_sorted, att_out; in the backward pass att, d_att, d_logits,
+ * by_edge_id, sorted; the weights of hgt_edge_spmm / hgt_relation_outer) may be NULL -- an empty array has no address -- and
+ * hgt_edge_logits*, hgt_edge_softmax, hgt_att_export, hgt_edge_softmax_bwd and hgt_edge_gather_sorted launch nothing.  With edges a
+ * NULL per-edge array is HGT_ERR_INVALID_ARG, and every other argument is checked with or without edges.
  * ---------------------------------------------------------------------------------------------- */
 int hgt_edge_logits(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations,
                     int32_t n_heads, int32_t dk_pad, const float* Q, const float* K, const float* rte_k,
@@ -476,6 +480,9 @@ int hgt_edge_aggregate_update_range(const void* plan, int64_t n_nodes, int64_t n
  *   hgt_typed_wgrad      out[g][m][n] += sum_{rows p of group g} A[rows[p]][m] B[rows[p]][n]   (exact fp32 MFMA; fp32 atomics)
  *   hgt_typed_colsum     out[g][c]    += sum_{rows p of group g} A[rows[p]][c]                  (bias gradients)
  * Accumulating outputs (+=) must be zeroed by the caller.
+ * n_edges == 0 (a sampled batch without edges): att / d_att / d_logits of hgt_edge_softmax_bwd and by_edge_id / sorted of
+ * hgt_edge_gather_sorted may be NULL like the weights of hgt_edge_spmm and hgt_relation_outer; both return HGT_OK without a launch
+ * (rho is per node and required).
  * ---------------------------------------------------------------------------------------------- */
 int hgt_edge_spmm(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations, int32_t n_heads,
                   int32_t dk_pad, const float* weights, const float* rows, const float* rte_rows, const float* f_p,

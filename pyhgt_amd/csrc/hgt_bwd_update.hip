@@ -402,7 +402,8 @@ extern "C" int hgt_mul_inplace(float* x, const float* m, int64_t n, void* stream
 
 extern "C" int hgt_edge_softmax_bwd(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, const float* att,
                                     const float* d_att, const float* rho, int64_t ld_rho, float* d_logits, void* stream) {
-    if (!plan || !att || !d_att || !rho || !d_logits || H <= 0) return HGT_ERR_INVALID_ARG;
+    // E == 0: the per-edge arrays att / d_att / d_logits may be NULL (rho is per node)
+    if (!plan || !rho || (E > 0 && (!att || !d_att || !d_logits)) || H <= 0) return HGT_ERR_INVALID_ARG;
     if (E == 0) return HGT_OK;
     HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
     k_edge_softmax_bwd<<<nblk(E * H, 256), 256, 0, (hipStream_t)stream>>>(pv.edst, att, d_att, rho, ld_rho, d_logits, E, H);
@@ -412,7 +413,7 @@ extern "C" int hgt_edge_softmax_bwd(const void* plan, int64_t N, int64_t E, int3
 
 extern "C" int hgt_edge_gather_sorted(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, const float* by_edge_id,
                                       float* sorted, void* stream) {
-    if (!plan || !by_edge_id || !sorted || H <= 0) return HGT_ERR_INVALID_ARG;
+    if (!plan || (E > 0 && (!by_edge_id || !sorted)) || H <= 0) return HGT_ERR_INVALID_ARG;      // E == 0: both may be NULL
     if (E == 0) return HGT_OK;
     HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
     k_gather_sorted<<<nblk(E * H, 256), 256, 0, (hipStream_t)stream>>>(pv.eid, by_edge_id, sorted, E, H);

@@ -263,7 +263,8 @@ static int mfma_logits_split_for(int vec_full, int lph_full) {
 static int edge_logits_impl(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad, const float* Q,
                             const float* K, const float* rte_k, const float* att_t, float* logits, int rel_lo, int rel_hi, void* stream,
                             const void* att_frag = nullptr, int frag_f16 = 0, int item_lo = 0, int item_hi = -1) {
-    if (!plan || !Q || !K || !att_t || !logits || H <= 0 || 64 % H != 0 || dk_pad <= 0) return HGT_ERR_INVALID_ARG;
+    // (the per-edge array may be NULL on an edgeless graph, as hgt_edge_spmm's weights may: an empty tensor has no address)
+    if (!plan || !Q || !K || !att_t || (E > 0 && !logits) || H <= 0 || 64 % H != 0 || dk_pad <= 0) return HGT_ERR_INVALID_ARG;
     if (rel_lo < 0 || rel_hi > R + 1 || rel_lo > rel_hi) return HGT_ERR_INVALID_ARG;
     if (E == 0) return HGT_OK;
     const int lph = 64 / H;
@@ -318,7 +319,7 @@ extern "C" int hgt_edge_logits_range(const void* plan, int64_t N, int64_t E, int
 
 extern "C" int hgt_edge_softmax(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, float* logits_att,
                                 void* stream) {
-    if (!plan || !logits_att || H <= 0) return HGT_ERR_INVALID_ARG;
+    if (!plan || (E > 0 && !logits_att) || H <= 0) return HGT_ERR_INVALID_ARG;      // E == 0: logits_att may be NULL
     if (E == 0 || N == 0) return HGT_OK;
     HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
     const int64_t threads = N * H;
@@ -330,7 +331,8 @@ extern "C" int hgt_edge_softmax(const void* plan, int64_t N, int64_t E, int32_t 
 
 extern "C" int hgt_att_export(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, const float* att_sorted,
                               float* att_out, int32_t H_out, void* stream) {
-    if (!plan || !att_sorted || !att_out || H <= 0 || H_out <= 0 || H_out > H) return HGT_ERR_INVALID_ARG;
+    // E == 0: att_sorted / att_out may be NULL
+    if (!plan || (E > 0 && (!att_sorted || !att_out)) || H <= 0 || H_out <= 0 || H_out > H) return HGT_ERR_INVALID_ARG;
     if (E == 0) return HGT_OK;
     HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
     k_att_export<<<(unsigned)((E * H + 255) / 256), 256, 0, (hipStream_t)stream>>>(pv.eid, att_sorted, att_out, E, H, H_out);
