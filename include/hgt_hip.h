@@ -781,6 +781,91 @@ int hgt_stack_sorted(const int32_t* src, const int32_t* dst, const int32_t* edge
                      int32_t* rel_ptr_out, int32_t* type_off_out, int32_t* node_map, int32_t* edge_map, void* tmp,
                      uint64_t tmp_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Device sampler (csrc/hgt_sampler.hip; pyhgt_amd/sampler.py): HGSampling, pyHGT/data.py:87-210, over a graph that is resident in
+ * device memory.  One entry point per step of the reference so that each can be tested on its own; the host loop that strings them
+ * together is sample_subgraph_device.  Added under ABI 8 (new symbols only).
+ *
+ * hgt_sampler_triple  one meta triple (target type, source type, relation) as a CSR by target id: indptr int32[n_tgt + 1], src and
+ *                     time int32[indptr[n_tgt]], neighbours in the order of the reference's adjacency dict; time ==
+ *                     HGT_SAMPLER_TIME_NONE stands for None (data.py:125: the neighbour inherits the target's time).  rel_id is the
+ *                     relation's id in the result (edge_dict of data.py:237); the induce calls need the triples ordered by
+ *                     (rel_id, tgt_type) and every rel_id below n_relations - 1, which is `self`.
+ * hgt_sampler_type    the state of one node type: score u64[n_nodes] (32.32 fixed point), stamp u64[n_nodes] ((step << 32) |
+ *                     (time ^ 0x80000000)), serial int32[n_nodes] (-1 = not sampled), sampled int32[cap_sampled] (ids in serial
+ *                     order), cand int32[cap_cand] (budget keys), counts int32[4] = {sampled, first serial of the newest batch,
+ *                     candidates, overflow flag}.  Before the first call: score = stamp = counts = 0, serial = -1;
+ *                     hgt_sampler_reset restores that by walking the two lists.  cap_sampled, cap_cand <= n_nodes.
+ * Both tables are HOST arrays of at most HGT_SAMPLER_MAX_TYPES / HGT_SAMPLER_MAX_TRIPLES entries (they travel as kernel
+ * arguments) whose pointer members are device pointers.  Random words: Philox4x32-10 under key = seed (the generator of
+ * hgt_dropout_*, other counter words).  `step` numbers the calls of one batch; it enters the stamps (a later step's time replaces an
+ * earlier one's, inside a step the largest time wins) and the random words.
+ *
+ *   hgt_sampler_seed        data.py:135-137: nodes ids[0..n) with times[0..n) become serials 0..n-1 of `type`.
+ *   hgt_sampler_add_budget  data.py:112-130 for the newest batch of `type` (at most max_new nodes) over every triple into it.  A row
+ *                           of more than sampled_number neighbours keeps those with the smallest (word, position), word keyed by
+ *                           (position, target id, step, 0x10000 + index of the triple in the table).  A kept neighbour is skipped
+ *                           when its (inherited) time exceeds max_time (has_max_time != 0) or when it is sampled; otherwise
+ *                           score += round(2^32 / min(degree, sampled_number)), stamp = max(stamp, (step, time)), and its first
+ *                           touch appends it to cand.  One wavefront per row up to HGT_SAMPLER_HUB_DEG neighbours, one
+ *                           1024-thread workgroup per longer row.  hub: int32[hub_entries >= max_new * triples into type + 1].
+ *   hgt_sampler_select      data.py:151-172: the min(sampled_number, candidates) candidates of `type` with the smallest
+ *                           (key, node id), key = -log(u) / s^2 in fp32, s = score * 2^-32, u = ((word >> 8) + 0.5) * 2^-24, word
+ *                           keyed by (node id, type, step, 0x20000); they get the next serials in that order and leave cand.
+ *                           keys: u64[cap_cand], tmp: int32[tmp_entries >= cap_cand].  sampled_number <= HGT_SAMPLER_MAX_NUMBER.
+ *   hgt_sampler_induce_slots  HOST only: the number of row slots of the induce calls = sum over the triples of their target type's
+ *                           cap_sampled.
+ *   hgt_sampler_induce_count  data.py:183-209, first pass: rowoff int32[n_entries >= slots + 1] and hub (same size) are scratch that
+ *                           the fill call reads again; out: type_off_out int32[T + 1], rel_ptr_out int32[R + 1] and sizes_out
+ *                           int32[T + M + 2] = {nodes per type, edges per triple, overflow flag, non-self edges} -- the one array
+ *                           the host reads per batch.
+ *   hgt_sampler_induce_fill   second pass: src_out / dst_out / time_out int32[n_edges] (n_edges = non-self edges + n_nodes),
+ *                           relation-major, inside a relation by global target id, a target's neighbours in adjacency order, the
+ *                           `self` edges last; edge time = time[tgt] - time[src] + 120 (data.py:250).  node_time_out and
+ *                           node_id_out int32[n_nodes]: time and original id of every sampled node in global order.
+ *   hgt_sampler_reset       clears the state entries that the sampled and candidate lists name, then the counts.
+ * No float atomics; every store is bounds-checked against the capacities in the tables.  Bad arguments -> a negative code and no
+ * launch (NULL table or array, negative size: HGT_ERR_INVALID_ARG; scratch too small: HGT_ERR_WORKSPACE; more types, triples or
+ * a larger sampled_number than the limits: HGT_ERR_UNSUPPORTED).
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_SAMPLER_MAX_TYPES 16
+#define HGT_SAMPLER_MAX_TRIPLES 48
+#define HGT_SAMPLER_MAX_NUMBER 1024
+#define HGT_SAMPLER_HUB_DEG 512
+#define HGT_SAMPLER_TIME_NONE INT32_MIN
+typedef struct hgt_sampler_type {
+    uint64_t* score;
+    uint64_t* stamp;
+    int32_t* serial;
+    int32_t* sampled;
+    int32_t* cand;
+    int32_t* counts;
+    int32_t n_nodes, cap_sampled, cap_cand, reserved;
+} hgt_sampler_type;
+typedef struct hgt_sampler_triple {
+    const int32_t* indptr;
+    const int32_t* src;
+    const int32_t* time;
+    int32_t tgt_type, src_type, rel_id, reserved;
+} hgt_sampler_triple;
+int hgt_sampler_seed(const hgt_sampler_type* types_host, int32_t n_types, int32_t type, const int32_t* ids, const int32_t* times,
+                     int32_t n, int32_t step, void* stream);
+int hgt_sampler_add_budget(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                           int32_t n_triples, int32_t type, int32_t step, int32_t sampled_number, int32_t max_new,
+                           int32_t has_max_time, int32_t max_time, uint64_t seed, int32_t* hub, int64_t hub_entries, void* stream);
+int hgt_sampler_select(const hgt_sampler_type* types_host, int32_t n_types, int32_t type, int32_t step, int32_t sampled_number,
+                       uint64_t seed, uint64_t* keys, int32_t* tmp, int64_t tmp_entries, void* stream);
+int hgt_sampler_induce_slots(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                             int32_t n_triples, int64_t* n_slots_host);
+int hgt_sampler_induce_count(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                             int32_t n_triples, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries,
+                             int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out, void* stream);
+int hgt_sampler_induce_fill(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                            int32_t n_triples, int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries,
+                            const int32_t* type_off, int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out,
+                            int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out, void* stream);
+int hgt_sampler_reset(const hgt_sampler_type* types_host, int32_t n_types, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

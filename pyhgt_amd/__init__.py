@@ -6,6 +6,7 @@ names, forward signature) backed by hand-written HIP kernels behind a C ABI (inc
 from .conv import HGTConv, DenseHGTConv, GeneralConv, RelTemporalEncoding, GraphPlan, install_into  # noqa: F401
 from .model import GNN, Classifier, Matcher  # noqa: F401
 from .autograd import set_deterministic, set_recompute  # noqa: F401
+from .sampler import DeviceHeteroGraph, sample_subgraph_device, sample_subgraph_host  # noqa: F401
 
 __all__ = ["HGTConv", "DenseHGTConv", "GeneralConv", "RelTemporalEncoding", "GraphPlan", "install_into", "GNN", "Classifier", "Matcher",
-           "set_deterministic", "set_recompute"]
+           "set_deterministic", "set_recompute", "DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host"]

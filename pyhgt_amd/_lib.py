@@ -35,6 +35,11 @@ HGT_LINEAR_TANH = 0x1000
 HGT_FEATURE_LAB_KERNELS = 1
 HGT_FEATURE_DETERMINISTIC_TRAINING = 2
 HGT_STACK_MAX_PIECES = 256
+HGT_SAMPLER_MAX_TYPES = 16
+HGT_SAMPLER_MAX_TRIPLES = 48
+HGT_SAMPLER_MAX_NUMBER = 1024
+HGT_SAMPLER_HUB_DEG = 512
+HGT_SAMPLER_TIME_NONE = -2 ** 31
 
 
 class HgtLayout(C.Structure):
@@ -77,6 +82,16 @@ class HgtConvArgs(C.Structure):
         ("item_begin", C.c_int32), ("item_end", C.c_int32),
         ("proj_c24", C.c_void_p), ("proj_c24_row0", C.c_int64),
     ]
+
+
+class HgtSamplerType(C.Structure):
+    _fields_ = [("score", C.c_void_p), ("stamp", C.c_void_p), ("serial", C.c_void_p), ("sampled", C.c_void_p), ("cand", C.c_void_p),
+                ("counts", C.c_void_p), ("n_nodes", C.c_int32), ("cap_sampled", C.c_int32), ("cap_cand", C.c_int32), ("reserved", C.c_int32)]
+
+
+class HgtSamplerTriple(C.Structure):
+    _fields_ = [("indptr", C.c_void_p), ("src", C.c_void_p), ("time", C.c_void_p), ("tgt_type", C.c_int32), ("src_type", C.c_int32),
+                ("rel_id", C.c_int32), ("reserved", C.c_int32)]
 
 
 ABI_VERSION = 8          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
@@ -196,6 +211,14 @@ SIGNATURES = {
     "hgt_stack_tmp_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_u64)]),
     "hgt_stack_sorted": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _u64, _vp]),
+    # device sampler (csrc/hgt_sampler.hip): every call starts with (types_host, n_types[, triples_host, n_triples])
+    "hgt_sampler_seed": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "hgt_sampler_add_budget": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _i64, _vp]),
+    "hgt_sampler_select": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _u64, _vp, _vp, _i64, _vp]),
+    "hgt_sampler_induce_slots": (C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(_i64)]),
+    "hgt_sampler_induce_count": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hgt_sampler_induce_fill": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hgt_sampler_reset": (C.c_int, [_vp, _i32, _vp]),
 }
 
 _lib = None

@@ -15,29 +15,9 @@
 // three XORs and two key additions: ~70 integer instructions per 16 bytes against 2 (apply) / 1 (mask) memory instructions.
 // Whether that leaves the kernel HBM-bound has not been measured here; tools/bench_train.py times it against hgt_mul_inplace.
 #include "hgt_common.h"
+#include "hgt_philox.h"      // philox4x32_10(counter, k0, k1), shared with hgt_sampler.hip
 
 namespace {
-
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;      // round multipliers
-constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;      // key increments (golden ratio, sqrt(3) - 1)
-
-struct Philox4 { uint32_t w[4]; };
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint64_t counter, uint32_t k0, uint32_t k1) {
-    uint32_t c0 = (uint32_t)counter, c1 = (uint32_t)(counter >> 32), c2 = 0u, c3 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0, p1 = (uint64_t)PHILOX_M1 * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += PHILOX_W0;
-        k1 += PHILOX_W1;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
 
 // APPLY: x[i] *= factor_i, else x[i] = factor_i.  Grid-stride over the groups of four elements; n_groups = ceil(n / 4).
 // keep_all: keep >= 1 (every word passes; thr cannot hold 2^32).  vec_ok: x is 16-byte aligned.

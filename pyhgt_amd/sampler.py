@@ -1,0 +1,526 @@
+"""HGSampling on the device (csrc/hgt_sampler.hip): the producer of the sampled batches.
+
+The reference draws a training batch with `sample_subgraph` + `to_torch` (pyHGT/data.py:87-256): Python dict walking on the CPU,
+seconds per batch.  Here the graph lives in device memory (`DeviceHeteroGraph`: one CSR by target id per meta triple, one feature
+matrix per type) and `sample_subgraph_device` turns seed nodes into the `_DeviceGraph` that `to_device_graph` would have built --
+the 7-tuple of `to_torch` with `.sorted`, `.plan` and `.indxs` -- with one host synchronisation per batch (the sizes of the
+result) and no host copy of an index.  `sample_subgraph_host` is its numpy sibling with the same definition: the same Philox words,
+the same fixed-point scores, selection keys in float64.
+
+The definition ("Device sampler", lists where it departs from the reference):
+
+  step     seeds of type j (get_types() order): step j;  layer l, type j: step T * (1 + l) + j.  Types are visited in get_types() order.
+  budget   data.py:112-130 per newly sampled node and meta triple into its type: all neighbours if degree <= sampled_number, else the
+           sampled_number neighbours with the smallest (Philox word, position); a neighbour whose time is None inherits the target's;
+           neighbours newer than max_time or already sampled are skipped; the others get score += round(2^32 / len(subset)) (u64,
+           32.32 fixed point) and stamp = max(stamp, (step << 32) | (time ^ 0x80000000)).
+  select   data.py:151-172: the min(sampled_number, candidates) candidates with the smallest (key, node id),
+           key = -log(u) / s^2, s = score * 2^-32, u = ((word >> 8) + 0.5) * 2^-24 (exponential keys of Efraimidis and Spirakis: the
+           ordered sample is distributed like successive weighted sampling without replacement, i.e. like
+           np.random.choice(p = score^2 / sum, replace = False)).  Serials follow that order; the node's time is its stamp's.
+  induce   data.py:183-209, 240-250: relation-major edges, inside a relation by global target id, a target's neighbours in adjacency
+           order, `self` edges last; edge_time = time[tgt] - time[src] + 120.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .conv import GraphPlan
+from .sampled import _DeviceGraph
+
+__all__ = ["DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "philox4x32_10"]
+
+TIME_NONE = _lib.HGT_SAMPLER_TIME_NONE
+_SUBSET_TAG, _SELECT_TAG = 0x10000, 0x20000
+_MASK = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(c0, c1, c2, c3, seed):
+    """Philox4x32-10 over numpy arrays (csrc/hgt_philox.h bit for bit): counter words c0..c3 (broadcast against each other), key =
+    (seed & 0xffffffff, seed >> 32) -> the four uint32 output words."""
+    c = [np.asarray(v, dtype=np.uint64) & _MASK for v in np.broadcast_arrays(c0, c1, c2, c3)]
+    c0, c1, c2, c3 = c
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
+    m0, m1, w0, w1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c0, m1 * c2
+        n0, n2 = (p1 >> s32) ^ c1 ^ k0, (p0 >> s32) ^ c3 ^ k1
+        c1, c3, c0, c2 = p1 & _MASK, p0 & _MASK, n0, n2
+        k0, k1 = (k0 + w0) & _MASK, (k1 + w1) & _MASK
+    return tuple(v.astype(np.uint32) for v in (c0, c1, c2, c3))
+
+
+def _bias(t):
+    return (np.asarray(t, dtype=np.int64) + 2 ** 31).astype(np.uint64)
+
+
+def _stamp_time(stamp):
+    return ((np.asarray(stamp, dtype=np.uint64) & _MASK).astype(np.int64) - 2 ** 31).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the graph
+class DeviceHeteroGraph:
+    """A heterogeneous graph resident on a device (or, device=None, on the host only -- what `sample_subgraph_host` needs).
+
+    types       node type names in get_types() order
+    triples     [(target type, source type, relation)] without `self`, ordered by (relation id, target type); the position in this
+                list is the triple's index in the random-word keys
+    csr         per triple (indptr int32[n_tgt + 1], src int32[], time int32[]), TIME_NONE = the reference's None
+    features    per type a float32 [n_type, in_dim] matrix (or None for a type without nodes)
+    It answers get_types() / get_meta_graph() like the reference's Graph, so it can stand in for `graph` in to_torch-like calls."""
+
+    def __init__(self, types, meta, n_nodes, csr, features=None, device=None):
+        self.types = list(types)
+        T = len(self.types)
+        if not 1 <= T <= _lib.HGT_SAMPLER_MAX_TYPES:
+            raise ValueError("pyhgt_amd: 1..%d node types, got %d" % (_lib.HGT_SAMPLER_MAX_TYPES, T))
+        meta = [tuple(m) for m in meta]
+        if len(meta) != len(csr):
+            raise ValueError("pyhgt_amd: one CSR per meta triple")
+        keep = [i for i, m in enumerate(meta) if m[2] != "self"]                    # data.py:116
+        self.meta = [meta[i] for i in keep]
+        if len(self.meta) > _lib.HGT_SAMPLER_MAX_TRIPLES:
+            raise ValueError("pyhgt_amd: at most %d meta triples" % _lib.HGT_SAMPLER_MAX_TRIPLES)
+        self.edge_dict = {m[2]: i for i, m in enumerate(self.meta)}                 # data.py:237-238
+        self.edge_dict["self"] = len(self.edge_dict)
+        self.n_nodes = [int(n_nodes[t]) for t in self.types]
+        tid = {t: i for i, t in enumerate(self.types)}
+        order = sorted(range(len(keep)), key=lambda i: (self.edge_dict[self.meta[i][2]], tid[self.meta[i][0]]))
+        self.triples = [self.meta[i] for i in order]
+        self.tri_types = [(tid[tt], tid[st], self.edge_dict[rel]) for tt, st, rel in self.triples]
+        self.csr = []
+        for i in order:
+            indptr, src, time = csr[keep[i]]
+            tt, st, _ = self.meta[i]
+            indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+            src = np.ascontiguousarray(src, dtype=np.int32)
+            time = np.full(src.shape, TIME_NONE, np.int32) if time is None else np.ascontiguousarray(time, dtype=np.int32)
+            if indptr.shape != (self.n_nodes[tid[tt]] + 1,) or indptr[0] != 0 or np.any(np.diff(indptr) < 0) or indptr[-1] != src.size:
+                raise ValueError("pyhgt_amd: indptr of %r is not a CSR over the target type's nodes" % (self.meta[i],))
+            if time.shape != src.shape or (src.size and (src.min() < 0 or src.max() >= self.n_nodes[tid[st]])):
+                raise ValueError("pyhgt_amd: neighbour ids / times of %r out of range" % (self.meta[i],))
+            self.csr.append((indptr, src, time))
+        self.features_host = None if features is None else [None if features.get(t) is None else features[t] for t in self.types]
+        self.device = None if device is None else torch.device(device)
+        self._host_state = None
+        self._dev_state = {}
+        self._dev_nodes = None
+        if self.device is not None:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            self.csr_dev = [tuple(up(a) for a in c) for c in self.csr]
+            self.features = None
+            if features is not None:
+                self.features = []
+                for t, f in zip(self.types, self.features_host):
+                    f = None if f is None else torch.as_tensor(f, dtype=torch.float32).to(self.device).contiguous()
+                    if f is not None and (f.dim() != 2 or f.size(0) != self.n_nodes[tid[t]]):
+                        raise ValueError("pyhgt_amd: features[%r] must be [n_nodes, in_dim]" % t)
+                    self.features.append(f)
+
+    @classmethod
+    def from_csr(cls, types, meta, n_nodes, csr, features=None, device=None):
+        """types: names; meta: [(target type, source type, relation)]; n_nodes: {type: count}; csr: per triple (indptr, src, time)
+        with time None or an int array in which TIME_NONE marks a missing time; features: {type: [n, in_dim]}."""
+        return cls(types, meta, n_nodes, csr, features, device)
+
+    @classmethod
+    def from_reference_graph(cls, graph, features, device=None, n_nodes=None):
+        """One walk over the reference's `graph.edge_list[target_type][source_type][relation][target_id][source_id] = time` into the
+        CSRs, neighbours in the dict's order, a relation named `self` ignored (data.py:116).  `features`: {type: [n_type, in_dim]}, built
+        once by the caller (e.g. feature_OAG over all ids); it also fixes the node counts unless n_nodes gives them."""
+        types = list(graph.get_types())
+        n_nodes = {t: (len(features[t]) if features.get(t) is not None else 0) for t in types} if n_nodes is None else dict(n_nodes)
+        meta, csr = [], []
+        for tt in graph.edge_list:
+            for st in graph.edge_list[tt]:
+                for rel in graph.edge_list[tt][st]:
+                    if rel == "self":
+                        continue
+                    adj = graph.edge_list[tt][st][rel]
+                    deg = np.zeros(n_nodes[tt] + 1, np.int64)
+                    for v, nb in adj.items():
+                        deg[int(v) + 1] = len(nb)
+                    indptr = np.cumsum(deg)
+                    src, time = np.empty(indptr[-1], np.int32), np.empty(indptr[-1], np.int32)
+                    for v, nb in adj.items():
+                        b = indptr[int(v)]
+                        src[b:b + len(nb)] = list(nb.keys())
+                        time[b:b + len(nb)] = [TIME_NONE if x is None else int(x) for x in nb.values()]
+                    meta.append((tt, st, rel))
+                    csr.append((indptr, src, time))
+        return cls(types, meta, n_nodes, csr, features, device)
+
+    def get_types(self):
+        return list(self.types)
+
+    def get_meta_graph(self):
+        return list(self.meta)
+
+
+def _seed_arrays(dgraph, inp):
+    """inp = {type: [[id, time], ...]} (data.py:135-137) -> per type (ids int32, times int32), in get_types() order."""
+    out = []
+    for t, n in zip(dgraph.types, dgraph.n_nodes):
+        a = np.asarray(inp.get(t, []), dtype=np.int64).reshape(-1, 2)
+        if a.shape[0] and (a[:, 0].min() < 0 or a[:, 0].max() >= n):
+            raise IndexError("pyhgt_amd: seed ids of %r outside [0, %d)" % (t, n))
+        if np.unique(a[:, 0]).size != a.shape[0]:
+            raise ValueError("pyhgt_amd: seed ids of %r repeat" % t)
+        out.append((a[:, 0].astype(np.int32), a[:, 1].astype(np.int32)))
+    unknown = set(inp) - set(dgraph.types)
+    if unknown:
+        raise KeyError("pyhgt_amd: seed types %r are not node types of the graph" % sorted(unknown))
+    return out
+
+
+def _capacities(dgraph, n_seed, depth, sn):
+    """Static list capacities: sampled nodes per type <= seeds + depth * sampled_number, candidates <= sampled targets * sampled_number
+    summed over the triples whose source is the type; both capped by the type's node count."""
+    T = len(dgraph.types)
+    reach = [any(st == t for _, st, _ in dgraph.tri_types) for t in range(T)]
+    cap_s = [min(dgraph.n_nodes[t], n_seed[t] + (depth * sn if reach[t] else 0)) for t in range(T)]
+    cap_c = [min(dgraph.n_nodes[t], sum(cap_s[tt] * sn for tt, st, _ in dgraph.tri_types if st == t)) for t in range(T)]
+    return cap_s, cap_c
+
+
+def _check_args(dgraph, sampled_depth, sampled_number):
+    if sampled_depth < 0 or not 1 <= sampled_number <= _lib.HGT_SAMPLER_MAX_NUMBER:
+        raise ValueError("pyhgt_amd: sampled_depth >= 0 and 1 <= sampled_number <= %d" % _lib.HGT_SAMPLER_MAX_NUMBER)
+
+
+# ---------------------------------------------------------------------------------------------------------------- numpy rule
+def _flat_rows(indptr, targets):
+    """positions of all neighbours of `targets` (in order) -> (flat positions, row index of each, degree per row)"""
+    beg = indptr[targets].astype(np.int64)
+    deg = indptr[np.asarray(targets) + 1].astype(np.int64) - beg
+    total = int(deg.sum())
+    row = np.repeat(np.arange(len(targets)), deg)
+    first = np.cumsum(deg) - deg
+    pos = np.arange(total) - first[row]
+    return beg[row] + pos, row, deg, pos
+
+
+def np_budget_contributions(csr, m, targets, target_times, step, sn, max_time, seed, src_serial):
+    """data.py:112-130 for the rows (triple m, target) of one call: -> (source ids, score terms uint64, stamps uint64) of the
+    surviving neighbours, one entry per contribution."""
+    indptr, src, time = csr
+    targets = np.asarray(targets, dtype=np.int64)
+    flat, row, deg, pos = _flat_rows(indptr, targets)
+    keep = np.ones(flat.size, bool)
+    first = np.cumsum(deg) - deg
+    for r in np.nonzero(deg > sn)[0]:                       # rows that draw: the sn smallest (word, position)
+        p = np.arange(deg[r])
+        words = philox4x32_10(p, targets[r], step, _SUBSET_TAG + m, seed)[0]
+        drop = np.lexsort((p, words))[sn:]
+        keep[first[r] + drop] = False
+    flat, row = flat[keep], row[keep]
+    ln = np.minimum(deg, sn)[row]
+    add = (((1 << 33) + ln) // (2 * ln)).astype(np.uint64)
+    s, tm = src[flat].astype(np.int64), time[flat].astype(np.int64)
+    tm = np.where(tm == TIME_NONE, np.asarray(target_times, dtype=np.int64)[row], tm)
+    ok = src_serial[s] < 0
+    if max_time is not None:
+        ok &= tm <= max_time
+    return s[ok], add[ok], (np.uint64(step) << np.uint64(32)) | _bias(tm[ok])
+
+
+def np_apply_budget(score, stamp, s, add, st):
+    """the atomics of add_budget: -> ids touched for the first time (ascending)"""
+    fresh = np.unique(s[score[s] == 0])
+    np.add.at(score, s, add)
+    np.maximum.at(stamp, s, st)
+    return fresh
+
+
+def np_select_keys(ids, score, t, step, seed):
+    """float64 selection keys of the candidates `ids` of type t"""
+    word = philox4x32_10(np.asarray(ids, dtype=np.int64), t, step, _SELECT_TAG, seed)[0]
+    u = ((word >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+    s = score[ids].astype(np.float64) * 2.0 ** -32
+    return -np.log(u) / (s * s)
+
+
+def np_select(ids, score, t, step, seed, sn):
+    """-> the chosen candidates in serial order"""
+    ids = np.asarray(ids, dtype=np.int64)
+    keys = np_select_keys(ids, score, t, step, seed)
+    return ids[np.lexsort((ids, keys))[:min(sn, ids.size)]]
+
+
+def np_induce(dgraph, sampled, times, serial):
+    """data.py:183-209 + 240-250 over the node lists `sampled[t]` (ids in serial order), their times and the serial arrays:
+    -> (src, dst, edge_time, rel_ptr, type_off) in the sorted int32 form."""
+    T, R = len(dgraph.types), len(dgraph.edge_dict)
+    type_off = np.concatenate([[0], np.cumsum([len(sampled[t]) for t in range(T)])]).astype(np.int64)
+    srcs, dsts, tms, per_rel = [], [], [], np.zeros(R, np.int64)
+    for (tt, st, rel), (indptr, src, _) in zip(dgraph.tri_types, dgraph.csr):
+        flat, row, _, _ = _flat_rows(indptr, np.asarray(sampled[tt], dtype=np.int64))
+        s = src[flat].astype(np.int64)
+        ser = serial[st][s].astype(np.int64)
+        ok = ser >= 0
+        srcs.append(ser[ok] + type_off[st])
+        dsts.append(row[ok] + type_off[tt])
+        tms.append(np.asarray(times[tt], dtype=np.int64)[row[ok]] - np.asarray(times[st], dtype=np.int64)[ser[ok]] + 120)
+        per_rel[rel] += int(ok.sum())
+    n = int(type_off[-1])
+    srcs.append(np.arange(n)); dsts.append(np.arange(n)); tms.append(np.full(n, 120, np.int64))
+    per_rel[R - 1] += n
+    rel_ptr = np.concatenate([[0], np.cumsum(per_rel)])
+    cat = lambda a: np.concatenate(a).astype(np.int32)
+    return cat(srcs), cat(dsts), cat(tms), rel_ptr.astype(np.int32), type_off.astype(np.int32)
+
+
+class _HostGraph(tuple):
+    """Result of sample_subgraph_host: the 7-tuple of to_torch (CPU tensors) with `.sorted` (numpy), `.indxs` and `.times`."""
+    sorted = None
+    indxs = None
+    times = None
+    plan = None
+
+
+def _wire_tuple(cls, dgraph, feat, n_per_type, src, dst, etime, rel_ptr, type_off):
+    """the reference's int64 tensors, derived as to_device_graph derives them"""
+    dev = src.device
+    T, R = len(dgraph.types), len(dgraph.edge_dict)
+    N, E = int(sum(n_per_type)), int(src.numel())
+    node_type = torch.repeat_interleave(torch.arange(T, device=dev), torch.as_tensor(n_per_type, dtype=torch.int64, device=dev), output_size=N)
+    edge_type = torch.repeat_interleave(torch.arange(R, device=dev), rel_ptr.long().diff(), output_size=E)
+    edge_index = torch.stack([src.long(), dst.long()], dim=1).t()
+    node_dict, n = {}, 0
+    for i, t in enumerate(dgraph.types):
+        node_dict[t] = [n, i]
+        n += int(n_per_type[i])
+    return cls((feat, node_type, etime.long(), edge_index, edge_type, node_dict, dict(dgraph.edge_dict)))
+
+
+def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, seed):
+    """numpy sibling of `sample_subgraph_device`: the same definition on the host copy of the graph.  Returns a `_HostGraph`."""
+    _check_args(dgraph, sampled_depth, sampled_number)
+    T, sn = len(dgraph.types), int(sampled_number)
+    seeds = _seed_arrays(dgraph, inp)
+    if dgraph._host_state is None:
+        dgraph._host_state = ([np.zeros(n, np.uint64) for n in dgraph.n_nodes], [np.zeros(n, np.uint64) for n in dgraph.n_nodes],
+                              [np.full(n, -1, np.int32) for n in dgraph.n_nodes])
+    score, stamp, serial = dgraph._host_state
+    sampled = [np.zeros(0, np.int64) for _ in range(T)]
+    cand = [np.zeros(0, np.int64) for _ in range(T)]
+
+    def add_budget(t, new, step):
+        times = _stamp_time(stamp[t][new])
+        for m, (tt, st, _) in enumerate(dgraph.tri_types):
+            if tt != t or new.size == 0:
+                continue
+            s, add, stp = np_budget_contributions(dgraph.csr[m], m, new, times, step, sn, max_time, seed, serial[st])
+            cand[st] = np.concatenate([cand[st], np_apply_budget(score[st], stamp[st], s, add, stp)])
+
+    try:
+        for t, (ids, tms) in enumerate(seeds):
+            sampled[t] = ids.astype(np.int64)
+            serial[t][ids] = np.arange(ids.size, dtype=np.int32)
+            stamp[t][ids] = (np.uint64(t) << np.uint64(32)) | _bias(tms)
+        for t in range(T):
+            add_budget(t, sampled[t], t)
+        for layer in range(sampled_depth):
+            for t in range(T):
+                step = T * (1 + layer) + t
+                new = np_select(cand[t], score[t], t, step, seed, sn)
+                serial[t][new] = np.arange(sampled[t].size, sampled[t].size + new.size, dtype=np.int32)
+                sampled[t] = np.concatenate([sampled[t], new])
+                cand[t] = np.setdiff1d(cand[t], new)
+                add_budget(t, new, step)
+        times = [_stamp_time(stamp[t][sampled[t]]) for t in range(T)]
+        src, dst, etime, rel_ptr, type_off = np_induce(dgraph, sampled, times, serial)
+    finally:                                                 # walk the lists the call touched
+        for t in range(T):
+            for ids in (sampled[t], cand[t]):
+                score[t][ids], stamp[t][ids], serial[t][ids] = 0, 0, -1
+    width = max([f.shape[1] for f in (dgraph.features_host or []) if f is not None] + [0])
+    feat = [np.zeros((0, width), np.float32) if dgraph.features_host is None or dgraph.features_host[t] is None or sampled[t].size == 0
+            else np.asarray(dgraph.features_host[t], dtype=np.float32)[sampled[t]] for t in range(T)]
+    feat = np.concatenate(feat, axis=0) if width else np.zeros((int(type_off[-1]), 0), np.float32)
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    out = _wire_tuple(_HostGraph, dgraph, tt(feat), [sampled[t].size for t in range(T)], tt(src), tt(dst), tt(etime), tt(rel_ptr), tt(type_off))
+    out.sorted = (src, dst, etime, rel_ptr, type_off)
+    out.indxs = {name: sampled[t] for t, name in enumerate(dgraph.types)}
+    out.times = {name: times[t] for t, name in enumerate(dgraph.types)}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- device
+class DeviceSamplerState:
+    """The device state of one (seed counts, depth, sampled_number) shape of call and the step-level calls on it (one method per C
+    entry point).  `sample_subgraph_device` strings them together; the tests call them one by one."""
+
+    def __init__(self, dgraph, n_seed, depth, sn):
+        if dgraph.device is None or dgraph.device.type != "cuda":
+            raise RuntimeError("pyhgt_amd: sample_subgraph_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host "
+                               "sibling is sample_subgraph_host)")
+        self.g, self.dev, self.sn, self.depth = dgraph, dgraph.device, int(sn), int(depth)
+        self.lib = _lib.load()
+        T, M, dev = len(dgraph.types), len(dgraph.triples), self.dev
+        self.T, self.M, self.R = T, M, len(dgraph.edge_dict)
+        self.cap_s, self.cap_c = _capacities(dgraph, n_seed, depth, sn)
+        if dgraph._dev_nodes is None:                        # the per-node arrays are shared by every shape of call
+            dgraph._dev_nodes = ([torch.zeros(n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
+                                 [torch.zeros(n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
+                                 [torch.full((n,), -1, dtype=torch.int32, device=dev) for n in dgraph.n_nodes])
+        self.score, self.stamp, self.serial = dgraph._dev_nodes
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.sampled = [torch.zeros(c, **i32) for c in self.cap_s]
+        self.cand = [torch.zeros(c, **i32) for c in self.cap_c]
+        self.counts = torch.zeros(T, 4, **i32)
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        self.types_c = (_lib.HgtSamplerType * T)()
+        for t in range(T):
+            self.types_c[t] = _lib.HgtSamplerType(ptr(self.score[t]), ptr(self.stamp[t]), ptr(self.serial[t]), ptr(self.sampled[t]),
+                                                  ptr(self.cand[t]), self.counts[t].data_ptr(), dgraph.n_nodes[t], self.cap_s[t], self.cap_c[t], 0)
+        self.triples_c = (_lib.HgtSamplerTriple * max(M, 1))()
+        for m, ((tt, st, rel), (ip, src, tm)) in enumerate(zip(dgraph.tri_types, dgraph.csr_dev)):
+            self.triples_c[m] = _lib.HgtSamplerTriple(ip.data_ptr(), ptr(src), ptr(tm), tt, st, rel, 0)
+        slots = C.c_int64()
+        _lib.check(self.lib.hgt_sampler_induce_slots(self.types_c, T, self.triples_c, M, C.byref(slots)), "hgt_sampler_induce_slots")
+        into = [sum(1 for tt, _, _ in dgraph.tri_types if tt == t) for t in range(T)]
+        rows = max([max(n_seed[t], sn) * into[t] for t in range(T)] + [0])       # add_budget: max_new x triples into the type
+        self.n_entries = max(int(slots.value), rows) + 1
+        self.rowoff, self.hub = torch.zeros(self.n_entries, **i32), torch.zeros(self.n_entries, **i32)
+        self.keys = torch.zeros(max(self.cap_c + [1]), dtype=torch.int64, device=dev)
+        self.tmp = torch.zeros(max(self.cap_c + [1]), **i32)
+        self.type_off, self.rel_ptr = torch.zeros(T + 1, **i32), torch.zeros(self.R + 1, **i32)
+        self.sizes = torch.zeros(T + M + 2, **i32)
+        self.dirty = False
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def seed_nodes(self, t, ids, times, step):
+        ids, times = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.dev) for a in (ids, times))
+        self.dirty = True
+        _lib.check(self.lib.hgt_sampler_seed(self.types_c, self.T, t, ids.data_ptr() if ids.numel() else None,
+                                             times.data_ptr() if ids.numel() else None, ids.numel(), step, self._stream()), "hgt_sampler_seed")
+        ids.record_stream(torch.cuda.current_stream(self.dev))
+        times.record_stream(torch.cuda.current_stream(self.dev))
+
+    def add_budget(self, t, step, max_new, max_time, seed):
+        self.dirty = True
+        _lib.check(self.lib.hgt_sampler_add_budget(self.types_c, self.T, self.triples_c, self.M, t, step, self.sn, max_new,
+                                                   0 if max_time is None else 1, 0 if max_time is None else int(max_time),
+                                                   seed & (2 ** 64 - 1), self.hub.data_ptr(), self.n_entries, self._stream()),
+                   "hgt_sampler_add_budget")
+
+    def select(self, t, step, seed):
+        self.dirty = True
+        _lib.check(self.lib.hgt_sampler_select(self.types_c, self.T, t, step, self.sn, seed & (2 ** 64 - 1), self.keys.data_ptr(),
+                                               self.tmp.data_ptr(), self.tmp.numel(), self._stream()), "hgt_sampler_select")
+
+    def induce(self):
+        """count pass, the one host read, fill pass -> (src, dst, edge_time, rel_ptr, type_off, node_time, node_id, nodes per type)"""
+        lib, T, M = self.lib, self.T, self.M
+        _lib.check(lib.hgt_sampler_induce_count(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(),
+                                                self.n_entries, self.type_off.data_ptr(), self.rel_ptr.data_ptr(), self.sizes.data_ptr(),
+                                                self._stream()), "hgt_sampler_induce_count")
+        sizes = self.sizes.cpu().numpy()                     # the host synchronisation of the batch
+        if sizes[T + M]:
+            raise RuntimeError("pyhgt_amd: a sampler list overflowed its static capacity or a seed id was out of range")
+        n_per_type = [int(v) for v in sizes[:T]]
+        N, E = sum(n_per_type), int(sizes[T + M + 1]) + sum(n_per_type)
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        src, dst, etime = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
+        node_time, node_id = torch.empty(N, **i32), torch.empty(N, **i32)
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        _lib.check(lib.hgt_sampler_induce_fill(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(),
+                                               self.n_entries, self.type_off.data_ptr(), N, E, ptr(src), ptr(dst), ptr(etime), ptr(node_time),
+                                               ptr(node_id), self._stream()), "hgt_sampler_induce_fill")
+        return src, dst, etime, self.rel_ptr.clone(), self.type_off.clone(), node_time, node_id, n_per_type
+
+    def reset(self):
+        _lib.check(self.lib.hgt_sampler_reset(self.types_c, self.T, self._stream()), "hgt_sampler_reset")
+        self.dirty = False
+
+    def clear(self):
+        """full clear of the per-node arrays: after a call that failed half way"""
+        for a in self.score + self.stamp:
+            a.zero_()
+        for a in self.serial:
+            a.fill_(-1)
+        self.counts.zero_()
+        self.dirty = False
+
+    def snapshot(self):
+        """host copies of the state (tests): score / stamp as uint64, serial, the two lists cut to their counts"""
+        counts = self.counts.cpu().numpy()
+        u64 = lambda a: a.cpu().numpy().view(np.uint64)
+        return dict(score=[u64(a) for a in self.score], stamp=[u64(a) for a in self.stamp], serial=[a.cpu().numpy() for a in self.serial],
+                    sampled=[a.cpu().numpy()[:counts[t, 0]].astype(np.int64) for t, a in enumerate(self.sampled)],
+                    cand=[a.cpu().numpy()[:counts[t, 2]].astype(np.int64) for t, a in enumerate(self.cand)], counts=counts)
+
+
+def _device_state(dgraph, n_seed, depth, sn):
+    key = (tuple(n_seed), int(depth), int(sn))
+    st = dgraph._dev_state.get(key)
+    if st is None:
+        if len(dgraph._dev_state) >= 4:                      # a loop uses one or two shapes of call; do not hoard lists
+            dgraph._dev_state.clear()
+        st = dgraph._dev_state[key] = DeviceSamplerState(dgraph, n_seed, depth, sn)
+    return st
+
+
+def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp, seed, plan=True):
+    """Sibling of `sample_subgraph` + `to_torch` (data.py:87-256) on the device: seeds `inp = {type: [[id, time], ...]}` -> the
+    `_DeviceGraph` 7-tuple (node_feature, node_type, edge_time, edge_index, edge_type, node_dict, edge_dict) with `.sorted`, `.plan`
+    (plan=False: none, for pieces that will only be stacked), `.indxs` = {type: original ids, int64 device tensor} and `.times`.
+    max_time=None: no time filter (the ogbn-mag variant).  Kernel launches are enqueued for seeds and every (layer, type) without a host
+    synchronisation; the single device->host read is the sizes of the result.  The result goes straight into `stack_device_graphs`."""
+    _check_args(dgraph, sampled_depth, sampled_number)
+    seeds = _seed_arrays(dgraph, inp)
+    T, sn, seed = len(dgraph.types), int(sampled_number), int(seed)
+    if dgraph.device is None or dgraph.device.type != "cuda":
+        raise RuntimeError("pyhgt_amd: sample_subgraph_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host sibling is "
+                           "sample_subgraph_host)")
+    if dgraph.features is None:
+        raise ValueError("pyhgt_amd: the DeviceHeteroGraph carries no features")
+    st = _device_state(dgraph, [ids.size for ids, _ in seeds], sampled_depth, sn)
+    dev = st.dev
+    with torch.cuda.device(dev):
+        if st.dirty:
+            st.clear()
+        for t, (ids, tms) in enumerate(seeds):
+            if ids.size:
+                st.seed_nodes(t, ids, tms, t)
+        for t, (ids, _) in enumerate(seeds):
+            if ids.size:
+                st.add_budget(t, t, ids.size, max_time, seed)
+        for layer in range(sampled_depth):
+            for t in range(T):
+                if st.cap_c[t] == 0:                         # nothing can ever be a candidate of this type
+                    continue
+                step = T * (1 + layer) + t
+                st.select(t, step, seed)
+                st.add_budget(t, step, sn, max_time, seed)
+        src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type = st.induce()
+        N = sum(n_per_type)
+        widths = sorted({f.size(1) for f in dgraph.features if f is not None and f.size(0) > 0})
+        if len(widths) > 1:
+            raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (widths,))
+        width = widths[0] if widths else 0
+        feat = torch.empty(N, width, dtype=torch.float32, device=dev)
+        off, stream = 0, torch.cuda.current_stream(dev).cuda_stream
+        for t, n in enumerate(n_per_type):
+            if n and width:
+                if dgraph.features[t] is None:
+                    raise ValueError("pyhgt_amd: no feature matrix for node type %r" % dgraph.types[t])
+                _lib.check(st.lib.hgt_gather_rows(dgraph.features[t].data_ptr(), width, st.sampled[t].data_ptr(), n, width,
+                                                  feat[off:].data_ptr(), stream), "hgt_gather_rows")
+            off += n
+        st.reset()
+        out = _wire_tuple(_DeviceGraph, dgraph, feat, n_per_type, src, dst, etime, rel_ptr, type_off)
+        out.sorted = (src, dst, etime, rel_ptr, type_off)
+        ids64, offs = node_id.long(), np.concatenate([[0], np.cumsum(n_per_type)])
+        out.indxs = {name: ids64[offs[t]:offs[t + 1]] for t, name in enumerate(dgraph.types)}
+        out.times = {name: node_time[offs[t]:offs[t + 1]] for t, name in enumerate(dgraph.types)}
+        if plan:
+            out.plan = GraphPlan.from_sorted(out[1], out[3], out[4], out[2], src, dst, etime, rel_ptr, type_off, T, st.R)
+            GraphPlan.register(out.plan, out[1], out[3], out[4], out[2], T, st.R)
+    return out

@@ -7,6 +7,7 @@ edge_type i64[E], edge_time i64[E] in [0,240) (data.py:250).  The recipe follows
 SURVEY.md section 8(d): uniform sources/targets (Poisson in-degree), relation
 ids independent of node types (every (src_type, rel, dst_type) combination occurs).
 """
+import numpy as np
 import torch
 
 
@@ -99,3 +100,38 @@ def induced_in_neighbourhood(node_feature, node_type, edge_index, edge_type, edg
     pos = torch.searchsorted(nodes, targets)
     tm = edge_time[eids].cpu() if edge_time is not None else None
     return (node_feature[nodes].cpu(), node_type[nodes].cpu(), ei_sub.cpu(), edge_type[eids].cpu(), tm, pos.cpu())
+
+
+def synthetic_hetero_csr(types, meta, n_nodes, mean_degree=4.0, seed=0, years=(2000, 2020), none_time=()):
+    """A random resident graph for the device sampler (pyhgt_amd.sampler.DeviceHeteroGraph.from_csr): per meta triple
+    (target type, source type, relation) a CSR by target id -> (indptr, src, time) int32 arrays in `meta` order.
+
+    A relation without the `rev_` prefix gets Poisson(mean_degree) distinct neighbours per target with one year per edge; its
+    `rev_` twin (data.py:61) is the transpose with the same years, so a type with few nodes (venues, fields) has the long rows the
+    reference's comment at data.py:106-111 speaks of.  Relations named in `none_time` carry no time (INT32_MIN, the reference's None)."""
+    rng = np.random.default_rng(seed)
+    meta = [tuple(m) for m in meta]
+    coo = {}
+    for tt, st, rel in meta:
+        if rel.startswith("rev_"):
+            continue
+        n_t, n_s = int(n_nodes[tt]), int(n_nodes[st])
+        if n_t == 0 or n_s == 0:
+            coo[(tt, st, rel)] = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64))
+            continue
+        deg = np.minimum(rng.poisson(mean_degree, size=n_t), n_s)
+        tgt = np.repeat(np.arange(n_t), deg)
+        pair = np.unique(tgt * n_s + rng.integers(0, n_s, size=tgt.size))
+        rng.shuffle(pair)                                                  # neighbours in no particular order, like a dict's
+        tm = np.full(pair.size, -2 ** 31, np.int64) if rel in none_time else rng.integers(years[0], years[1], size=pair.size)
+        coo[(tt, st, rel)] = (pair // n_s, pair % n_s, tm)
+    out = []
+    for tt, st, rel in meta:
+        if rel.startswith("rev_") and (st, tt, rel[4:]) in coo:
+            src, tgt, tm = coo[(st, tt, rel[4:])]
+        else:
+            tgt, src, tm = coo[(tt, st, rel)]
+        order = np.argsort(tgt, kind="stable")
+        indptr = np.concatenate([[0], np.cumsum(np.bincount(tgt, minlength=int(n_nodes[tt])))])
+        out.append((indptr.astype(np.int32), src[order].astype(np.int32), tm[order].astype(np.int32)))
+    return out

@@ -1,0 +1,109 @@
+#!/usr/bin/env python
+"""Time per sampled batch: sample_subgraph_device against its numpy sibling sample_subgraph_host and, for scale, to_device_graph on the
+host sibling's output, on MAG- and OAG-shaped synthetic resident graphs (the schemas of pyhgt_amd/sampled.py) at the reference's batch
+shapes: 128 seed papers, depth 6, width 128 (OAG/train_paper_field.py) and width 520 (ogbn-mag/train_ogbn_mag.py:44-55).
+
+    python tools/bench_sampler.py [--papers 200000] [--reps 10] [--host-reps 2] [--out profiles/r11_device_sampler.json]
+
+Device time is wall-clock per call with a synchronisation after each (the call synchronises once by itself, for the sizes of the
+result); launches per batch are counted from the calls the host loop makes (every C entry point is a fixed number of launches).  One
+JSON line per workload on stdout, all of them in --out."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+from pyhgt_amd import sample_subgraph_device, sample_subgraph_host  # noqa: E402
+from pyhgt_amd.sampled import SchemaGraph, to_device_graph  # noqa: E402
+from train_device_sampler import resident_graph  # noqa: E402
+
+WORKLOADS = {"oag_d6_w128": ("oag", 6, 128, 2015), "mag_d6_w520": ("mag", 6, 520, None), "mag_d6_w128": ("mag", 6, 128, None)}
+# launches per C entry point (csrc/hgt_sampler.hip): seed 1, add_budget memset + 2, select 2, induce_count memset + 3, induce_fill 3, reset 2
+LAUNCHES = dict(seed=1, add_budget=3, select=2, induce=7, reset=2)
+
+
+def launches_per_batch(dgraph, depth, n_seed_types=1):
+    T = len(dgraph.types)
+    live = sum(1 for t in range(T) if any(st == t for _, st, _ in dgraph.tri_types))
+    feature_gathers = T
+    return (n_seed_types * (LAUNCHES["seed"] + LAUNCHES["add_budget"]) + depth * live * (LAUNCHES["select"] + LAUNCHES["add_budget"])
+            + LAUNCHES["induce"] + LAUNCHES["reset"] + feature_gathers)
+
+
+def hand_over(res, dgraph):
+    """the host sibling's result as (feature, time, edge_list, graph) for to_device_graph"""
+    types = dgraph.get_types()
+    src, dst, _, rel_ptr, off = res.sorted
+    feat = res[0].numpy()
+    feature = {t: feat[off[i]:off[i + 1]] for i, t in enumerate(types)}
+    edge_list = {}
+    for i, t in enumerate(types):
+        n = int(off[i + 1] - off[i])
+        if n:
+            edge_list.setdefault(t, {}).setdefault(t, {})["self"] = np.stack([np.arange(n), np.arange(n)], axis=1)
+    tid = {t: i for i, t in enumerate(types)}
+    for tt, st, rel in dgraph.triples:
+        r = dgraph.edge_dict[rel]
+        e = slice(rel_ptr[r], rel_ptr[r + 1])
+        if rel_ptr[r + 1] > rel_ptr[r]:
+            edge_list.setdefault(tt, {}).setdefault(st, {})[rel] = np.stack([dst[e] - off[tid[tt]], src[e] - off[tid[st]]], axis=1)
+    return feature, res.times, edge_list, SchemaGraph(types, dgraph.get_meta_graph())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--papers", type=int, default=200000)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--host-reps", type=int, default=2)
+    ap.add_argument("--feat-dim", type=int, default=128)
+    ap.add_argument("--mean-degree", type=float, default=3.0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    dev, lines = "cuda:0", []
+    for name, (schema, depth, width, max_time) in WORKLOADS.items():
+        dgraph, n_nodes = resident_graph(schema, a.papers, a.feat_dim, dev, seed=1, mean_degree=a.mean_degree)
+        rng = np.random.default_rng(7)
+        inps = [{"paper": np.stack([rng.choice(n_nodes["paper"], 128, replace=False), np.full(128, 2015)], axis=1)} for _ in range(a.reps + 2)]
+        for i in range(2):                                   # warm-up: allocations of the state, first launches
+            g = sample_subgraph_device(dgraph, max_time, depth, width, inps[i], seed=i)
+        torch.cuda.synchronize()
+        t_dev = []
+        for i in range(a.reps):
+            t0 = time.perf_counter()
+            g = sample_subgraph_device(dgraph, max_time, depth, width, inps[2 + i], seed=100 + i)
+            torch.cuda.synchronize()
+            t_dev.append(time.perf_counter() - t0)
+        t_host, t_hand = [], []
+        for i in range(a.host_reps):
+            t0 = time.perf_counter()
+            h = sample_subgraph_host(dgraph, max_time, depth, width, inps[2 + i], seed=100 + i)
+            t_host.append(time.perf_counter() - t0)
+            args = hand_over(h, dgraph)
+            t0 = time.perf_counter()
+            to_device_graph(*args, device=dev)
+            torch.cuda.synchronize()
+            t_hand.append(time.perf_counter() - t0)
+        line = dict(workload=name, schema=schema, papers=a.papers, nodes_total=int(sum(n_nodes.values())),
+                    edges_total=int(sum(c[1].size for c in dgraph.csr)), max_degree=int(max(np.diff(c[0]).max() for c in dgraph.csr)),
+                    seeds=128, depth=depth, width=width, batch_nodes=int(g[1].numel()), batch_edges=int(g[4].numel()),
+                    launches_per_batch=launches_per_batch(dgraph, depth), device_ms_per_batch=float(np.median(t_dev) * 1e3),
+                    device_ms_min=float(np.min(t_dev) * 1e3), host_sibling_ms_per_batch=float(np.median(t_host) * 1e3),
+                    to_device_graph_ms=float(np.median(t_hand) * 1e3), host_batch_nodes=int(h[1].numel()))
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del dgraph
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(lines, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

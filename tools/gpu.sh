@@ -19,6 +19,8 @@
 #   latency   kernel timelines of the latency-regime workloads (c3, script-default batch, c5, published 4-layer model, c1; $3 = precision):
 #             per-kernel us and gaps of a steady-state forward (tools/trace_latency.py) -> $OUT/<tag>_latency_<workload>.txt
 #   small     the latency-regime part of the judged line only (bench.py --small-only): wall-clock us per layer / forward + parity
+#   sampler   the device sampler: its GPU tests, then tools/bench_sampler.py (device call against the numpy sibling and to_device_graph on
+#             MAG- / OAG-shaped resident graphs) -> $OUT/<tag>_device_sampler.json, and the example loop that trains on sampled batches
 # Everything lands in $OUT (HGT_OUT_DIR, default bench_out/); summaries to be judged are copied to profiles/ by hand (or by `final`).
 # bench.py runs whose parity, secondaries or CPU baseline are read here pass --full (a plain bench.py run is the headline only).
 # Kernel experiments: tools/lab/build_lab.sh (lab libraries), lab_run.sh (phase times), pmc_quick.sh (counters), isa.sh (ISA + resources).
@@ -161,6 +163,12 @@ for k, v in j.items():
     for p, e in v.items():
         if isinstance(e, dict): print("    ", p, {kk: (float("%.4g" % vv) if isinstance(vv, float) else vv) for kk, vv in e.items()})
 PY
+    ;;
+sampler)
+    timeout 600 python -m pytest tests/test_sampler_gpu.py -m gpu -q -x -s > $OUT/${TAG}_sampler_tests.log 2>&1; echo "tests rc=$?"
+    grep -E "^select | passed| failed|^FAILED|^ERROR" $OUT/${TAG}_sampler_tests.log | tail -20
+    timeout 900 python tools/bench_sampler.py --out $OUT/${TAG}_device_sampler.json 2> $OUT/${TAG}_device_sampler.err; echo "bench rc=$?"
+    timeout 300 python examples/train_device_sampler.py --steps 20 2>&1 | tail -4
     ;;
 emuprof)
     export TMPDIR=/tmp; ROOT=$(pwd); cd /tmp
