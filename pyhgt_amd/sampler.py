@@ -108,6 +108,7 @@ class DeviceHeteroGraph:
         self._host_state = None
         self._dev_state = {}
         self._dev_nodes = None
+        self._dev_dirty = False                              # the per-node device arrays hold something a reset has not walked
         if self.device is not None:
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
             self.csr_dev = [tuple(up(a) for a in c) for c in self.csr]
@@ -296,8 +297,10 @@ def _wire_tuple(cls, dgraph, feat, n_per_type, src, dst, etime, rel_ptr, type_of
     return cls((feat, node_type, etime.long(), edge_index, edge_type, node_dict, dict(dgraph.edge_dict)))
 
 
-def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, seed):
-    """numpy sibling of `sample_subgraph_device`: the same definition on the host copy of the graph.  Returns a `_HostGraph`."""
+def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, seed, trace=None):
+    """numpy sibling of `sample_subgraph_device`: the same definition on the host copy of the graph.  Returns a `_HostGraph`.
+    trace: a list that receives, per select step, (type index, step, candidate ids, their float64 keys) -- what decides whether a
+    fp32 key order can differ from this one (tests)."""
     _check_args(dgraph, sampled_depth, sampled_number)
     T, sn = len(dgraph.types), int(sampled_number)
     seeds = _seed_arrays(dgraph, inp)
@@ -326,7 +329,10 @@ def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, s
         for layer in range(sampled_depth):
             for t in range(T):
                 step = T * (1 + layer) + t
-                new = np_select(cand[t], score[t], t, step, seed, sn)
+                keys = np_select_keys(cand[t], score[t], t, step, seed)
+                new = cand[t][np.lexsort((cand[t], keys))[:min(sn, cand[t].size)]]      # np_select, with the keys kept
+                if trace is not None:
+                    trace.append((t, step, cand[t].copy(), keys))
                 serial[t][new] = np.arange(sampled[t].size, sampled[t].size + new.size, dtype=np.int32)
                 sampled[t] = np.concatenate([sampled[t], new])
                 cand[t] = np.setdiff1d(cand[t], new)
@@ -390,7 +396,16 @@ class DeviceSamplerState:
         self.tmp = torch.zeros(max(self.cap_c + [1]), **i32)
         self.type_off, self.rel_ptr = torch.zeros(T + 1, **i32), torch.zeros(self.R + 1, **i32)
         self.sizes = torch.zeros(T + M + 2, **i32)
-        self.dirty = False
+
+    # Clean or dirty is a fact about the per-node arrays, which every shape of call shares: it lives on the graph.  A state that
+    # starts on a graph another state left dirty (a call that raised half way, a state evicted from the cache) sees it.
+    @property
+    def dirty(self):
+        return self.g._dev_dirty
+
+    @dirty.setter
+    def dirty(self, value):
+        self.g._dev_dirty = bool(value)
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -440,12 +455,14 @@ class DeviceSamplerState:
         self.dirty = False
 
     def clear(self):
-        """full clear of the per-node arrays: after a call that failed half way"""
+        """full clear of the per-node arrays: after a call that failed half way.  The counters of every cached state go with them: the
+        state that failed is not the one that finds the graph dirty when the next call has another shape."""
         for a in self.score + self.stamp:
             a.zero_()
         for a in self.serial:
             a.fill_(-1)
-        self.counts.zero_()
+        for st in [self] + list(self.g._dev_state.values()):
+            st.counts.zero_()
         self.dirty = False
 
     def snapshot(self):

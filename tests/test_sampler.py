@@ -1,6 +1,7 @@
 """CPU tests of the device sampler's definition (pyhgt_amd/sampler.py): the numpy sibling against the reference's sample_subgraph in
-the regime where that draws no random number, the selection rule's distribution, the CSR builder and the argument rules of the C ABI.
-No kernel runs here."""
+the regime where that draws no random number, the selection rule's distribution, the CSR builder and the argument rules of the C ABI;
+the lists of whole calls that test_sampler_gpu.py compares with the sibling bit for bit, each certified here by the sibling's own
+float64 keys, and the rows whose subset draw has a duplicated threshold word (tools/find_sampler_ties.py).  No kernel runs here."""
 import ctypes as C
 import importlib.util
 import itertools
@@ -12,13 +13,13 @@ import pytest
 from oracle.reference_loader import reference_available, load_reference_data
 from pyhgt_amd import _lib
 from pyhgt_amd.sampler import (DeviceHeteroGraph, sample_subgraph_host, sample_subgraph_device, philox4x32_10, np_select, np_select_keys,
-                               TIME_NONE)
+                               np_budget_contributions, TIME_NONE)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _tool():
-    spec = importlib.util.spec_from_file_location("gen_golden_sampler", os.path.join(ROOT, "tools", "gen_golden_sampler.py"))
+def _tool(name="gen_golden_sampler"):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
@@ -246,3 +247,187 @@ def test_sampler_abi_argument_rules():
     assert lib.hgt_sampler_induce_fill(types, 2, triples, 2, 3, p, p, 8, p, 4, 6, p, p, p, p, p, None) == WS
     assert lib.hgt_sampler_induce_fill(types, 2, triples, 2, 3, p, p, 9, p, 4, 2 ** 31, p, p, p, p, p, None) == -4
     del buf
+
+
+# ---------------------------------------------------------------------------------------------------------------- whole calls
+# The device draws the Philox words of the host sibling and holds the same integer scores, so a whole call can differ from the
+# sibling's only where two fp32 selection keys order differently from their float64 twins.  A device key is within MARGIN = 1 + 2^-20
+# of its float64 twin (test_sampler_gpu.py), two keys that move against each other need MARGIN ** 2, and the certificate asks for
+# MARGIN ** 4 (a factor two of headroom in the exponent) between every pair of adjacent keys among the min(sampled_number + 1, n)
+# smallest of every select step: then the chosen set and its serial order are those of the sibling, and by induction over the steps so
+# is everything else.  The lists below are certified by the sibling alone, on the CPU; test_sampler_gpu.py runs them on the device.
+MARGIN = 1.0 + 2.0 ** -20
+CERTIFIED_GAP = MARGIN ** 4 - 1.0
+
+
+def certificate_gap(trace, sampled_number):
+    """smallest (ratio of adjacent keys - 1) among the min(sampled_number + 1, n) smallest float64 keys over the select steps of a
+    trace of sample_subgraph_host; inf for a trace without two keys to compare"""
+    gap = np.inf
+    for _, _, ids, keys in trace:
+        k = np.sort(keys)[:sampled_number + 1]
+        if k.size > 1:
+            gap = min(gap, float((k[1:] / k[:-1]).min() - 1.0))
+    return gap
+
+
+def host_certified(dg, call):
+    """-> (result of the host sibling, certificate gap, number of select steps that had a candidate) of call = (inp, max_time, depth,
+    sampled_number, seed)"""
+    inp, max_time, depth, sn, seed = call
+    trace = []
+    res = sample_subgraph_host(dg, max_time, depth, sn, inp, seed, trace=trace)
+    return res, certificate_gap(trace, sn), sum(1 for _, _, ids, _ in trace if ids.size)
+
+
+OAG_TYPES = ["paper", "author", "field", "venue", "affiliation"]
+OAG_N = {"paper": 6000, "author": 4000, "field": 45, "venue": 40, "affiliation": 200}
+# (target, source, relation): venue rows (~600 papers) are above the hub line of 512, field rows (~530 +- 23) lie on both sides of it;
+# paper <- venue carries no time; no triple has affiliation as its source, so nothing can ever be a candidate of that type
+OAG_META = [("paper", "author", "AP_write"), ("author", "paper", "rev_AP_write"), ("paper", "venue", "PV"), ("venue", "paper", "rev_PV"),
+            ("paper", "field", "PF"), ("field", "paper", "rev_PF"), ("paper", "paper", "PP_cite"), ("paper", "paper", "rev_PP_cite"),
+            ("field", "field", "FF_in"), ("affiliation", "author", "AA_in")]
+
+
+def oag_graph(device=None):
+    from pyhgt_amd.synth import synthetic_hetero_csr
+    csr = synthetic_hetero_csr(OAG_TYPES, OAG_META, OAG_N, mean_degree=4.0, seed=5, years=(-10, 10), none_time=("PV",))
+    rng = np.random.default_rng(6)
+    feats = {t: rng.standard_normal((OAG_N[t], 8)).astype(np.float32) for t in OAG_TYPES}
+    return DeviceHeteroGraph.from_csr(OAG_TYPES, OAG_META, OAG_N, csr, feats, device=device)
+
+
+def _ids(lo, n, stride, time):
+    return [[lo + i * stride, time] for i in range(n)]
+
+
+_PAPERS = {"paper": _ids(3, 32, 187, 4)}
+_THREE = {"paper": _ids(1, 12, 499, 6), "author": _ids(2, 7, 571, -3), "venue": _ids(0, 3, 13, 0)}
+_AFFIL = {"affiliation": _ids(5, 9, 21, 2)}                # a seed type nothing points into
+# (seeds, max_time, depth, sampled_number, Philox seed)
+OAG_CALLS = [(inp, max_time, depth, sn, seed) for inp, max_time, depth, sn, seeds in [
+    (_PAPERS, 5, 0, 16, (0,)), (_THREE, None, 0, 128, (1,)),
+    (_PAPERS, 5, 1, 1, (0, 1)), (_PAPERS, None, 1, 16, (2,)), (_THREE, 3, 1, 128, (3,)), (_AFFIL, None, 1, 128, (4,)),
+    (_PAPERS, 5, 3, 16, (0, 1, 2, 3)), (_PAPERS, None, 3, 128, (5, 6)), (_THREE, -2, 3, 16, (7, 8)), (_THREE, None, 3, 1, (9, 10)),
+    (_THREE, 3, 3, 128, (11, 16)), (_AFFIL, 4, 3, 16, (13, 14)), (_AFFIL, None, 3, 1, (15,))] for seed in seeds]
+
+
+def _wide_meta(n_types, n_forward):
+    types = ["t%02d" % i for i in range(n_types)]
+    meta = []
+    for i in range(n_forward):
+        tt, st = types[i % n_types], types[(5 * i + 3) % n_types]
+        meta += [(tt, st, "r%02d" % i), (st, tt, "rev_r%02d" % i)]
+    return types, meta
+
+
+def table_graph(kind, device=None):
+    """the limits of the kernel-argument tables: `wide` = HGT_SAMPLER_MAX_TYPES types and HGT_SAMPLER_MAX_TRIPLES triples, ten to fifty
+    nodes per type; `one` = one type, one triple (x, x, xx)"""
+    from pyhgt_amd.synth import synthetic_hetero_csr
+    if kind == "wide":
+        types, meta = _wide_meta(_lib.HGT_SAMPLER_MAX_TYPES, _lib.HGT_SAMPLER_MAX_TRIPLES // 2)
+        n = {t: 10 + (i * 7) % 41 for i, t in enumerate(types)}
+    else:
+        types, meta, n = ["x"], [("x", "x", "xx")], {"x": 300}
+    csr = synthetic_hetero_csr(types, meta, n, mean_degree=5.0, seed=8, years=(-10, 10), none_time=("r03",))
+    rng = np.random.default_rng(9)
+    feats = {t: rng.standard_normal((n[t], 4)).astype(np.float32) for t in types}
+    return DeviceHeteroGraph.from_csr(types, meta, n, csr, feats, device=device)
+
+
+TABLE_CALLS = {"wide": [({"t00": _ids(0, 4, 2, 3), "t07": _ids(1, 3, 3, -1), "t15": _ids(0, 2, 5, 8)}, 6, 3, 4, 0),
+                        ({"t05": _ids(0, 5, 2, 0)}, None, 2, 16, 1)],
+               "one": [({"x": _ids(2, 6, 31, 1)}, 5, 3, 4, 0), ({"x": _ids(0, 3, 100, -4)}, None, 2, 16, 1)]}
+
+
+@pytest.fixture(scope="module")
+def oag():
+    return oag_graph()
+
+
+def test_trace_hook_reports_every_select_step(oag):
+    """the trace of a call: one entry per (layer, type) in step order, and re-ranking its keys gives the nodes the call added"""
+    inp, max_time, depth, sn, seed = next(c for c in OAG_CALLS if c[0] is _AFFIL and c[2] == 3 and c[3] == 16)
+    trace = []
+    res = sample_subgraph_host(oag, max_time, depth, sn, inp, seed, trace=trace)
+    plain = sample_subgraph_host(oag, max_time, depth, sn, inp, seed)
+    assert all(np.array_equal(a, b) for a, b in zip(res.sorted, plain.sorted))
+    T = len(OAG_TYPES)
+    assert [(t, step) for t, step, _, _ in trace] == [(t, T * (1 + layer) + t) for layer in range(depth) for t in range(T)]
+    taken = {t: len(inp.get(t, [])) for t in OAG_TYPES}
+    for t, step, ids, keys in trace:
+        assert ids.dtype == np.int64 and keys.dtype == np.float64 and ids.shape == keys.shape and np.all(keys > 0)
+        new = ids[np.lexsort((ids, keys))[:sn]]
+        name = OAG_TYPES[t]
+        assert np.array_equal(res.indxs[name][taken[name]:taken[name] + new.size], new), (name, step)
+        taken[name] += new.size
+    assert taken == {t: len(res.indxs[t]) for t in OAG_TYPES}
+    assert not any(ids.size for t, _, ids, _ in trace if OAG_TYPES[t] == "affiliation") and len(res.indxs["affiliation"]) == 9
+
+
+def test_whole_call_lists_are_certified(oag):
+    """every call the GPU tests compare whole is certified by the host sibling alone; the lists cover depth 0 / 1 / 3, sampled_number
+    1 / 16 / 128, max_time set and None, one and three seed types and a seed type nothing points into"""
+    assert len(OAG_CALLS) >= 16 and {c[2] for c in OAG_CALLS} == {0, 1, 3} and {c[3] for c in OAG_CALLS} == {1, 16, 128}
+    assert {c[1] is None for c in OAG_CALLS} == {True, False} and {len(c[0]) for c in OAG_CALLS} == {1, 3}
+    hubs = [int((np.diff(ip) > 512).sum()) for ip, _, _ in oag.csr]
+    rows = sum(ip.size - 1 for ip, _, _ in oag.csr)
+    assert sum(1 for h in hubs if h) >= 2 and sum(hubs) < rows // 50, hubs
+    smallest, drew = np.inf, 0
+    for graph, calls in [(oag, OAG_CALLS)] + [(table_graph(k), TABLE_CALLS[k]) for k in ("wide", "one")]:
+        for i, call in enumerate(calls):
+            res, gap, steps = host_certified(graph, call)
+            assert gap > CERTIFIED_GAP, "call %d of %s: gap %.3g" % (i, graph.types[:2], gap)
+            assert call[2] == 0 or steps > 0
+            smallest, drew = min(smallest, gap), drew + steps
+    print("smallest certified gap %.3g (threshold %.3g) over %d select steps" % (smallest, CERTIFIED_GAP, drew))
+    wide = table_graph("wide")
+    assert len(wide.types) == _lib.HGT_SAMPLER_MAX_TYPES and len(wide.triples) == _lib.HGT_SAMPLER_MAX_TRIPLES
+    assert all(10 <= n <= 50 for n in wide.n_nodes)
+
+
+# ---------------------------------------------------------------------------------------------------------------- ties of the subset draw
+# Found by tools/find_sampler_ties.py (its defaults, 2.9 s; --degree 512 --targets 4096 --seeds 64, 4.5 s): rows whose r-th and
+# (r + 1)-th smallest Philox words are equal.  seed, target id, step, triple index, degree, r, the word, its two positions.
+TIES = {"workgroup": dict(seed=0, target=119, step=0, triple=0, degree=60000, r=486, word=0x02110750, positions=(32474, 49873)),
+        "wavefront": dict(seed=2, target=1360, step=0, triple=0, degree=512, r=248, word=0x829cb37c, positions=(203, 255))}
+TIE_N = {"x": 1400, "y": 60000}
+
+
+def tie_graph(device=None):
+    """x <- y, one triple: the two rows of TIES (each neighbour list a permutation prefix of y, so the tied positions hold different
+    ids), every other row empty"""
+    rng = np.random.default_rng(14)
+    deg = np.zeros(TIE_N["x"], np.int64)
+    for tie in TIES.values():
+        deg[tie["target"]] = tie["degree"]
+    indptr = np.concatenate([[0], np.cumsum(deg)])
+    src = np.concatenate([rng.permutation(TIE_N["y"])[:d] for d in deg[deg > 0]])
+    tm = rng.integers(-10, 10, size=src.size)
+    tm[rng.random(src.size) < 0.1] = TIME_NONE
+    feats = {t: np.zeros((n, 1), np.float32) for t, n in TIE_N.items()}
+    return DeviceHeteroGraph.from_csr(["x", "y"], [("x", "y", "xy")], TIE_N, [(indptr, src, tm)], feats, device=device)
+
+
+@pytest.mark.parametrize("name", list(TIES))
+def test_tie_fixtures_sit_where_the_constants_say(name):
+    tie = TIES[name]
+    F = _tool("find_sampler_ties")
+    words = F.row_words(tie["degree"], tie["target"], tie["step"], tie["triple"], tie["seed"])
+    order = np.lexsort((np.arange(words.size), words))
+    r = tie["r"]
+    assert 1 <= r and r + 1 < tie["degree"] and r + 1 <= _lib.HGT_SAMPLER_MAX_NUMBER          # sampled_number = r and r + 1 both draw
+    assert (name == "wavefront") == (tie["degree"] <= _lib.HGT_SAMPLER_HUB_DEG)
+    assert words[order[r - 1]] == words[order[r]] == tie["word"] and (order[r - 1], order[r]) == tie["positions"]
+    assert words[order[r - 2]] < tie["word"] < words[order[r + 1]]                            # a tie of exactly two
+    assert F.tie_of_row(words, r) == (r, tie["word"]) + tie["positions"]
+    dg = tie_graph()
+    indptr, src, tm = dg.csr[tie["triple"]]
+    beg = indptr[tie["target"]]
+    assert indptr[tie["target"] + 1] - beg == tie["degree"]
+    p, q = tie["positions"]
+    assert src[beg + p] != src[beg + q]
+    # breaking the tie the other way changes the result: both neighbours pass the filters of the draw the GPU test makes
+    s, add, _ = np_budget_contributions(dg.csr[0], 0, [tie["target"]], [0], tie["step"], r, None, tie["seed"], np.full(TIE_N["y"], -1))
+    assert s.size == r and src[beg + p] in s and src[beg + q] not in s

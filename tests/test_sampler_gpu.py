@@ -4,7 +4,14 @@ and the result through GNN / stack_device_graphs against the same arrays handed 
 
 The `lines` graph (3 types, 5 meta triples, ~10^4 nodes: one row must be longer than the 8192 Philox words a hub workgroup keeps in
 registers) has rows on both sides of every line of the kernels: degrees sampled_number - 1 / = / + 1 for sampled_number 8 and 128, a
-row of 512 neighbours (the last a wavefront takes) and of 513 (the first a workgroup takes), one of 9000."""
+row of 512 neighbours (the last a wavefront takes) and of 513 (the first a workgroup takes), one of 9000.
+
+Whole calls that draw random numbers are compared with the host sibling bit for bit where the sibling's own float64 keys certify
+that no fp32 key order can differ (test_sampler.py, "whole calls"); a call that is not certified fails.  Further graphs put a
+duplicated threshold word into a subset draw, more hub rows into the queues than there are hub workgroups, sampled_number and the
+kernel-argument tables at their limits, and lists against capacities smaller than their tensors."""
+import os
+import re
 from collections import OrderedDict
 
 import numpy as np
@@ -15,7 +22,7 @@ import test_sampler as TS
 from pyhgt_amd import GNN, GraphPlan
 from pyhgt_amd.sampled import SchemaGraph, stack_device_graphs, to_device_graph
 from pyhgt_amd.sampler import (DeviceHeteroGraph, DeviceSamplerState, sample_subgraph_device, sample_subgraph_host, np_apply_budget,
-                               np_budget_contributions, np_induce, np_select_keys, _stamp_time, TIME_NONE)
+                               np_budget_contributions, np_induce, np_select_keys, _device_state, _stamp_time, TIME_NONE)
 from test_hgt_gpu import DEV
 
 pytestmark = pytest.mark.gpu
@@ -191,6 +198,45 @@ def test_induce_equals_the_numpy_induction_of_the_devices_node_set(lines, sn):
 
 
 # ---------------------------------------------------------------------------------------------------------------- whole calls
+_HOST = {}
+
+
+def _certified_host(dg, call):
+    """the host sibling's result of call = (inp, max_time, depth, sampled_number, seed), computed once; a call whose float64 keys do
+    not certify the comparison fails the test that asked"""
+    key = (len(dg.types), repr(call))
+    if key not in _HOST:
+        _HOST[key] = TS.host_certified(dg, call)[:2]
+    res, gap = _HOST[key]
+    assert gap > TS.CERTIFIED_GAP, "not certified: two float64 keys within %.3g of each other (need %.3g)" % (gap, TS.CERTIFIED_GAP)
+    return res
+
+
+def _assert_equals_host(res, host, dg):
+    """a device result against the sibling's, bit for bit"""
+    for got, exp, name in zip(res.sorted, host.sorted, ("src", "dst", "edge_time", "rel_ptr", "type_off")):
+        assert got.dtype == torch.int32 and np.array_equal(got.cpu().numpy(), exp), name
+    for t in dg.types:
+        assert np.array_equal(res.indxs[t].cpu().numpy(), host.indxs[t]), "ids of %s in serial order" % t
+        assert np.array_equal(res.times[t].cpu().numpy(), host.times[t]), "times of %s" % t
+    for i, name in enumerate(("node_feature", "node_type", "edge_time", "edge_index", "edge_type")):
+        assert res[i].dtype == host[i].dtype and torch.equal(res[i].cpu(), host[i]), name
+    assert res[5] == host[5] and res[6] == host[6]
+
+
+def _assert_same(a, b):
+    """two device results"""
+    for u, v in zip(list(a[:5]) + list(a.sorted), list(b[:5]) + list(b.sorted)):
+        assert torch.equal(u, v)
+    assert all(torch.equal(a.indxs[t], b.indxs[t]) and torch.equal(a.times[t], b.times[t]) for t in a.indxs)
+    assert a[5] == b[5] and a[6] == b[6]
+
+
+def _call(dg, call):
+    inp, max_time, depth, sn, seed = call
+    return sample_subgraph_device(dg, max_time, depth, sn, inp, seed, plan=False)
+
+
 def _canonical(res):
     cpu = lambda v: v.cpu().numpy()
     return G.canonical(list(res[5]), {t: cpu(v) for t, v in res.indxs.items()}, {t: cpu(v) for t, v in res.times.items()}, cpu(res[3]),
@@ -240,10 +286,9 @@ def test_random_regime_is_valid_and_repeatable(lines):
     assert (times[0][12:] <= 2008).all() and (times[1] <= 2008).all()
     assert torch.equal(a[0], torch.cat([lines.features[t][a.indxs[TYPES[t]]] for t in range(3)]))
     a.plan.raise_if_bad(wait=True)
-    # the host sibling draws the same words: the same node sets unless an fp32 key order differs from the float64 one
-    h = sample_subgraph_host(lines, 2008, depth, sn, inp, seed=31)
-    same = [np.array_equal(np.sort(h.indxs[t]), np.sort(ids[i])) for i, t in enumerate(TYPES)]
-    print("node sets equal to the host sibling's:", same)
+    # the host sibling draws the same words: the same result unless an fp32 key order differs from the float64 one, which the
+    # sibling's own keys rule out for this seed
+    _assert_equals_host(a, _certified_host(lines, (inp, 2008, depth, sn, 31)), lines)
 
 
 def _hand_over(res, dg):
@@ -290,3 +335,285 @@ def test_sampled_graph_runs_through_gnn_and_stacking_like_a_handed_over_one(line
     assert torch.equal(out_s, twin_s) and out_s.shape[0] == parts[0][1].numel() + parts[1][1].numel()
     S.plan.raise_if_bad(wait=True)
     GraphPlan.clear_cache()
+
+
+# ---------------------------------------------------------------------------------------------------------------- whole calls that draw
+@pytest.fixture(scope="module")
+def oag_dev():
+    return TS.oag_graph(device=DEV)
+
+
+@pytest.mark.parametrize("i", range(len(TS.OAG_CALLS)))
+def test_certified_call_equals_the_host_sibling(oag_dev, i):
+    """seed -> budget -> select -> budget -> ... -> induce over several layers and types against the definition: the step numbering,
+    the newest-batch hand-over from select to add_budget, the skip of a type nothing points into, max_new"""
+    call = TS.OAG_CALLS[i]
+    host = _certified_host(oag_dev, call)
+    res = _call(oag_dev, call)
+    _assert_equals_host(res, host, oag_dev)
+    if call[2] == 3 and call[3] == 16 and call[0] is TS._PAPERS:      # not a trivial call: the layers added nodes of four types
+        assert [len(host.indxs[t]) for t in TS.OAG_TYPES] == [32 + 48, 48, 45, 40, 0]
+
+
+@pytest.mark.parametrize("kind, i", [("wide", 0), ("wide", 1), ("one", 0), ("one", 1)])
+def test_certified_call_with_maximal_and_minimal_tables(kind, i):
+    """16 types and 48 triples (every entry of the kernel-argument tables in use), and one type with one triple (15 padded types,
+    47 padded triples)"""
+    dg = TS.table_graph(kind, device=DEV)
+    call = TS.TABLE_CALLS[kind][i]
+    host = _certified_host(dg, call)
+    _assert_equals_host(_call(dg, call), host, dg)
+    assert sum(len(v) for v in host.indxs.values()) > sum(len(v) for v in call[0].values())
+
+
+# ---------------------------------------------------------------------------------------------------------------- step-level edges
+def _assert_budget(st, dg, t, new, step, sn, max_time, seed):
+    """one add_budget on the device's own state against the numpy rule, exactly; -> (snapshot after, first touches per type)"""
+    want = st.snapshot()
+    st.add_budget(t, step, len(new), max_time, seed)
+    got = st.snapshot()
+    fresh = _np_budget(dg, want, t, np.asarray(new, dtype=np.int64), step, sn, max_time, seed)
+    for i, name in enumerate(dg.types):
+        assert np.array_equal(got["score"][i], want["score"][i]), "score of %s" % name
+        assert np.array_equal(got["stamp"][i], want["stamp"][i]), "stamp of %s" % name
+        assert np.array_equal(np.sort(got["cand"][i]), np.union1d(want["cand"][i], fresh[i])) and got["counts"][i, 3] == 0, name
+    return got, fresh
+
+
+def _assert_induce(st, dg):
+    snap = st.snapshot()
+    src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type = st.induce()
+    times = [_stamp_time(snap["stamp"][t][snap["sampled"][t]]) for t in range(len(dg.types))]
+    for got, exp, name in zip((src, dst, etime, rel_ptr, type_off), np_induce(dg, snap["sampled"], times, snap["serial"]),
+                              ("src", "dst", "edge_time", "rel_ptr", "type_off")):
+        assert np.array_equal(got.cpu().numpy(), exp), name
+    assert n_per_type == [len(v) for v in snap["sampled"]]
+    assert np.array_equal(node_id.cpu().numpy(), np.concatenate(snap["sampled"]))
+    assert np.array_equal(node_time.cpu().numpy(), np.concatenate(times))
+    return rel_ptr.cpu().numpy()
+
+
+@pytest.fixture(scope="module")
+def tie_dev():
+    return TS.tie_graph(device=DEV)
+
+
+@pytest.mark.parametrize("extra", [0, 1])
+@pytest.mark.parametrize("name", list(TS.TIES))
+def test_add_budget_where_the_threshold_word_is_duplicated(tie_dev, name, extra):
+    """the r-th and (r + 1)-th smallest words of the row are equal (test_sampler.py, TIES): sampled_number = r needs one of the two,
+    by position; sampled_number = r + 1 needs both.  The workgroup's row has 60 000 neighbours: the tail beyond the 8192 words held in
+    registers is recomputed in every pass, and both tied positions lie in it."""
+    tie = TS.TIES[name]
+    sn = tie["r"] + extra
+    st = DeviceSamplerState(tie_dev, [1, 0], 1, sn)
+    st.clear()
+    try:
+        st.seed_nodes(0, [tie["target"]], [3], tie["step"])
+        beg = tie_dev.csr[0][0][tie["target"]]
+        p, q = (int(tie_dev.csr[0][1][beg + v]) for v in tie["positions"])
+        for max_time in (None, 4):                            # the second draw adds the same subset again, minus the newer ones
+            got, _ = _assert_budget(st, tie_dev, 0, [tie["target"]], tie["step"], sn, max_time, tie["seed"])
+        assert len(got["cand"][1]) == sn and p in got["cand"][1] and (q in got["cand"][1]) == bool(extra)
+    finally:
+        st.clear()
+
+
+def _csr_pair(n_t, n_s, tgt, src, tm):
+    """(target <- source) and its transpose as CSRs"""
+    out = []
+    for a, b, n in ((tgt, src, n_t), (src, tgt, n_s)):
+        order = np.argsort(a, kind="stable")
+        out.append((np.concatenate([[0], np.cumsum(np.bincount(a, minlength=n))]), b[order], tm[order]))
+    return out
+
+
+def _rows_graph(n_x, n_y, deg, seed):
+    """x <- y with the given degrees (distinct neighbours, a tenth of the times None) and y <- x, its transpose"""
+    rng = np.random.default_rng(seed)
+    deg = np.asarray(deg)
+    tgt = np.repeat(np.arange(n_x), deg)
+    src = np.concatenate([rng.choice(n_y, size=d, replace=False) for d in deg])
+    tm = rng.integers(1990, 2011, size=src.size)
+    tm[rng.random(src.size) < 0.1] = TIME_NONE
+    feats = {"x": np.zeros((n_x, 1), np.float32), "y": np.zeros((n_y, 1), np.float32)}
+    return DeviceHeteroGraph.from_csr(["x", "y"], [("x", "y", "xy"), ("y", "x", "rev_xy")], {"x": n_x, "y": n_y},
+                                      _csr_pair(n_x, n_y, tgt, src, tm), feats, device=DEV)
+
+
+def _hub_blocks():
+    with open(os.path.join(TS.ROOT, "pyhgt_amd", "csrc", "hgt_sampler.hip")) as f:
+        return int(re.search(r"constexpr int HUB_BLOCKS = (\d+);", f.read()).group(1))
+
+
+def test_more_hub_rows_than_hub_workgroups():
+    """300 seeds with 513 .. 600 neighbours each: the hub launches of add_budget and of both induce passes have fewer workgroups than
+    queued rows, so a workgroup takes a second row on the LDS words the first one used"""
+    n_seed, sn, max_time, seed = 300, 16, 2008, 21
+    dg = _rows_graph(304, 2000, np.random.default_rng(20).integers(513, 601, size=304), 22)
+    assert 150000 < dg.csr[0][1].size < 180000
+    st = DeviceSamplerState(dg, [n_seed, 0], 1, sn)
+    st.clear()
+    try:
+        st.seed_nodes(0, np.arange(n_seed), np.full(n_seed, 2005), 0)
+        _assert_budget(st, dg, 0, np.arange(n_seed), 0, sn, max_time, seed)
+        assert int(st.hub[0]) == n_seed > _hub_blocks()
+        n_x = n_seed
+        for t in (1, 0):                                      # y first: only its budget makes candidates of x (those that are no seeds)
+            cand = st.snapshot()["cand"][t]
+            st.select(t, 2 + t, seed)
+            new = st.snapshot()
+            new = new["sampled"][t][new["counts"][t, 1]:]
+            assert len(new) == (sn if t else len(cand)) and (t or 1 <= len(new) <= 4)
+            _assert_budget(st, dg, t, new, 2 + t, sn, max_time, seed)
+            n_x += 0 if t else len(new)
+        rel_ptr = _assert_induce(st, dg)
+        # every row of x is above the hub line and none of y: the induce queue holds the sampled nodes of x
+        assert int(st.hub[0]) == n_x > _hub_blocks() and rel_ptr[1] > 0 and rel_ptr[2] > rel_ptr[1]
+        st.reset()
+        clean = st.snapshot()
+        assert not any(a.any() for a in clean["score"] + clean["stamp"]) and all((a == -1).all() for a in clean["serial"])
+    finally:
+        st.clear()
+
+
+def test_sampled_number_at_its_limit():
+    """sampled_number = 1024: rows of 1023 / 1024 / 1025 and 9000 neighbours (no draw, no draw, a draw that drops one, a hub draw),
+    then a selection that fills chosen[] in LDS and ranks 1024 keys"""
+    sn, max_time, seed = 1024, 2008, 23
+    assert sn == TS._lib.HGT_SAMPLER_MAX_NUMBER
+    dg = _rows_graph(8, 12000, [1023, 1024, 1025, 9000, 0, 3, 0, 0], 24)
+    st = DeviceSamplerState(dg, [4, 0], 1, sn)
+    st.clear()
+    try:
+        st.seed_nodes(0, np.arange(4), np.full(4, 2005), 0)
+        got, _ = _assert_budget(st, dg, 0, np.arange(4), 0, sn, max_time, seed)
+        assert len(got["cand"][1]) > 2 * sn
+        assert _check_select(st, dg, 1, 3, seed, sn) == (sn, len(got["cand"][1]))
+        _assert_budget(st, dg, 1, st.snapshot()["sampled"][1], 3, sn, max_time, seed)
+        _assert_induce(st, dg)
+    finally:
+        st.clear()
+
+
+# ---------------------------------------------------------------------------------------------------------------- capacity guards
+# The library is told a smaller capacity than the tensor holds and the tail of the tensor is poisoned: a guard that did not hold
+# would change a poison word inside the tensor.
+POISON = -7
+
+
+def test_candidate_list_stops_at_its_capacity(lines):
+    n_seed, sn, small = 40, 8, 50
+    st = _seeded(lines, n_seed, 1, sn)
+    try:
+        assert st.cand[1].numel() >= n_seed * sn             # every first touch of this draw fits the tensor
+        st.cand[1].fill_(POISON)
+        st.types_c[1].cap_cand = small
+        want = st.snapshot()
+        st.add_budget(0, 0, n_seed, 2008, 77)
+        fresh = _np_budget(lines, want, 0, np.arange(n_seed), 0, sn, 2008, 77)
+        counts = st.counts.cpu().numpy()
+        cand = st.cand[1].cpu().numpy()
+        assert len(fresh[1]) > small and counts[1, 2] == len(fresh[1]) and counts[1, 3] == 1      # counted past the end, flagged
+        assert len(set(cand[:small].tolist())) == small and set(cand[:small].tolist()) <= set(fresh[1].tolist())
+        assert (cand[small:] == POISON).all()
+        assert np.array_equal(st.score[1].cpu().numpy().view(np.uint64), want["score"][1])        # the atomics do not depend on the list
+        assert counts[0, 3] == 0 and counts[2, 3] == 0 and np.array_equal(np.sort(st.cand[2].cpu().numpy()[:counts[2, 2]]), fresh[2])
+        with pytest.raises(RuntimeError, match="overflowed"):
+            st.induce()
+        assert (st.cand[1].cpu().numpy()[small:] == POISON).all()
+    finally:
+        st.clear()
+
+
+def test_selection_stops_at_the_capacity_of_the_sampled_list(lines):
+    n_seed, sn, room, seed = 40, 8, 3, 5
+    st = _seeded(lines, n_seed, 1, sn)
+    try:
+        assert st.sampled[0].numel() == n_seed + sn
+        st.add_budget(0, 0, n_seed, 2008, seed)
+        st.sampled[0][n_seed:] = POISON
+        st.types_c[0].cap_sampled = n_seed + room
+        before = st.snapshot()
+        cand = before["cand"][0]
+        assert len(cand) > sn
+        st.select(0, 3, seed)
+        counts = st.counts.cpu().numpy()
+        sampled = st.sampled[0].cpu().numpy()
+        assert counts[0, 0] == n_seed + room and counts[0, 1] == n_seed and counts[0, 2] == len(cand) - room and counts[0, 3] == 0
+        assert (sampled[n_seed + room:] == POISON).all() and np.array_equal(sampled[:n_seed], np.arange(n_seed))
+        chosen = sampled[n_seed:n_seed + room].astype(np.int64)
+        keys = dict(zip(cand.tolist(), np_select_keys(cand, before["score"][0], 0, 3, seed)))
+        k_chosen = np.array([keys[v] for v in chosen.tolist()])                                   # KeyError: not a candidate
+        rest = np.setdiff1d(cand, chosen)
+        assert len(rest) == len(cand) - room and np.array_equal(np.sort(st.cand[0].cpu().numpy()[:counts[0, 2]]), rest)
+        assert k_chosen.max() <= MARGIN * min(keys[v] for v in rest.tolist()) and (k_chosen[:-1] <= MARGIN * k_chosen[1:]).all()
+        serial = st.serial[0].cpu().numpy()
+        assert np.array_equal(serial[chosen], np.arange(n_seed, n_seed + room)) and (serial >= 0).sum() == n_seed + room
+    finally:
+        st.clear()
+
+
+# ---------------------------------------------------------------------------------------------------------------- state reuse
+# The per-node arrays belong to the graph and are shared by every shape of call; a call that raises half way leaves them dirty.
+_SHAPES = [next(c for c in TS.OAG_CALLS if c[0] is inp and c[2:4] == (depth, sn)) for inp, depth, sn in
+           [(TS._PAPERS, 3, 16), (TS._THREE, 3, 16), (TS._PAPERS, 1, 1), (TS._THREE, 3, 128), (TS._AFFIL, 3, 16), (TS._PAPERS, 3, 128)]]
+
+
+def _fail_on_features(dg, call):
+    """ValueError after induce(): a type that has sampled nodes and no feature matrix"""
+    i = dg.types.index("author")
+    keep, dg.features[i] = dg.features[i], None
+    try:
+        with pytest.raises(ValueError, match="no feature matrix"):
+            _call(dg, call)
+    finally:
+        dg.features[i] = keep
+
+
+def _fail_on_overflow(dg, call):
+    """RuntimeError in induce(): the candidate list of the authors told to be shorter than the call needs"""
+    st = _device_state(dg, [len(call[0].get(t, [])) for t in dg.types], call[2], call[3])
+    i = dg.types.index("author")
+    keep, st.types_c[i].cap_cand = st.types_c[i].cap_cand, 5
+    try:
+        with pytest.raises(RuntimeError, match="overflowed"):
+            _call(dg, call)
+    finally:
+        st.types_c[i].cap_cand = keep
+
+
+def _assert_right(dg, fresh, call):
+    got = _call(dg, call)
+    _assert_same(got, _call(fresh, call))
+    _assert_equals_host(got, _certified_host(dg, call), dg)
+
+
+@pytest.mark.parametrize("fail", [_fail_on_features, _fail_on_overflow], ids=["ValueError", "RuntimeError"])
+def test_a_failed_call_does_not_poison_a_call_of_another_shape(oag_dev, fail):
+    """a good call, a failing call of shape A, then shape B (other seed counts), shape C (other depth) and shape A again: each equals
+    what a freshly built graph returns and the host sibling"""
+    a, b, c = _SHAPES[:3]
+    fresh = TS.oag_graph(device=DEV)
+    _assert_right(oag_dev, fresh, a)
+    fail(oag_dev, a)
+    for call in (b, c, a):
+        _assert_right(oag_dev, fresh, call)
+    fail(oag_dev, a)
+    _assert_right(oag_dev, fresh, a)                          # the same shape straight after
+
+
+def test_a_failed_call_survives_the_eviction_of_its_state(oag_dev):
+    """the cache of states holds four shapes: the failing call is the fourth, the next shape evicts all of them, and four more shapes
+    evict again"""
+    fresh = TS.oag_graph(device=DEV)
+    oag_dev._dev_state.clear()
+    for call in _SHAPES[:3]:
+        _assert_right(oag_dev, fresh, call)
+    _fail_on_features(oag_dev, _SHAPES[3])
+    assert len(oag_dev._dev_state) == 4
+    _assert_right(oag_dev, fresh, _SHAPES[4])
+    assert len(oag_dev._dev_state) == 1
+    for call in [_SHAPES[3], _SHAPES[5]] + _SHAPES[:3]:
+        _assert_right(oag_dev, fresh, call)
+    assert len(oag_dev._dev_state) == 2
