@@ -866,6 +866,48 @@ int hgt_sampler_induce_fill(const hgt_sampler_type* types_host, int32_t n_types,
                             int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out, void* stream);
 int hgt_sampler_reset(const hgt_sampler_type* types_host, int32_t n_types, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Task batches (csrc/hgt_sampler.hip, csrc/hgt_sampler_labels.hip): what the reference's training scripts do between sample_subgraph
+ * and to_torch (OAG/train_paper_field.py:109-137 and its siblings) -- take the edges of the label relation at the output nodes out of
+ * the batch and build the labels from the same relation of the full graph.  Added under ABI 8 (new symbols only).
+ *
+ *   hgt_sampler_induce_count_masked / _fill_masked   the induce calls with one hgt_sampler_mask per triple (HOST array of n_triples
+ *                           entries; the thresholds travel as kernel arguments next to the tables).  The rule: an edge of triple m
+ *                           between the sampled target of serial i and a sampled source of serial ser is left out iff
+ *                           i < masks[m].tgt_below or ser < masks[m].src_below.  Serials are per type, and the seeds of a type are
+ *                           its first serials in the order given, so a threshold equal to the number of seeds names exactly the
+ *                           edges at the seeds.  `self` edges are never masked.  Count pass (rowoff, rel_ptr, sizes_out) and fill
+ *                           pass apply the same rule, in wavefront rows and in hub rows; the order of the surviving edges, the edge
+ *                           times and the node outputs are those of the unmasked calls; a relation may come out empty.  All-zero
+ *                           masks give the arrays of the unmasked calls bit for bit.  masks_host == NULL or a negative threshold:
+ *                           HGT_ERR_INVALID_ARG, no launch.  Both passes of one batch must be given the same masks.
+ *   hgt_sampler_labels      labels of n nodes of the triple's target type from the resident CSR.  For row r, v = ids[r]: a neighbour
+ *                           (in adjacency order) qualifies iff col_of[src] >= 0 and, with has_window != 0, its edge time is not
+ *                           HGT_SAMPLER_TIME_NONE and lies in [t_min, t_max].  C = the set of distinct columns of the qualifying
+ *                           neighbours.  dist_out[r * ld + c] = 1.0f / (float)|C| for c in C and 0 for every other c < n_cols (the
+ *                           whole row is written, the padding ld - n_cols is not touched); index_out[r] = the column of the first
+ *                           qualifying neighbour or -1; count_out[r] = |C|.  An id outside [0, n_tgt_nodes) gives a zero row, -1
+ *                           and 0.  ids, col_of (int32[n_src_nodes], -1 = no class) and the outputs are device arrays; any of the
+ *                           three outputs may be NULL.  One launch, one workgroup per row, no float atomics, the result does not
+ *                           depend on the launch geometry.  NULL table or array with n > 0, a negative size, ld < n_cols (with
+ *                           dist_out), t_min > t_max with a window: HGT_ERR_INVALID_ARG, no launch.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hgt_sampler_mask {
+    int32_t tgt_below, src_below;
+} hgt_sampler_mask;
+int hgt_sampler_induce_count_masked(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                    int32_t n_triples, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries,
+                                    int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out, const hgt_sampler_mask* masks_host,
+                                    void* stream);
+int hgt_sampler_induce_fill_masked(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                   int32_t n_triples, int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries,
+                                   const int32_t* type_off, int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out,
+                                   int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out, const hgt_sampler_mask* masks_host,
+                                   void* stream);
+int hgt_sampler_labels(const hgt_sampler_triple* triple_host, int32_t n_tgt_nodes, int32_t n_src_nodes, const int32_t* ids, int32_t n,
+                       const int32_t* col_of, int32_t n_cols, int32_t has_window, int32_t t_min, int32_t t_max, float* dist_out,
+                       int64_t ld, int32_t* index_out, int32_t* count_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,10 @@ class HgtSamplerTriple(C.Structure):
                 ("rel_id", C.c_int32), ("reserved", C.c_int32)]
 
 
+class HgtSamplerMask(C.Structure):
+    _fields_ = [("tgt_below", C.c_int32), ("src_below", C.c_int32)]
+
+
 ABI_VERSION = 8          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
 
 _i32, _i64, _u64, _vp = C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
@@ -219,6 +223,12 @@ SIGNATURES = {
     "hgt_sampler_induce_count": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "hgt_sampler_induce_fill": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hgt_sampler_reset": (C.c_int, [_vp, _i32, _vp]),
+    # task batches: the induce calls with (masks_host) in front of the stream; labels (csrc/hgt_sampler_labels.hip): (triple_host,
+    # n_tgt_nodes, n_src_nodes, ids, n, col_of, n_cols, has_window, t_min, t_max, dist_out, ld, index_out, count_out, stream)
+    "hgt_sampler_induce_count_masked": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "hgt_sampler_induce_fill_masked": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp]),
+    "hgt_sampler_labels": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _lib = None

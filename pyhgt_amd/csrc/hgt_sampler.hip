@@ -31,6 +31,10 @@
 //                           counted, scanned (one workgroup), then written relation-major in global target order with
 //                           edge_time = time[tgt] - time[src] + 120; `self` edges last.  Rows above the hub line take a workgroup,
 //                           as in add_budget.  The caller reads sizes_out between the two calls (the only host read of a batch).
+//   hgt_sampler_induce_count_masked / _fill_masked   the same two passes with a pair of thresholds per triple (task batches: the label
+//                           edges at the seeds, OAG/train_paper_field.py:109-122): an edge between the target of serial i and a source
+//                           of serial ser is left out iff i < tgt_below or ser < src_below.  The thresholds ride next to the tables
+//                           as a kernel argument; the unmasked entry points run the same kernels with all-zero thresholds.
 //   hgt_sampler_reset       walks the sampled and candidate lists and clears exactly the entries the call touched
 // No float atomics in this file; compiled without fast-math like the rest of the library.
 #include "hgt_common.h"
@@ -50,6 +54,13 @@ struct Tables {
     int32_t slot_off[HGT_SAMPLER_MAX_TRIPLES + 1];      // induce: first row slot of triple m (slots of m: cap_sampled of its target type)
     int32_t T, M;
 };
+
+// induce: one pair of thresholds per triple, next to the tables in the kernel-argument space (all zero: nothing is masked)
+struct Masks {
+    hgt_sampler_mask m[HGT_SAMPLER_MAX_TRIPLES];
+};
+// a launch carries 4 KB of arguments: the tables, the thresholds and the scalars and pointers of the induce kernels (below 128 bytes)
+static_assert(sizeof(Tables) + sizeof(Masks) + 128 <= 4096, "the argument structs of the induce kernels do not fit one launch");
 
 struct BudgetParams {
     int32_t t, step, sn, has_max, max_time, max_new, ntr;
@@ -327,13 +338,20 @@ __device__ __forceinline__ void induce_decode(const Tables& tb, int slot, int* m
     *deg = ip[*v + 1] - ip[*v];
 }
 
-// FILL = false: the number of sampled neighbours of the row -> rowoff[slot];  FILL = true: the edges, from position rowoff[slot] on
+// FILL = false: the number of sampled neighbours of the row -> rowoff[slot];  FILL = true: the edges, from position rowoff[slot] on.
+// The mask of the triple leaves out the whole row of a target with serial i < tgt_below and every source with serial < src_below; both
+// passes apply it, so the offsets of the count pass are those of the edges the fill pass writes.
 template <int G, bool FILL>
-__device__ __forceinline__ void induce_row(const Tables& tb, int m, int i, int v, int deg, int slot, int lane, int* sh, int32_t* __restrict__ rowoff,
-                                           const int32_t* __restrict__ type_off, int32_t* __restrict__ src_out, int32_t* __restrict__ dst_out,
-                                           int32_t* __restrict__ time_out, int n_edges) {
+__device__ __forceinline__ void induce_row(const Tables& tb, const hgt_sampler_mask mk, int m, int i, int v, int deg, int slot, int lane, int* sh,
+                                           int32_t* __restrict__ rowoff, const int32_t* __restrict__ type_off, int32_t* __restrict__ src_out,
+                                           int32_t* __restrict__ dst_out, int32_t* __restrict__ time_out, int n_edges) {
     const hgt_sampler_triple& tr = tb.tr[m];
     const hgt_sampler_type& S = tb.ty[tr.src_type];
+    if (i < mk.tgt_below) {                                                       // uniform over the group that owns the row
+        if constexpr (!FILL)
+            if (lane == 0) rowoff[slot] = 0;
+        return;
+    }
     const int beg = tr.indptr[v];
     int run = 0;
     int base = 0, tgt = 0, s_off = 0;
@@ -350,6 +368,7 @@ __device__ __forceinline__ void induce_row(const Tables& tb, int m, int i, int v
         if (p < deg) {
             s = tr.src[beg + p];
             if ((unsigned)s < (unsigned)S.n_nodes) ser = S.serial[s];
+            if (ser < mk.src_below) ser = -1;
         }
         int total;
         const int prefix = group_scan_flag<G>(ser >= 0, &total, sh);
@@ -368,7 +387,7 @@ __device__ __forceinline__ void induce_row(const Tables& tb, int m, int i, int v
 }
 
 template <bool FILL>
-__global__ void __launch_bounds__(256) k_induce(Tables tb, int n_slots, int32_t* __restrict__ rowoff, int32_t* __restrict__ hub,
+__global__ void __launch_bounds__(256) k_induce(Tables tb, Masks mk, int n_slots, int32_t* __restrict__ rowoff, int32_t* __restrict__ hub,
                                                 const int32_t* __restrict__ type_off, int32_t* __restrict__ src_out,
                                                 int32_t* __restrict__ dst_out, int32_t* __restrict__ time_out, int n_edges) {
     const int lane = threadIdx.x & 63;
@@ -387,13 +406,14 @@ __global__ void __launch_bounds__(256) k_induce(Tables tb, int n_slots, int32_t*
         }
         return;
     }
-    induce_row<HGT_WAVE, FILL>(tb, m, i, v, deg, slot, lane, nullptr, rowoff, type_off, src_out, dst_out, time_out, n_edges);
+    induce_row<HGT_WAVE, FILL>(tb, mk.m[m], m, i, v, deg, slot, lane, nullptr, rowoff, type_off, src_out, dst_out, time_out, n_edges);
 }
 
 template <bool FILL>
-__global__ void __launch_bounds__(BIG) k_induce_hub(Tables tb, int n_slots, int32_t* __restrict__ rowoff, const int32_t* __restrict__ hub,
-                                                    const int32_t* __restrict__ type_off, int32_t* __restrict__ src_out,
-                                                    int32_t* __restrict__ dst_out, int32_t* __restrict__ time_out, int n_edges) {
+__global__ void __launch_bounds__(BIG) k_induce_hub(Tables tb, Masks mk, int n_slots, int32_t* __restrict__ rowoff,
+                                                    const int32_t* __restrict__ hub, const int32_t* __restrict__ type_off,
+                                                    int32_t* __restrict__ src_out, int32_t* __restrict__ dst_out,
+                                                    int32_t* __restrict__ time_out, int n_edges) {
     __shared__ int sh[BIG / HGT_WAVE];
     const int n = clamp0(hub[0], n_slots);
     for (int h = blockIdx.x; h < n; h += gridDim.x) {
@@ -402,7 +422,7 @@ __global__ void __launch_bounds__(BIG) k_induce_hub(Tables tb, int n_slots, int3
         int m, i, v, deg;
         induce_decode(tb, slot, &m, &i, &v, &deg);
         if (deg <= 0) continue;
-        induce_row<BIG, FILL>(tb, m, i, v, deg, slot, threadIdx.x, sh, rowoff, type_off, src_out, dst_out, time_out, n_edges);
+        induce_row<BIG, FILL>(tb, mk.m[m], m, i, v, deg, slot, threadIdx.x, sh, rowoff, type_off, src_out, dst_out, time_out, n_edges);
     }
 }
 
@@ -623,20 +643,35 @@ static int induce_check(const hgt_sampler_type* types_host, int32_t T, const hgt
     return HGT_OK;
 }
 
-extern "C" int hgt_sampler_induce_count(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
-                                        int32_t n_triples, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries,
-                                        int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out, void* stream) {
+// the thresholds of a masked call in kernel-argument form; masks_host == NULL with masked = false: the all-zero masks of the unmasked
+// entry points, which run the same kernels
+static int make_masks(const hgt_sampler_mask* masks_host, int32_t M, bool masked, Masks* out) {
+    for (int m = 0; m < HGT_SAMPLER_MAX_TRIPLES; ++m) out->m[m] = hgt_sampler_mask{0, 0};
+    if (!masked) return HGT_OK;
+    if (!masks_host) return HGT_ERR_INVALID_ARG;
+    for (int m = 0; m < M; ++m) {
+        if (masks_host[m].tgt_below < 0 || masks_host[m].src_below < 0) return HGT_ERR_INVALID_ARG;
+        out->m[m] = masks_host[m];
+    }
+    return HGT_OK;
+}
+
+static int induce_count(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
+                        int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries, int32_t* type_off_out, int32_t* rel_ptr_out,
+                        int32_t* sizes_out, const hgt_sampler_mask* masks_host, bool masked, void* stream) {
     Tables tb;
+    Masks mk;
     int64_t slots = 0;
     if (int rc = induce_check(types_host, n_types, triples_host, n_triples, n_relations, &tb, &slots)) return rc;
+    if (int rc = make_masks(masks_host, n_triples, masked, &mk)) return rc;
     if (!rowoff || !hub || !type_off_out || !rel_ptr_out || !sizes_out) return HGT_ERR_INVALID_ARG;
     if (n_entries < slots + 1) return HGT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(hub, 0, 4, st) != hipSuccess) return HGT_ERR_LAUNCH;
     if (slots > 0) {
-        k_induce<false><<<blocks_for(slots, 4), 256, 0, st>>>(tb, (int)slots, rowoff, hub, nullptr, nullptr, nullptr, nullptr, 0);
+        k_induce<false><<<blocks_for(slots, 4), 256, 0, st>>>(tb, mk, (int)slots, rowoff, hub, nullptr, nullptr, nullptr, nullptr, 0);
         HGT_CHECK_LAUNCH();
-        k_induce_hub<false><<<(unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), BIG, 0, st>>>(tb, (int)slots, rowoff, hub, nullptr, nullptr,
+        k_induce_hub<false><<<(unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), BIG, 0, st>>>(tb, mk, (int)slots, rowoff, hub, nullptr, nullptr,
                                                                                               nullptr, nullptr, 0);
         HGT_CHECK_LAUNCH();
     }
@@ -645,13 +680,30 @@ extern "C" int hgt_sampler_induce_count(const hgt_sampler_type* types_host, int3
     return HGT_OK;
 }
 
-extern "C" int hgt_sampler_induce_fill(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
-                                       int32_t n_triples, int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries,
-                                       const int32_t* type_off, int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out,
-                                       int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out, void* stream) {
+extern "C" int hgt_sampler_induce_count(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                        int32_t n_triples, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries,
+                                        int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out, void* stream) {
+    return induce_count(types_host, n_types, triples_host, n_triples, n_relations, rowoff, hub, n_entries, type_off_out, rel_ptr_out, sizes_out,
+                        nullptr, false, stream);
+}
+
+extern "C" int hgt_sampler_induce_count_masked(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                               int32_t n_triples, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries,
+                                               int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out,
+                                               const hgt_sampler_mask* masks_host, void* stream) {
+    return induce_count(types_host, n_types, triples_host, n_triples, n_relations, rowoff, hub, n_entries, type_off_out, rel_ptr_out, sizes_out,
+                        masks_host, true, stream);
+}
+
+static int induce_fill(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
+                       int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries, const int32_t* type_off,
+                       int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out, int32_t* time_out, int32_t* node_time_out,
+                       int32_t* node_id_out, const hgt_sampler_mask* masks_host, bool masked, void* stream) {
     Tables tb;
+    Masks mk;
     int64_t slots = 0;
     if (int rc = induce_check(types_host, n_types, triples_host, n_triples, n_relations, &tb, &slots)) return rc;
+    if (int rc = make_masks(masks_host, n_triples, masked, &mk)) return rc;
     if (!rowoff || !hub || !type_off || n_nodes < 0 || n_edges < n_nodes) return HGT_ERR_INVALID_ARG;
     if (n_edges > 0x7fffffff) return HGT_ERR_TOO_LARGE;
     if (n_entries < slots + 1) return HGT_ERR_WORKSPACE;
@@ -661,11 +713,11 @@ extern "C" int hgt_sampler_induce_fill(const hgt_sampler_type* types_host, int32
     const int e_ns = (int)(n_edges - n_nodes);
     if (slots > 0 && e_ns > 0) {
         int32_t* ro = const_cast<int32_t*>(rowoff);      // the FILL instantiations only read it
-        k_induce<true><<<blocks_for(slots, 4), 256, 0, st>>>(tb, (int)slots, ro, const_cast<int32_t*>(hub), type_off, src_out, dst_out, time_out,
+        k_induce<true><<<blocks_for(slots, 4), 256, 0, st>>>(tb, mk, (int)slots, ro, const_cast<int32_t*>(hub), type_off, src_out, dst_out, time_out,
                                                             e_ns);
         HGT_CHECK_LAUNCH();
-        k_induce_hub<true><<<(unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), BIG, 0, st>>>(tb, (int)slots, ro, hub, type_off, src_out, dst_out,
-                                                                                             time_out, e_ns);
+        k_induce_hub<true><<<(unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), BIG, 0, st>>>(tb, mk, (int)slots, ro, hub, type_off, src_out,
+                                                                                             dst_out, time_out, e_ns);
         HGT_CHECK_LAUNCH();
     }
     if (n_nodes > 0) {
@@ -674,6 +726,23 @@ extern "C" int hgt_sampler_induce_fill(const hgt_sampler_type* types_host, int32
         HGT_CHECK_LAUNCH();
     }
     return HGT_OK;
+}
+
+extern "C" int hgt_sampler_induce_fill(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                       int32_t n_triples, int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries,
+                                       const int32_t* type_off, int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out,
+                                       int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out, void* stream) {
+    return induce_fill(types_host, n_types, triples_host, n_triples, n_relations, rowoff, hub, n_entries, type_off, n_nodes, n_edges, src_out,
+                       dst_out, time_out, node_time_out, node_id_out, nullptr, false, stream);
+}
+
+extern "C" int hgt_sampler_induce_fill_masked(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                              int32_t n_triples, int32_t n_relations, const int32_t* rowoff, const int32_t* hub,
+                                              int64_t n_entries, const int32_t* type_off, int64_t n_nodes, int64_t n_edges, int32_t* src_out,
+                                              int32_t* dst_out, int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out,
+                                              const hgt_sampler_mask* masks_host, void* stream) {
+    return induce_fill(types_host, n_types, triples_host, n_triples, n_relations, rowoff, hub, n_entries, type_off, n_nodes, n_edges, src_out,
+                       dst_out, time_out, node_time_out, node_id_out, masks_host, true, stream);
 }
 
 extern "C" int hgt_sampler_reset(const hgt_sampler_type* types_host, int32_t n_types, void* stream) {

@@ -20,6 +20,13 @@ The definition ("Device sampler", lists where it departs from th
            np.random.choice(p = score^2 / sum, replace = False)).  Serials follow that order; the node's time is its stamp's.
   induce   data.py:183-209, 240-250: relation-major edges, inside a relation by global target id, a target's neighbours in adjacency
            order, `self` edges last; edge_time = time[tgt] - time[src] + 120.
+  mask     (task batches, OAG/train_paper_field.py:109-122) mask = {(target type, source type, relation): (tgt_below, src_below)}: an
+           edge of that triple between the sampled target of serial i and a sampled source of serial ser is left out iff
+           i < tgt_below or ser < src_below.  Serials are per type and the seeds of a type are its first serials in the order given;
+           `self` edges are never masked; nothing else changes.  `np_induce` is the definition, `seed_edge_mask` builds the dict.
+
+Labels of a task batch come from the same relation of the full graph: `LabelSpace` (csrc/hgt_sampler_labels.hip on a device graph, the
+`np_label_*` siblings on the host).
 """
 import ctypes as C
 
@@ -30,7 +37,8 @@ from . import _lib
 from .conv import GraphPlan
 from .sampled import _DeviceGraph
 
-__all__ = ["DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "philox4x32_10"]
+__all__ = ["DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "philox4x32_10", "seed_edge_mask", "LabelSpace",
+           "np_label_distribution", "np_label_index", "np_label_counts"]
 
 TIME_NONE = _lib.HGT_SAMPLER_TIME_NONE
 _SUBSET_TAG, _SELECT_TAG = 0x10000, 0x20000
@@ -192,6 +200,42 @@ def _check_args(dgraph, sampled_depth, sampled_number):
         raise ValueError("pyhgt_amd: sampled_depth >= 0 and 1 <= sampled_number <= %d" % _lib.HGT_SAMPLER_MAX_NUMBER)
 
 
+def _mask_table(dgraph, mask):
+    """mask = {(target type, source type, relation): (tgt_below, src_below)} -> int32 [n_triples, 2] in the order of dgraph.triples, or
+    None for None / {} (the unmasked call).  A table that went through here passes unchanged."""
+    if isinstance(mask, np.ndarray):
+        return mask
+    if not mask:
+        return None
+    table = np.zeros((len(dgraph.triples), 2), np.int32)
+    where = {tri: m for m, tri in enumerate(dgraph.triples)}
+    for tri, pair in mask.items():
+        if tuple(tri) not in where:
+            raise KeyError("pyhgt_amd: %r is not a meta triple of the graph" % (tri,))
+        tgt_below, src_below = (int(v) for v in pair)
+        if tgt_below < 0 or src_below < 0:
+            raise ValueError("pyhgt_amd: mask thresholds of %r are negative" % (tri,))
+        table[where[tuple(tri)]] = (min(tgt_below, 2 ** 31 - 1), min(src_below, 2 ** 31 - 1))
+    return table
+
+
+def seed_edge_mask(dgraph, relations, node_type, below):
+    """The mask that takes the edges of `relations` at the first `below` nodes of `node_type` out of a batch: for every meta triple
+    whose relation is in `relations`, tgt_below = below if its target type is node_type and src_below = below if its source type is.
+    seed_edge_mask(dg, ["PF_in_L2", "rev_PF_in_L2"], "paper", batch_size) is the masking step of the reference's
+    node_classification_sample (train_paper_field.py:109-122) when the papers to classify are the first seeds."""
+    relations, below = set(relations), int(below)
+    if node_type not in dgraph.types:
+        raise KeyError("pyhgt_amd: %r is not a node type of the graph" % (node_type,))
+    if below < 0:
+        raise ValueError("pyhgt_amd: mask thresholds are not negative")
+    unknown = relations - {rel for _, _, rel in dgraph.triples}
+    if unknown:
+        raise KeyError("pyhgt_amd: %r are not relations of the graph" % sorted(unknown))
+    return {(tt, st, rel): (below if tt == node_type else 0, below if st == node_type else 0)
+            for tt, st, rel in dgraph.triples if rel in relations}
+
+
 # ---------------------------------------------------------------------------------------------------------------- numpy rule
 def _flat_rows(indptr, targets):
     """positions of all neighbours of `targets` (in order) -> (flat positions, row index of each, degree per row)"""
@@ -251,17 +295,21 @@ def np_select(ids, score, t, step, seed, sn):
     return ids[np.lexsort((ids, keys))[:min(sn, ids.size)]]
 
 
-def np_induce(dgraph, sampled, times, serial):
+def np_induce(dgraph, sampled, times, serial, mask=None):
     """data.py:183-209 + 240-250 over the node lists `sampled[t]` (ids in serial order), their times and the serial arrays:
-    -> (src, dst, edge_time, rel_ptr, type_off) in the sorted int32 form."""
+    -> (src, dst, edge_time, rel_ptr, type_off) in the sorted int32 form.  mask (the dict of the module docstring): an edge of triple m
+    from the source of serial `ser` to the target of serial `row` is left out iff row < tgt_below[m] or ser < src_below[m]."""
     T, R = len(dgraph.types), len(dgraph.edge_dict)
+    table = _mask_table(dgraph, mask)
     type_off = np.concatenate([[0], np.cumsum([len(sampled[t]) for t in range(T)])]).astype(np.int64)
     srcs, dsts, tms, per_rel = [], [], [], np.zeros(R, np.int64)
-    for (tt, st, rel), (indptr, src, _) in zip(dgraph.tri_types, dgraph.csr):
+    for m, ((tt, st, rel), (indptr, src, _)) in enumerate(zip(dgraph.tri_types, dgraph.csr)):
         flat, row, _, _ = _flat_rows(indptr, np.asarray(sampled[tt], dtype=np.int64))
         s = src[flat].astype(np.int64)
         ser = serial[st][s].astype(np.int64)
         ok = ser >= 0
+        if table is not None:
+            ok &= (row >= table[m, 0]) & (ser >= table[m, 1])
         srcs.append(ser[ok] + type_off[st])
         dsts.append(row[ok] + type_off[tt])
         tms.append(np.asarray(times[tt], dtype=np.int64)[row[ok]] - np.asarray(times[st], dtype=np.int64)[ser[ok]] + 120)
@@ -274,12 +322,25 @@ def np_induce(dgraph, sampled, times, serial):
     return cat(srcs), cat(dsts), cat(tms), rel_ptr.astype(np.int32), type_off.astype(np.int32)
 
 
-class _HostGraph(tuple):
-    """Result of sample_subgraph_host: the 7-tuple of to_torch (CPU tensors) with `.sorted` (numpy), `.indxs` and `.times`."""
+class _Seeds:
+    """what a sampled result knows about its seeds: `.n_seed` = {type: count}; the seeds of a type are its first nodes"""
+    n_seed = None
+
+    def seed_rows(self, node_type):
+        """global rows (int64 tensor on the result's device) of the seeds of `node_type`, in the order given: `x_ids` of the scripts"""
+        return self[5][node_type][0] + torch.arange(self.n_seed[node_type], dtype=torch.int64, device=self[1].device)
+
+
+class _HostGraph(_Seeds, tuple):
+    """Result of sample_subgraph_host: the 7-tuple of to_torch (CPU tensors) with `.sorted` (numpy), `.indxs`, `.times`, `.n_seed`."""
     sorted = None
     indxs = None
     times = None
     plan = None
+
+
+class _SampledDeviceGraph(_Seeds, _DeviceGraph):
+    """Result of sample_subgraph_device: a `_DeviceGraph` with `.indxs`, `.times` and `.n_seed`."""
 
 
 def _wire_tuple(cls, dgraph, feat, n_per_type, src, dst, etime, rel_ptr, type_off):
@@ -297,11 +358,12 @@ def _wire_tuple(cls, dgraph, feat, n_per_type, src, dst, etime, rel_ptr, type_of
     return cls((feat, node_type, etime.long(), edge_index, edge_type, node_dict, dict(dgraph.edge_dict)))
 
 
-def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, seed, trace=None):
+def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, seed, trace=None, mask=None):
     """numpy sibling of `sample_subgraph_device`: the same definition on the host copy of the graph.  Returns a `_HostGraph`.
     trace: a list that receives, per select step, (type index, step, candidate ids, their float64 keys) -- what decides whether a
-    fp32 key order can differ from this one (tests)."""
+    fp32 key order can differ from this one (tests).  mask: the edges to leave out of the induced graph (module docstring)."""
     _check_args(dgraph, sampled_depth, sampled_number)
+    table = _mask_table(dgraph, mask)
     T, sn = len(dgraph.types), int(sampled_number)
     seeds = _seed_arrays(dgraph, inp)
     if dgraph._host_state is None:
@@ -338,7 +400,7 @@ def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, s
                 cand[t] = np.setdiff1d(cand[t], new)
                 add_budget(t, new, step)
         times = [_stamp_time(stamp[t][sampled[t]]) for t in range(T)]
-        src, dst, etime, rel_ptr, type_off = np_induce(dgraph, sampled, times, serial)
+        src, dst, etime, rel_ptr, type_off = np_induce(dgraph, sampled, times, serial, table)
     finally:                                                 # walk the lists the call touched
         for t in range(T):
             for ids in (sampled[t], cand[t]):
@@ -352,6 +414,7 @@ def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, s
     out.sorted = (src, dst, etime, rel_ptr, type_off)
     out.indxs = {name: sampled[t] for t, name in enumerate(dgraph.types)}
     out.times = {name: times[t] for t, name in enumerate(dgraph.types)}
+    out.n_seed = {name: int(seeds[t][0].size) for t, name in enumerate(dgraph.types)}
     return out
 
 
@@ -430,12 +493,21 @@ class DeviceSamplerState:
         _lib.check(self.lib.hgt_sampler_select(self.types_c, self.T, t, step, self.sn, seed & (2 ** 64 - 1), self.keys.data_ptr(),
                                                self.tmp.data_ptr(), self.tmp.numel(), self._stream()), "hgt_sampler_select")
 
-    def induce(self):
-        """count pass, the one host read, fill pass -> (src, dst, edge_time, rel_ptr, type_off, node_time, node_id, nodes per type)"""
+    def induce(self, mask=None):
+        """count pass, the one host read, fill pass -> (src, dst, edge_time, rel_ptr, type_off, node_time, node_id, nodes per type).
+        mask (dict or the table of _mask_table): the masked entry points, the same launches with the thresholds as one more argument;
+        None or {}: the unmasked ones."""
         lib, T, M = self.lib, self.T, self.M
-        _lib.check(lib.hgt_sampler_induce_count(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(),
-                                                self.n_entries, self.type_off.data_ptr(), self.rel_ptr.data_ptr(), self.sizes.data_ptr(),
-                                                self._stream()), "hgt_sampler_induce_count")
+        table = _mask_table(self.g, mask)
+        if table is None:
+            count, fill, tail, what = lib.hgt_sampler_induce_count, lib.hgt_sampler_induce_fill, (), "hgt_sampler_induce"
+        else:
+            masks_c = (_lib.HgtSamplerMask * max(M, 1))()
+            for m in range(M):
+                masks_c[m] = _lib.HgtSamplerMask(int(table[m, 0]), int(table[m, 1]))
+            count, fill, tail, what = lib.hgt_sampler_induce_count_masked, lib.hgt_sampler_induce_fill_masked, (masks_c,), "hgt_sampler_induce_masked"
+        _lib.check(count(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
+                         self.type_off.data_ptr(), self.rel_ptr.data_ptr(), self.sizes.data_ptr(), *tail, self._stream()), what + " (count)")
         sizes = self.sizes.cpu().numpy()                     # the host synchronisation of the batch
         if sizes[T + M]:
             raise RuntimeError("pyhgt_amd: a sampler list overflowed its static capacity or a seed id was out of range")
@@ -445,9 +517,9 @@ class DeviceSamplerState:
         src, dst, etime = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
         node_time, node_id = torch.empty(N, **i32), torch.empty(N, **i32)
         ptr = lambda t: t.data_ptr() if t.numel() else None
-        _lib.check(lib.hgt_sampler_induce_fill(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(),
-                                               self.n_entries, self.type_off.data_ptr(), N, E, ptr(src), ptr(dst), ptr(etime), ptr(node_time),
-                                               ptr(node_id), self._stream()), "hgt_sampler_induce_fill")
+        _lib.check(fill(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
+                        self.type_off.data_ptr(), N, E, ptr(src), ptr(dst), ptr(etime), ptr(node_time), ptr(node_id), *tail, self._stream()),
+                   what + " (fill)")
         return src, dst, etime, self.rel_ptr.clone(), self.type_off.clone(), node_time, node_id, n_per_type
 
     def reset(self):
@@ -484,14 +556,18 @@ def _device_state(dgraph, n_seed, depth, sn):
     return st
 
 
-def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp, seed, plan=True):
+def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp, seed, plan=True, mask=None):
     """Sibling of `sample_subgraph` + `to_torch` (data.py:87-256) on the device: seeds `inp = {type: [[id, time], ...]}` -> the
     `_DeviceGraph` 7-tuple (node_feature, node_type, edge_time, edge_index, edge_type, node_dict, edge_dict) with `.sorted`, `.plan`
     (plan=False: none, for pieces that will only be stacked), `.indxs` = {type: original ids, int64 device tensor} and `.times`.
     max_time=None: no time filter (the ogbn-mag variant).  Kernel launches are enqueued for seeds and every (layer, type) without a host
-    synchronisation; the single device->host read is the sizes of the result.  The result goes straight into `stack_device_graphs`."""
+    synchronisation; the single device->host read is the sizes of the result.  The result goes straight into `stack_device_graphs`.
+    mask = {(target type, source type, relation): (tgt_below, src_below)} leaves edges out of the induced graph (module docstring;
+    `seed_edge_mask` builds the one of a task batch) inside the induction kernels: no further launch, no further host read.  `.n_seed`
+    and `.seed_rows(type)` name the seeds' rows in the result."""
     _check_args(dgraph, sampled_depth, sampled_number)
     seeds = _seed_arrays(dgraph, inp)
+    table = _mask_table(dgraph, mask)
     T, sn, seed = len(dgraph.types), int(sampled_number), int(seed)
     if dgraph.device is None or dgraph.device.type != "cuda":
         raise RuntimeError("pyhgt_amd: sample_subgraph_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host sibling is "
@@ -516,7 +592,7 @@ def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp,
                 step = T * (1 + layer) + t
                 st.select(t, step, seed)
                 st.add_budget(t, step, sn, max_time, seed)
-        src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type = st.induce()
+        src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type = st.induce(table)
         N = sum(n_per_type)
         widths = sorted({f.size(1) for f in dgraph.features if f is not None and f.size(0) > 0})
         if len(widths) > 1:
@@ -532,12 +608,157 @@ def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp,
                                                   feat[off:].data_ptr(), stream), "hgt_gather_rows")
             off += n
         st.reset()
-        out = _wire_tuple(_DeviceGraph, dgraph, feat, n_per_type, src, dst, etime, rel_ptr, type_off)
+        out = _wire_tuple(_SampledDeviceGraph, dgraph, feat, n_per_type, src, dst, etime, rel_ptr, type_off)
         out.sorted = (src, dst, etime, rel_ptr, type_off)
         ids64, offs = node_id.long(), np.concatenate([[0], np.cumsum(n_per_type)])
         out.indxs = {name: ids64[offs[t]:offs[t + 1]] for t, name in enumerate(dgraph.types)}
         out.times = {name: node_time[offs[t]:offs[t + 1]] for t, name in enumerate(dgraph.types)}
+        out.n_seed = {name: int(seeds[t][0].size) for t, name in enumerate(dgraph.types)}
         if plan:
             out.plan = GraphPlan.from_sorted(out[1], out[3], out[4], out[2], src, dst, etime, rel_ptr, type_off, T, st.R)
             GraphPlan.register(out.plan, out[1], out[3], out[4], out[2], T, st.R)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- task labels
+# The labels of a task batch come from the label relation of the FULL graph (train_paper_field.py:133-137, train_paper_venue.py:134),
+# not from the sampled one, whose label edges at the seeds the mask took out.  For a row of the triple's CSR, a neighbour qualifies iff
+# it has a class column (col_of[src] >= 0) and, when a window [t_min, t_max] is given, its edge time is not None and lies inside; C is
+# the set of distinct columns of the qualifying neighbours.  distribution = 1 / |C| on C (float32, the IEEE quotient), index = the
+# column of the first qualifying neighbour in adjacency order (-1 without one), counts = |C|.  An id outside the target type gives a
+# zero row, -1 and 0.
+def _window(t_min, t_max):
+    """-> (has_window, t_min, t_max) as int32 values; one open end is unbounded"""
+    if t_min is None and t_max is None:
+        return 0, 0, 0
+    lo, hi = (-2 ** 31 if t_min is None else int(t_min)), (2 ** 31 - 1 if t_max is None else int(t_max))
+    if lo > hi:
+        raise ValueError("pyhgt_amd: the window [%d, %d] is empty" % (lo, hi))
+    return 1, max(lo, -2 ** 31), min(hi, 2 ** 31 - 1)
+
+
+def _np_qualifying(csr, col_of, ids, t_min, t_max):
+    """-> (row of each qualifying neighbour in adjacency order, its column, its edge time) for the rows `ids` of one CSR"""
+    indptr, src, time = csr
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    valid = np.nonzero((ids >= 0) & (ids < indptr.size - 1))[0]
+    flat, row, _, _ = _flat_rows(indptr, ids[valid])
+    col, tm = np.asarray(col_of, dtype=np.int64)[src[flat]], time[flat].astype(np.int64)
+    ok = col >= 0
+    has, lo, hi = _window(t_min, t_max)
+    if has:
+        ok &= (tm != TIME_NONE) & (tm >= lo) & (tm <= hi)
+    return valid[row[ok]], col[ok], tm[ok]
+
+
+def np_label_counts(dgraph, triple, col_of, ids, t_min=None, t_max=None):
+    """|C| per row: int64 [n]"""
+    ids = np.asarray(ids).reshape(-1)
+    row, col, _ = _np_qualifying(dgraph.csr[dgraph.triples.index(tuple(triple))], col_of, ids, t_min, t_max)
+    pairs = np.unique(np.stack([row, col], axis=1), axis=0) if row.size else np.zeros((0, 2), np.int64)
+    return np.bincount(pairs[:, 0], minlength=ids.size).astype(np.int64)
+
+
+def np_label_distribution(dgraph, triple, col_of, n_cols, ids, t_min=None, t_max=None):
+    """`ylabel` of train_paper_field.py:133-137: float32 [n, n_cols], 1 / |C| in the columns of C"""
+    ids = np.asarray(ids).reshape(-1)
+    row, col, _ = _np_qualifying(dgraph.csr[dgraph.triples.index(tuple(triple))], col_of, ids, t_min, t_max)
+    member = np.zeros((ids.size, int(n_cols)), bool)
+    member[row, col] = True
+    count = member.sum(axis=1)
+    value = np.float32(1.0) / np.maximum(count, 1).astype(np.float32)
+    return np.where(member, value[:, None], np.float32(0.0)).astype(np.float32)
+
+
+def np_label_index(dgraph, triple, col_of, ids, t_min=None, t_max=None):
+    """the class of train_paper_venue.py:159-170 + :134 (the first source in the window wins): int64 [n], -1 without one"""
+    ids = np.asarray(ids).reshape(-1)
+    row, col, _ = _np_qualifying(dgraph.csr[dgraph.triples.index(tuple(triple))], col_of, ids, t_min, t_max)
+    out = np.full(ids.size, -1, np.int64)
+    rows, first = np.unique(row, return_index=True)
+    out[rows] = col[first]
+    return out
+
+
+class LabelSpace:
+    """The classes of one task: `candidates` = the source ids of the meta triple `triple` = (target type, source type, relation) in class
+    order (`cand_list` of the scripts); a target node's labels are the classes of its neighbours in that relation of the full graph.
+    The id -> column map is built once and lives on the device when the graph does; there `distribution` / `index` / `counts` are one
+    launch of csrc/hgt_sampler_labels.hip on the current stream without a synchronisation, and `ids` may be a device tensor (e.g.
+    `g.indxs["paper"][:n]`) or a host array.  On a host graph they return what the numpy siblings `np_label_*` return, as CPU tensors."""
+
+    def __init__(self, dgraph, triple, candidates):
+        triple = tuple(triple)
+        if triple not in dgraph.triples:
+            raise KeyError("pyhgt_amd: %r is not a meta triple of the graph" % (triple,))
+        self.g, self.triple, self.m = dgraph, triple, dgraph.triples.index(triple)
+        self.n_tgt, self.n_src = (dgraph.n_nodes[t] for t in dgraph.tri_types[self.m][:2])
+        cand = np.asarray(candidates, dtype=np.int64).reshape(-1)
+        if cand.size and (cand.min() < 0 or cand.max() >= self.n_src):
+            raise IndexError("pyhgt_amd: candidate ids outside [0, %d)" % self.n_src)
+        if np.unique(cand).size != cand.size:
+            raise ValueError("pyhgt_amd: candidate ids repeat")
+        self.candidates, self.n_cols = cand, int(cand.size)
+        self.col_of = np.full(self.n_src, -1, np.int32)
+        self.col_of[cand] = np.arange(cand.size, dtype=np.int32)
+        self.device = dgraph.device
+        if self.device is not None:
+            self.col_of_dev = torch.from_numpy(self.col_of).to(self.device)
+            ip, src, tm = dgraph.csr_dev[self.m]
+            ptr = lambda t: t.data_ptr() if t.numel() else None
+            self._triple_c = _lib.HgtSamplerTriple(ip.data_ptr(), ptr(src), ptr(tm), *dgraph.tri_types[self.m], 0)
+
+    def _device_ids(self, ids):
+        ids = torch.as_tensor(ids).reshape(-1).to(self.device)
+        outside = (ids < 0) | (ids >= self.n_tgt)                                # also what an int64 id would wrap to
+        return torch.where(outside, torch.full_like(ids, -1), ids).to(torch.int32).contiguous()
+
+    def _launch(self, ids, t_min, t_max, dist=None, index=None, count=None):
+        has, lo, hi = _window(t_min, t_max)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().hgt_sampler_labels(C.byref(self._triple_c), self.n_tgt, self.n_src, ids.data_ptr() if ids.numel() else None,
+                                                      ids.numel(), self.col_of_dev.data_ptr() if self.n_src else None, self.n_cols, has, lo, hi,
+                                                      None if dist is None or not dist.numel() else dist.data_ptr(),
+                                                      0 if dist is None else max(dist.stride(0), self.n_cols),
+                                                      None if index is None else index.data_ptr(), None if count is None else count.data_ptr(),
+                                                      torch.cuda.current_stream(self.device).cuda_stream), "hgt_sampler_labels")
+            ids.record_stream(torch.cuda.current_stream(self.device))
+
+    def distribution(self, ids, t_min=None, t_max=None, out=None):
+        """float32 [n, C]: 1 / |C_r| in the columns of row r's classes (`ylabel` of the paper-field script).  out: a float32 device
+        tensor [n, C] with unit column stride -- e.g. the first C columns of a wider one -- whose rows the kernel writes whole."""
+        if self.device is None:
+            return torch.from_numpy(np_label_distribution(self.g, self.triple, self.col_of, self.n_cols, ids, t_min, t_max))
+        ids = self._device_ids(ids)
+        if out is None:
+            out = torch.empty(ids.numel(), self.n_cols, dtype=torch.float32, device=self.device)
+        elif (out.dtype != torch.float32 or out.device != ids.device or out.shape != (ids.numel(), self.n_cols)
+              or (out.numel() and (out.stride(1) != 1 and self.n_cols > 1 or out.stride(0) < self.n_cols))):
+            raise ValueError("pyhgt_amd: out must be a float32 [n, %d] tensor on the graph's device with unit column stride" % self.n_cols)
+        self._launch(ids, t_min, t_max, dist=out)
+        return out
+
+    def index(self, ids, t_min=None, t_max=None):
+        """int64 [n]: the class of the first qualifying neighbour (the paper-venue script), -1 without one"""
+        if self.device is None:
+            return torch.from_numpy(np_label_index(self.g, self.triple, self.col_of, ids, t_min, t_max))
+        ids = self._device_ids(ids)
+        out = torch.empty(ids.numel(), dtype=torch.int32, device=self.device)
+        self._launch(ids, t_min, t_max, index=out)
+        return out.long()
+
+    def counts(self, ids, t_min=None, t_max=None):
+        """int64 [n]: the number of distinct classes per row"""
+        if self.device is None:
+            return torch.from_numpy(np_label_counts(self.g, self.triple, self.col_of, ids, t_min, t_max))
+        ids = self._device_ids(ids)
+        out = torch.empty(ids.numel(), dtype=torch.int32, device=self.device)
+        self._launch(ids, t_min, t_max, count=out)
+        return out.long()
+
+    def targets(self, t_min=None, t_max=None):
+        """host numpy, for set-up time: (ids, times) of the target nodes with at least one qualifying neighbour, the time that of the
+        first qualifying edge -- what train_pairs / valid_pairs / test_pairs of the scripts hold for a time range"""
+        row, _, tm = _np_qualifying(self.g.csr[self.m], self.col_of, np.arange(self.n_tgt), t_min, t_max)
+        ids, first = np.unique(row, return_index=True)
+        return ids.astype(np.int64), tm[first].astype(np.int64)

@@ -4,6 +4,11 @@ host sibling's output, on MAG- and OAG-shaped synthetic resident graphs (the sch
 shapes: 128 seed papers, depth 6, width 128 (OAG/train_paper_field.py) and width 520 (ogbn-mag/train_ogbn_mag.py:44-55).
 
     python tools/bench_sampler.py [--papers 200000] [--reps 10] [--host-reps 2] [--out profiles/r11_device_sampler.json]
+    python tools/bench_sampler.py --task [--out profiles/r12_task_batches.json]
+
+--task times a task batch instead (the OAG workload only): the call with the label edges at the 128 seed papers masked out
+(mask=seed_edge_mask(...), the same launches as the plain call) against the plain call, alternating in one process, medians of 8 each;
+and LabelSpace.distribution / LabelSpace.index for the 128 seeds (one launch each).
 
 Device time is wall-clock per call with a synchronisation after each (the call synchronises once by itself, for the sizes of the
 result); launches per batch are counted from the calls the host loop makes (every C entry point is a fixed number of launches).  One
@@ -20,7 +25,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "examples"))
-from pyhgt_amd import sample_subgraph_device, sample_subgraph_host  # noqa: E402
+from pyhgt_amd import LabelSpace, sample_subgraph_device, sample_subgraph_host, seed_edge_mask  # noqa: E402
 from pyhgt_amd.sampled import SchemaGraph, to_device_graph  # noqa: E402
 from train_device_sampler import resident_graph  # noqa: E402
 
@@ -57,6 +62,50 @@ def hand_over(res, dgraph):
     return feature, res.times, edge_list, SchemaGraph(types, dgraph.get_meta_graph())
 
 
+def _timed(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def task_line(a, dev):
+    """masked against plain call, alternating in the same windows, and the two label calls, on the OAG workload"""
+    name = "oag_d6_w128"
+    schema, depth, width, max_time = WORKLOADS[name]
+    dgraph, n_nodes = resident_graph(schema, a.papers, a.feat_dim, dev, seed=1, mean_degree=a.mean_degree)
+    relations = ["PF_in_L2", "rev_PF_in_L2", "PV_Journal", "rev_PV_Journal"]
+    mask = seed_edge_mask(dgraph, relations, "paper", 128)
+    fields = LabelSpace(dgraph, ("paper", "field", "PF_in_L2"), np.arange(n_nodes["field"]))
+    venues = LabelSpace(dgraph, ("paper", "venue", "PV_Journal"), np.arange(n_nodes["venue"]))
+    rng = np.random.default_rng(7)
+    reps = 8
+    inps = [{"paper": np.stack([rng.choice(n_nodes["paper"], 128, replace=False), np.full(128, 2015)], axis=1)} for _ in range(reps + 2)]
+    for i in range(2):                                       # warm-up of both forms and of the label kernel
+        g = sample_subgraph_device(dgraph, max_time, depth, width, inps[i], seed=i, mask=mask if i else None)
+        fields.distribution(g.indxs["paper"][:128]), venues.index(g.indxs["paper"][:128])
+    torch.cuda.synchronize()
+    t = dict(plain=[], masked=[], distribution=[], index=[])
+    removed = []
+    for i in range(reps):
+        order = [("plain", None), ("masked", mask)] if i % 2 == 0 else [("masked", mask), ("plain", None)]
+        got = {}
+        for key, m in order:
+            dt, got[key] = _timed(lambda: sample_subgraph_device(dgraph, max_time, depth, width, inps[2 + i], seed=100 + i, mask=m))
+            t[key].append(dt)
+        removed.append(int(got["plain"][4].numel() - got["masked"][4].numel()))
+        seeds = got["masked"].indxs["paper"][:128]
+        t["distribution"].append(_timed(lambda: fields.distribution(seeds))[0])
+        t["index"].append(_timed(lambda: venues.index(seeds))[0])
+    ms = lambda v: float(np.median(v) * 1e3)
+    spread = lambda v: [float(np.min(v) * 1e3), float(np.max(v) * 1e3)]
+    return dict(workload=name + "_task", papers=a.papers, seeds=128, depth=depth, width=width, reps=reps, masked_relations=relations,
+                batch_edges=int(got["plain"][4].numel()), edges_masked_median=int(np.median(removed)),
+                launches_per_batch=launches_per_batch(dgraph, depth), plain_ms=ms(t["plain"]), plain_ms_min_max=spread(t["plain"]),
+                masked_ms=ms(t["masked"]), masked_ms_min_max=spread(t["masked"]), label_classes=[fields.n_cols, venues.n_cols],
+                label_distribution_ms=ms(t["distribution"]), label_index_ms=ms(t["index"]), label_launches=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--papers", type=int, default=200000)
@@ -65,9 +114,13 @@ def main():
     ap.add_argument("--feat-dim", type=int, default=128)
     ap.add_argument("--mean-degree", type=float, default=3.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--task", action="store_true")
     a = ap.parse_args()
     dev, lines = "cuda:0", []
-    for name, (schema, depth, width, max_time) in WORKLOADS.items():
+    if a.task:
+        lines.append(task_line(a, dev))
+        print(json.dumps(lines[0]), flush=True)
+    for name, (schema, depth, width, max_time) in ({} if a.task else WORKLOADS).items():
         dgraph, n_nodes = resident_graph(schema, a.papers, a.feat_dim, dev, seed=1, mean_degree=a.mean_degree)
         rng = np.random.default_rng(7)
         inps = [{"paper": np.stack([rng.choice(n_nodes["paper"], 128, replace=False), np.full(128, 2015)], axis=1)} for _ in range(a.reps + 2)]
