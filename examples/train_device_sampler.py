@@ -5,7 +5,8 @@ sample_subgraph_device (instead of sample_subgraph + to_torch on the host) -> GN
 
     python examples/train_device_sampler.py [--schema mag|oag] [--steps 30] [--stack B] [--papers 20000]
 
---stack B: B sampled batches per optimizer step, stacked on the device (stack_device_graphs); the pieces are sampled without a plan.
+--stack B: B sampled batches per optimizer step, drawn by one sample_subgraphs_device call (one pass of launches, one host read) and
+stacked on the device (stack_device_graphs); the pieces are sampled without a plan.  --stack 1 is the single call.
 The datasets are not available offline, so the task is synthetic: a paper's label is a fixed random projection of its features."""
 import argparse
 import os
@@ -16,7 +17,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pyhgt_amd import GNN, Classifier, DeviceHeteroGraph, sample_subgraph_device  # noqa: E402
+from pyhgt_amd import GNN, Classifier, DeviceHeteroGraph, sample_subgraph_device, sample_subgraphs_device  # noqa: E402
+from pyhgt_amd._lib import HGT_SAMPLER_MAX_BATCH  # noqa: E402
 from pyhgt_amd.sampled import MAG_META, OAG_META, stack_device_graphs  # noqa: E402
 from pyhgt_amd.synth import synthetic_hetero_csr  # noqa: E402
 
@@ -52,11 +54,18 @@ def run(schema="mag", steps=30, n_paper=20000, n_hid=128, n_heads=8, n_layers=2,
     losses, t_sample, t0 = [], 0.0, time.perf_counter()
     for step in range(steps):
         ts = time.perf_counter()
-        pieces = []
+        inps = []
         for b in range(stack):
             ids = rng.choice(n_nodes["paper"], size=batch_size, replace=False)
-            inp = {"paper": np.stack([ids, np.full(batch_size, 2015)], axis=1)}
-            pieces.append(sample_subgraph_device(dgraph, 2015, depth, width, inp, seed=seed * 100003 + step * stack + b, plan=stack == 1))
+            inps.append({"paper": np.stack([ids, np.full(batch_size, 2015)], axis=1)})
+        keys = [seed * 100003 + step * stack + b for b in range(stack)]
+        if stack == 1:
+            pieces = [sample_subgraph_device(dgraph, 2015, depth, width, inps[0], seed=keys[0])]
+        else:                                                               # the same pieces as `stack` single calls, bit for bit
+            pieces = []
+            for lo in range(0, stack, HGT_SAMPLER_MAX_BATCH):
+                hi = min(stack, lo + HGT_SAMPLER_MAX_BATCH)
+                pieces += sample_subgraphs_device(dgraph, 2015, depth, width, inps[lo:hi], keys[lo:hi], plan=False)
         if stack == 1:
             g, seeds = pieces[0], slice(0, batch_size)                      # the seeds are the first papers of the batch
         else:

@@ -908,6 +908,73 @@ int hgt_sampler_labels(const hgt_sampler_triple* triple_host, int32_t n_tgt_node
                        const int32_t* col_of, int32_t n_cols, int32_t has_window, int32_t t_min, int32_t t_max, float* dist_out,
                        int64_t ld, int32_t* index_out, int32_t* count_out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Batched device sampler (csrc/hgt_sampler.hip; sample_subgraphs_device): n_batch independent batches (replicas) that share the
+ * resident graph and nothing else, drawn by ONE pass of the launches of a single batch -- replica b of every launch is blockIdx.y = b.
+ * Added under ABI 8 (new symbols only); the single entry points above keep their signatures, their kernels and their bits.
+ *
+ * Form: explicit arguments.  Every entry point is its single sibling with n_batch behind the tables and these rules:
+ *   state        the tables are those of ONE replica (replica 0) and travel as kernel arguments as before; replica b's arrays are
+ *                the table's pointers shifted by b strides, and every stride is a field of the tables: score / stamp / serial by
+ *                n_nodes, sampled by cap_sampled, cand by cap_cand, counts by 4 * n_types.  So score is u64[n_batch][n_nodes],
+ *                sampled int32[n_batch][cap_sampled], counts of type t int32[n_batch][n_types][4] + 4 * t, and so on.
+ *   scratch      sizes (hub_entries, tmp_entries, n_entries) are PER REPLICA, exactly the single call's requirement, and the arrays
+ *                hold n_batch times as much: keys u64[n_batch][tmp_entries], tmp int32[n_batch][tmp_entries], rowoff
+ *                int32[n_batch][n_entries].  hub int32[n_batch * hub_entries]: the n_batch queue counters first (one memset),
+ *                then replica b's queue entries at hub + n_batch + b * (hub_entries - 1) -- every replica's queue is its own.
+ *   inputs       ids / times int32[n_batch][n]; seeds_host: HOST array of n_batch Philox keys, which ride in the kernel-argument
+ *                space next to the tables (that is what bounds HGT_SAMPLER_MAX_BATCH: tables + parameters + 8 bytes per replica
+ *                within the 4 KB of arguments of a launch).  type, step, sampled_number, max_new, max_time and the masks are shared.
+ *   count pass   type_off_out int32[n_batch][T + 1], rel_ptr_out int32[n_batch][R + 1], sizes_out int32[n_batch][T + M + 2]: the one
+ *                array the host reads per batched call.  Replica b raises its own overflow flag, sizes_out[b][T + M].
+ *   fill pass    n_nodes / n_edges are the totals over the replicas; src_out / dst_out / time_out int32[n_edges] and node_time_out /
+ *                node_id_out int32[n_nodes] hold the replicas one after the other, indices local to each piece exactly as a single
+ *                call writes them.  offs_out int32[2 * (n_batch + 1)] receives the node prefix sums over b, then the edge prefix sums
+ *                (one more launch, from `sizes`, the array of the count pass); a replica whose range does not lie inside the totals
+ *                writes nothing.  The masked forms take the one mask table for all replicas.
+ *   hgt_sampler_gather_features   the feature rows of the whole call in one launch, one wavefront per output row: row g finds its
+ *                replica in the node prefix sums (offs), its type in that replica's type_off, and copies `width` floats of row
+ *                node_id[g] of features_host[type] (HOST array of n_types device pointers, NULL for a type without a matrix;
+ *                type_nodes_host: rows per matrix) -- a pure copy, bit-equal to hgt_gather_rows.  A row whose type has no matrix or
+ *                whose id is outside it is left untouched.
+ * One workgroup per replica in the selection and the scan, the hub launches loop over their replica's queue; row logic, bounds checks
+ * and the absence of float atomics are those of the single entry points (the same device functions under a replica view).  Bad
+ * arguments -> a negative code and no launch: n_batch < 1, a NULL per-replica array with n > 0, a negative size: HGT_ERR_INVALID_ARG;
+ * scratch below the single requirement per replica: HGT_ERR_WORKSPACE; n_batch > HGT_SAMPLER_MAX_BATCH: HGT_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_SAMPLER_MAX_BATCH 64
+int hgt_sampler_seed_batched(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, int32_t type, const int32_t* ids,
+                             const int32_t* times, int32_t n, int32_t step, void* stream);
+int hgt_sampler_add_budget_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                   int32_t n_triples, int32_t n_batch, int32_t type, int32_t step, int32_t sampled_number,
+                                   int32_t max_new, int32_t has_max_time, int32_t max_time, const uint64_t* seeds_host, int32_t* hub,
+                                   int64_t hub_entries, void* stream);
+int hgt_sampler_select_batched(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, int32_t type, int32_t step,
+                               int32_t sampled_number, const uint64_t* seeds_host, uint64_t* keys, int32_t* tmp, int64_t tmp_entries,
+                               void* stream);
+int hgt_sampler_induce_count_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                     int32_t n_triples, int32_t n_batch, int32_t n_relations, int32_t* rowoff, int32_t* hub,
+                                     int64_t n_entries, int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out, void* stream);
+int hgt_sampler_induce_count_masked_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                            int32_t n_triples, int32_t n_batch, int32_t n_relations, int32_t* rowoff, int32_t* hub,
+                                            int64_t n_entries, int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out,
+                                            const hgt_sampler_mask* masks_host, void* stream);
+int hgt_sampler_induce_fill_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                    int32_t n_triples, int32_t n_batch, int32_t n_relations, const int32_t* rowoff, const int32_t* hub,
+                                    int64_t n_entries, const int32_t* type_off, const int32_t* sizes, int32_t* offs_out, int64_t n_nodes,
+                                    int64_t n_edges, int32_t* src_out, int32_t* dst_out, int32_t* time_out, int32_t* node_time_out,
+                                    int32_t* node_id_out, void* stream);
+int hgt_sampler_induce_fill_masked_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                           int32_t n_triples, int32_t n_batch, int32_t n_relations, const int32_t* rowoff,
+                                           const int32_t* hub, int64_t n_entries, const int32_t* type_off, const int32_t* sizes,
+                                           int32_t* offs_out, int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out,
+                                           int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out,
+                                           const hgt_sampler_mask* masks_host, void* stream);
+int hgt_sampler_reset_batched(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, void* stream);
+int hgt_sampler_gather_features(const float* const* features_host, const int32_t* type_nodes_host, int32_t n_types, int32_t n_batch,
+                                int32_t width, const int32_t* type_off, const int32_t* offs, const int32_t* node_id, int64_t n_nodes,
+                                float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,10 @@ names, forward signature) backed by hand-written HIP kernels behind a C ABI (inc
 from .conv import HGTConv, DenseHGTConv, GeneralConv, RelTemporalEncoding, GraphPlan, install_into  # noqa: F401
 from .model import GNN, Classifier, Matcher  # noqa: F401
 from .autograd import set_deterministic, set_recompute  # noqa: F401
-from .sampler import DeviceHeteroGraph, sample_subgraph_device, sample_subgraph_host  # noqa: F401
+from .sampler import (DeviceHeteroGraph, sample_subgraph_device, sample_subgraph_host, sample_subgraphs_device,  # noqa: F401
+                      sample_subgraphs_host)
 from .sampler import LabelSpace, seed_edge_mask, np_label_distribution, np_label_index, np_label_counts  # noqa: F401
 
 __all__ = ["HGTConv", "DenseHGTConv", "GeneralConv", "RelTemporalEncoding", "GraphPlan", "install_into", "GNN", "Classifier", "Matcher",
-           "set_deterministic", "set_recompute", "DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host"]
+           "set_deterministic", "set_recompute", "DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "sample_subgraphs_device",
+           "sample_subgraphs_host"]

@@ -40,6 +40,7 @@ HGT_SAMPLER_MAX_TRIPLES = 48
 HGT_SAMPLER_MAX_NUMBER = 1024
 HGT_SAMPLER_HUB_DEG = 512
 HGT_SAMPLER_TIME_NONE = -2 ** 31
+HGT_SAMPLER_MAX_BATCH = 64
 
 
 class HgtLayout(C.Structure):
@@ -229,6 +230,20 @@ SIGNATURES = {
     "hgt_sampler_induce_fill_masked": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                                  _vp]),
     "hgt_sampler_labels": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    # batched device sampler: the single calls with n_batch behind the tables, a host array of n_batch Philox seeds in place of the
+    # seed, and in the fill calls (sizes, offs_out) behind type_off; gather_features: (features_host, type_nodes_host, n_types, n_batch,
+    # width, type_off, offs, node_id, n_nodes, out, stream)
+    "hgt_sampler_seed_batched": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "hgt_sampler_add_budget_batched": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "hgt_sampler_select_batched": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "hgt_sampler_induce_count_batched": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hgt_sampler_induce_count_masked_batched": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "hgt_sampler_induce_fill_batched": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp]),
+    "hgt_sampler_induce_fill_masked_batched": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
+                                                         _vp, _vp, _vp, _vp, _vp]),
+    "hgt_sampler_reset_batched": (C.c_int, [_vp, _i32, _i32, _vp]),
+    "hgt_sampler_gather_features": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -27,6 +27,10 @@ The definition ("Device sampler", lists where it departs from th
 
 Labels of a task batch come from the same relation of the full graph: `LabelSpace` (csrc/hgt_sampler_labels.hip on a device graph, the
 `np_label_*` siblings on the host).
+
+Batched calls: `sample_subgraphs_device` draws B sub-graphs that share nothing but the resident graph in one pass of the launches of a
+single call (replica b = blockIdx.y of every launch) with one host read; element b is bit for bit what `sample_subgraph_device` returns
+for (inps[b], seeds[b]).  `sample_subgraphs_host` is the definition: the list of the single host calls.
 """
 import ctypes as C
 
@@ -37,8 +41,8 @@ from . import _lib
 from .conv import GraphPlan
 from .sampled import _DeviceGraph
 
-__all__ = ["DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "philox4x32_10", "seed_edge_mask", "LabelSpace",
-           "np_label_distribution", "np_label_index", "np_label_counts"]
+__all__ = ["DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "sample_subgraphs_device", "sample_subgraphs_host",
+           "philox4x32_10", "seed_edge_mask", "LabelSpace", "np_label_distribution", "np_label_index", "np_label_counts"]
 
 TIME_NONE = _lib.HGT_SAMPLER_TIME_NONE
 _SUBSET_TAG, _SELECT_TAG = 0x10000, 0x20000
@@ -117,6 +121,9 @@ class DeviceHeteroGraph:
         self._dev_state = {}
         self._dev_nodes = None
         self._dev_dirty = False                              # the per-node device arrays hold something a reset has not walked
+        self._batch_state = {}                               # the same three for batched calls (sample_subgraphs_device): [B, n] arrays
+        self._batch_nodes = None                             # of their own, sized for the largest B seen, and a flag of their own
+        self._batch_dirty = False
         if self.device is not None:
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
             self.csr_dev = [tuple(up(a) for a in c) for c in self.csr]
@@ -419,6 +426,31 @@ def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, s
 
 
 # ---------------------------------------------------------------------------------------------------------------- device
+def _triple_table(dgraph):
+    """the resident CSRs as the C table of meta triples"""
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    triples_c = (_lib.HgtSamplerTriple * max(len(dgraph.triples), 1))()
+    for m, ((tt, st, rel), (ip, src, tm)) in enumerate(zip(dgraph.tri_types, dgraph.csr_dev)):
+        triples_c[m] = _lib.HgtSamplerTriple(ip.data_ptr(), ptr(src), ptr(tm), tt, st, rel, 0)
+    return triples_c
+
+
+def _scratch_entries(lib, dgraph, types_c, triples_c, n_seed, sn):
+    """entries of rowoff / hub for one batch: the row slots of the induction or the rows of the largest add_budget call, + 1"""
+    T, slots = len(dgraph.types), C.c_int64()
+    _lib.check(lib.hgt_sampler_induce_slots(types_c, T, triples_c, len(dgraph.triples), C.byref(slots)), "hgt_sampler_induce_slots")
+    into = [sum(1 for tt, _, _ in dgraph.tri_types if tt == t) for t in range(T)]
+    rows = max([max(n_seed[t], sn) * into[t] for t in range(T)] + [0])       # add_budget: max_new x triples into the type
+    return max(int(slots.value), rows) + 1
+
+
+def _masks_c(table, M):
+    masks_c = (_lib.HgtSamplerMask * max(M, 1))()
+    for m in range(M):
+        masks_c[m] = _lib.HgtSamplerMask(int(table[m, 0]), int(table[m, 1]))
+    return masks_c
+
+
 class DeviceSamplerState:
     """The device state of one (seed counts, depth, sampled_number) shape of call and the step-level calls on it (one method per C
     entry point).  `sample_subgraph_device` strings them together; the tests call them one by one."""
@@ -446,14 +478,8 @@ class DeviceSamplerState:
         for t in range(T):
             self.types_c[t] = _lib.HgtSamplerType(ptr(self.score[t]), ptr(self.stamp[t]), ptr(self.serial[t]), ptr(self.sampled[t]),
                                                   ptr(self.cand[t]), self.counts[t].data_ptr(), dgraph.n_nodes[t], self.cap_s[t], self.cap_c[t], 0)
-        self.triples_c = (_lib.HgtSamplerTriple * max(M, 1))()
-        for m, ((tt, st, rel), (ip, src, tm)) in enumerate(zip(dgraph.tri_types, dgraph.csr_dev)):
-            self.triples_c[m] = _lib.HgtSamplerTriple(ip.data_ptr(), ptr(src), ptr(tm), tt, st, rel, 0)
-        slots = C.c_int64()
-        _lib.check(self.lib.hgt_sampler_induce_slots(self.types_c, T, self.triples_c, M, C.byref(slots)), "hgt_sampler_induce_slots")
-        into = [sum(1 for tt, _, _ in dgraph.tri_types if tt == t) for t in range(T)]
-        rows = max([max(n_seed[t], sn) * into[t] for t in range(T)] + [0])       # add_budget: max_new x triples into the type
-        self.n_entries = max(int(slots.value), rows) + 1
+        self.triples_c = _triple_table(dgraph)
+        self.n_entries = _scratch_entries(self.lib, dgraph, self.types_c, self.triples_c, n_seed, sn)
         self.rowoff, self.hub = torch.zeros(self.n_entries, **i32), torch.zeros(self.n_entries, **i32)
         self.keys = torch.zeros(max(self.cap_c + [1]), dtype=torch.int64, device=dev)
         self.tmp = torch.zeros(max(self.cap_c + [1]), **i32)
@@ -502,10 +528,8 @@ class DeviceSamplerState:
         if table is None:
             count, fill, tail, what = lib.hgt_sampler_induce_count, lib.hgt_sampler_induce_fill, (), "hgt_sampler_induce"
         else:
-            masks_c = (_lib.HgtSamplerMask * max(M, 1))()
-            for m in range(M):
-                masks_c[m] = _lib.HgtSamplerMask(int(table[m, 0]), int(table[m, 1]))
-            count, fill, tail, what = lib.hgt_sampler_induce_count_masked, lib.hgt_sampler_induce_fill_masked, (masks_c,), "hgt_sampler_induce_masked"
+            count, fill, tail = lib.hgt_sampler_induce_count_masked, lib.hgt_sampler_induce_fill_masked, (_masks_c(table, M),)
+            what = "hgt_sampler_induce_masked"
         _lib.check(count(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
                          self.type_off.data_ptr(), self.rel_ptr.data_ptr(), self.sizes.data_ptr(), *tail, self._stream()), what + " (count)")
         sizes = self.sizes.cpu().numpy()                     # the host synchronisation of the batch
@@ -617,6 +641,263 @@ def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp,
         if plan:
             out.plan = GraphPlan.from_sorted(out[1], out[3], out[4], out[2], src, dst, etime, rel_ptr, type_off, T, st.R)
             GraphPlan.register(out.plan, out[1], out[3], out[4], out[2], T, st.R)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- batched calls
+class BatchedDeviceSamplerState:
+    """`DeviceSamplerState` with a batch dimension: the device state of n_batch replicas of one (seed counts, depth, sampled_number)
+    shape of call and the step-level calls on all of them at once (one method per batched C entry point; replica b of every launch
+    is blockIdx.y = b).  Every array is one [n_batch, .] tensor: replica b is base + b * stride, and the strides are the fields of the
+    one table the kernels get (n_nodes, cap_sampled, cap_cand).  The per-node arrays (score / stamp / serial over every node of every
+    type, 20 bytes x nodes x B) live on the graph, apart from the single call's, sized for the largest n_batch seen; the lists, keys
+    and induction scratch (a few hundred KB per replica at the training shapes) belong to the state."""
+
+    def __init__(self, dgraph, n_seed, depth, sn, n_batch):
+        if dgraph.device is None or dgraph.device.type != "cuda":
+            raise RuntimeError("pyhgt_amd: sample_subgraphs_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host "
+                               "sibling is sample_subgraphs_host)")
+        if not 1 <= n_batch <= _lib.HGT_SAMPLER_MAX_BATCH:
+            raise ValueError("pyhgt_amd: 1 <= n_batch <= %d" % _lib.HGT_SAMPLER_MAX_BATCH)
+        self.g, self.dev, self.sn, self.depth, self.B = dgraph, dgraph.device, int(sn), int(depth), int(n_batch)
+        self.lib = _lib.load()
+        T, M, dev, B = len(dgraph.types), len(dgraph.triples), self.dev, self.B
+        self.T, self.M, self.R = T, M, len(dgraph.edge_dict)
+        self.cap_s, self.cap_c = _capacities(dgraph, n_seed, depth, sn)
+        if dgraph._batch_nodes is None or dgraph._batch_nodes[0][0].size(0) < B:
+            dgraph._batch_state.clear()                      # the cached states point into the arrays that go
+            dgraph._batch_nodes = ([torch.zeros(B, n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
+                                   [torch.zeros(B, n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
+                                   [torch.full((B, n), -1, dtype=torch.int32, device=dev) for n in dgraph.n_nodes])
+            dgraph._batch_dirty = False
+        self.score, self.stamp, self.serial = dgraph._batch_nodes
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.sampled = [torch.zeros(B, c, **i32) for c in self.cap_s]
+        self.cand = [torch.zeros(B, c, **i32) for c in self.cap_c]
+        self.counts = torch.zeros(B, T, 4, **i32)
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        self.types_c = (_lib.HgtSamplerType * T)()           # the table of replica 0; the kernels shift it by b strides
+        for t in range(T):
+            self.types_c[t] = _lib.HgtSamplerType(ptr(self.score[t]), ptr(self.stamp[t]), ptr(self.serial[t]), ptr(self.sampled[t]),
+                                                  ptr(self.cand[t]), self.counts[0, t].data_ptr(), dgraph.n_nodes[t], self.cap_s[t],
+                                                  self.cap_c[t], 0)
+        self.triples_c = _triple_table(dgraph)
+        self.n_entries = _scratch_entries(self.lib, dgraph, self.types_c, self.triples_c, n_seed, sn)      # per replica
+        self.rowoff, self.hub = torch.zeros(B, self.n_entries, **i32), torch.zeros(B * self.n_entries, **i32)
+        self.n_tmp = max(self.cap_c + [1])
+        self.keys = torch.zeros(B, self.n_tmp, dtype=torch.int64, device=dev)
+        self.tmp = torch.zeros(B, self.n_tmp, **i32)
+        self.type_off, self.rel_ptr = torch.zeros(B, T + 1, **i32), torch.zeros(B, self.R + 1, **i32)
+        self.sizes, self.offs = torch.zeros(B, T + M + 2, **i32), torch.zeros(2 * (B + 1), **i32)
+
+    # the state rule of the single call with a flag of its own: the batched per-node arrays are another set of arrays
+    @property
+    def dirty(self):
+        return self.g._batch_dirty
+
+    @dirty.setter
+    def dirty(self, value):
+        self.g._batch_dirty = bool(value)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _seeds_c(self, seeds):
+        if len(seeds) != self.B:
+            raise ValueError("pyhgt_amd: %d Philox seeds for %d replicas" % (len(seeds), self.B))
+        return (C.c_uint64 * self.B)(*[int(s) & (2 ** 64 - 1) for s in seeds])
+
+    def seed_nodes(self, t, ids, times, step):
+        """ids, times: [n_batch, n]"""
+        ids, times = (np.ascontiguousarray(a, dtype=np.int32) for a in (ids, times))
+        if ids.ndim != 2 or ids.shape[0] != self.B or times.shape != ids.shape:
+            raise ValueError("pyhgt_amd: seed ids and times must be [%d, n]" % self.B)
+        n = ids.shape[1]
+        ids, times = (torch.from_numpy(a).to(self.dev) for a in (ids, times))
+        self.dirty = True
+        _lib.check(self.lib.hgt_sampler_seed_batched(self.types_c, self.T, self.B, t, ids.data_ptr() if n else None,
+                                                     times.data_ptr() if n else None, n, step, self._stream()), "hgt_sampler_seed_batched")
+        ids.record_stream(torch.cuda.current_stream(self.dev))
+        times.record_stream(torch.cuda.current_stream(self.dev))
+
+    def add_budget(self, t, step, max_new, max_time, seeds):
+        self.dirty = True
+        _lib.check(self.lib.hgt_sampler_add_budget_batched(self.types_c, self.T, self.triples_c, self.M, self.B, t, step, self.sn, max_new,
+                                                           0 if max_time is None else 1, 0 if max_time is None else int(max_time),
+                                                           self._seeds_c(seeds), self.hub.data_ptr(), self.n_entries, self._stream()),
+                   "hgt_sampler_add_budget_batched")
+
+    def select(self, t, step, seeds):
+        self.dirty = True
+        _lib.check(self.lib.hgt_sampler_select_batched(self.types_c, self.T, self.B, t, step, self.sn, self._seeds_c(seeds),
+                                                       self.keys.data_ptr(), self.tmp.data_ptr(), self.n_tmp, self._stream()),
+                   "hgt_sampler_select_batched")
+
+    def induce(self, mask=None):
+        """count pass, the one host read of the call (sizes [n_batch, T + M + 2]), fill pass into buffers that hold the replicas one
+        after the other -> (src, dst, edge_time, rel_ptr [B, R + 1], type_off [B, T + 1], node_time, node_id, nodes per type [B][T],
+        node offsets [B + 1], edge offsets [B + 1]); indices are local to each piece."""
+        lib, T, M, B = self.lib, self.T, self.M, self.B
+        table = _mask_table(self.g, mask)
+        if table is None:
+            count, fill, tail, what = lib.hgt_sampler_induce_count_batched, lib.hgt_sampler_induce_fill_batched, (), "hgt_sampler_induce_batched"
+        else:
+            count, fill, tail = lib.hgt_sampler_induce_count_masked_batched, lib.hgt_sampler_induce_fill_masked_batched, (_masks_c(table, M),)
+            what = "hgt_sampler_induce_masked_batched"
+        _lib.check(count(self.types_c, T, self.triples_c, M, B, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
+                         self.type_off.data_ptr(), self.rel_ptr.data_ptr(), self.sizes.data_ptr(), *tail, self._stream()), what + " (count)")
+        sizes = self.sizes.cpu().numpy()                     # the host synchronisation of the batched call
+        if sizes[:, T + M].any():
+            raise RuntimeError("pyhgt_amd: a sampler list overflowed its static capacity or a seed id was out of range")
+        n_per_type = [[int(v) for v in row[:T]] for row in sizes]
+        nodes = np.array([sum(row) for row in n_per_type], dtype=np.int64)
+        node_off = np.concatenate([[0], np.cumsum(nodes)])
+        edge_off = np.concatenate([[0], np.cumsum(nodes + sizes[:, T + M + 1].astype(np.int64))])
+        N, E = int(node_off[-1]), int(edge_off[-1])
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        src, dst, etime = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
+        node_time, node_id = torch.empty(N, **i32), torch.empty(N, **i32)
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        _lib.check(fill(self.types_c, T, self.triples_c, M, B, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
+                        self.type_off.data_ptr(), self.sizes.data_ptr(), self.offs.data_ptr(), N, E, ptr(src), ptr(dst), ptr(etime),
+                        ptr(node_time), ptr(node_id), *tail, self._stream()), what + " (fill)")
+        return src, dst, etime, self.rel_ptr.clone(), self.type_off.clone(), node_time, node_id, n_per_type, node_off, edge_off
+
+    def gather_features(self, type_off, node_id, n_per_type, width):
+        """the feature rows of every replica's nodes in one launch: float32 [nodes of the call, width].  self.offs still holds the
+        node offsets the fill pass wrote.  A type with rows and no matrix is an error of the caller, found here before the launch."""
+        N = int(node_id.numel())
+        feats = self.g.features
+        for t in range(self.T):
+            if width and feats[t] is None and any(row[t] for row in n_per_type):
+                raise ValueError("pyhgt_amd: no feature matrix for node type %r" % self.g.types[t])
+        out = torch.empty(N, width, dtype=torch.float32, device=self.dev)
+        mats = (C.c_void_p * self.T)(*[None if f is None or f.numel() == 0 else f.data_ptr() for f in feats])
+        rows = (C.c_int32 * self.T)(*[0 if f is None else int(f.size(0)) for f in feats])
+        _lib.check(self.lib.hgt_sampler_gather_features(mats, rows, self.T, self.B, width, type_off.data_ptr(), self.offs.data_ptr(),
+                                                        node_id.data_ptr() if N else None, N, out.data_ptr() if out.numel() else None,
+                                                        self._stream()), "hgt_sampler_gather_features")
+        return out
+
+    def reset(self):
+        _lib.check(self.lib.hgt_sampler_reset_batched(self.types_c, self.T, self.B, self._stream()), "hgt_sampler_reset_batched")
+        self.dirty = False
+
+    def clear(self):
+        """full clear of the batched per-node arrays (every replica the graph holds, not only this state's) and of the counters of
+        every cached batched state"""
+        for a in self.score + self.stamp:
+            a.zero_()
+        for a in self.serial:
+            a.fill_(-1)
+        for st in [self] + list(self.g._batch_state.values()):
+            st.counts.zero_()
+        self.dirty = False
+
+    def snapshot(self):
+        """host copies of the state, one dict per replica in the form of DeviceSamplerState.snapshot()"""
+        counts = self.counts.cpu().numpy()
+        u64 = lambda a: a.cpu().numpy().view(np.uint64)
+        score, stamp = [u64(a) for a in self.score], [u64(a) for a in self.stamp]
+        serial, sampled, cand = ([a.cpu().numpy() for a in v] for v in (self.serial, self.sampled, self.cand))
+        return [dict(score=[a[b] for a in score], stamp=[a[b] for a in stamp], serial=[a[b] for a in serial],
+                     sampled=[a[b, :counts[b, t, 0]].astype(np.int64) for t, a in enumerate(sampled)],
+                     cand=[a[b, :counts[b, t, 2]].astype(np.int64) for t, a in enumerate(cand)], counts=counts[b]) for b in range(self.B)]
+
+
+def _batched_state(dgraph, n_seed, depth, sn, n_batch):
+    key = (tuple(n_seed), int(depth), int(sn), int(n_batch))
+    st = dgraph._batch_state.get(key)
+    if st is None:
+        if len(dgraph._batch_state) >= 4:
+            dgraph._batch_state.clear()
+        st = BatchedDeviceSamplerState(dgraph, n_seed, depth, sn, n_batch)
+        dgraph._batch_state[key] = st                        # after the constructor: a larger n_batch empties the cache in there
+    return st
+
+
+def _batch_args(dgraph, inps, seeds):
+    """-> (per replica the seed arrays of _seed_arrays, Philox seeds); every replica has the same number of seeds per type"""
+    inps, seeds = list(inps), [int(s) for s in seeds]
+    if not 1 <= len(inps) <= _lib.HGT_SAMPLER_MAX_BATCH:
+        raise ValueError("pyhgt_amd: 1 <= number of batches <= %d, got %d" % (_lib.HGT_SAMPLER_MAX_BATCH, len(inps)))
+    if len(seeds) != len(inps):
+        raise ValueError("pyhgt_amd: %d Philox seeds for %d batches" % (len(seeds), len(inps)))
+    arrays = [_seed_arrays(dgraph, inp) for inp in inps]
+    shape = [ids.size for ids, _ in arrays[0]]
+    for b, a in enumerate(arrays):
+        if [ids.size for ids, _ in a] != shape:
+            raise ValueError("pyhgt_amd: batch %d has %r seeds per type, batch 0 has %r (a short last batch goes through the single call)"
+                             % (b, [ids.size for ids, _ in a], shape))
+    return arrays, seeds
+
+
+def sample_subgraphs_host(dgraph, max_time, sampled_depth, sampled_number, inps, seeds, mask=None):
+    """The definition of `sample_subgraphs_device`: the list of the single host calls."""
+    inps, seeds = list(inps), list(seeds)
+    if len(seeds) != len(inps):
+        raise ValueError("pyhgt_amd: %d Philox seeds for %d batches" % (len(seeds), len(inps)))
+    return [sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, seed, mask=mask) for inp, seed in zip(inps, seeds)]
+
+
+def sample_subgraphs_device(dgraph, max_time, sampled_depth, sampled_number, inps, seeds, plan=True, mask=None):
+    """B sub-graphs in one pass of launches: inps = B seed dicts in the form `sample_subgraph_device` takes, all with the same number of
+    seeds per type (ValueError otherwise, before any launch; 1 <= B <= HGT_SAMPLER_MAX_BATCH), seeds = B Philox seeds; max_time, depth,
+    sampled_number and mask are shared.  Returns a list whose element b is, bit for bit, what sample_subgraph_device(dgraph, max_time,
+    sampled_depth, sampled_number, inps[b], seeds[b], plan=plan, mask=mask) returns (random words are keyed by what is drawn and by the
+    seed, serials are ranks, the state updates are integer atomics); its tensors are slices of buffers the call allocates once.  The
+    number of sampler launches is that of a single call whatever B is, and the call reads the device once (the [B, T + M + 2] sizes);
+    an overflow in any replica raises the single call's RuntimeError.  The list goes straight into `stack_device_graphs`.
+    Memory: 20 bytes x nodes of the graph x B for the per-node state, kept on the graph for the largest B seen."""
+    _check_args(dgraph, sampled_depth, sampled_number)
+    arrays, seeds = _batch_args(dgraph, inps, seeds)
+    table = _mask_table(dgraph, mask)
+    T, sn, B = len(dgraph.types), int(sampled_number), len(arrays)
+    if dgraph.device is None or dgraph.device.type != "cuda":
+        raise RuntimeError("pyhgt_amd: sample_subgraphs_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host sibling is "
+                           "sample_subgraphs_host)")
+    if dgraph.features is None:
+        raise ValueError("pyhgt_amd: the DeviceHeteroGraph carries no features")
+    n_seed = [ids.size for ids, _ in arrays[0]]
+    st = _batched_state(dgraph, n_seed, sampled_depth, sn, B)
+    dev = st.dev
+    with torch.cuda.device(dev):
+        if st.dirty:
+            st.clear()
+        for t in range(T):
+            if n_seed[t]:
+                st.seed_nodes(t, np.stack([a[t][0] for a in arrays]), np.stack([a[t][1] for a in arrays]), t)
+        for t in range(T):
+            if n_seed[t]:
+                st.add_budget(t, t, n_seed[t], max_time, seeds)
+        for layer in range(sampled_depth):
+            for t in range(T):
+                if st.cap_c[t] == 0:
+                    continue
+                step = T * (1 + layer) + t
+                st.select(t, step, seeds)
+                st.add_budget(t, step, sn, max_time, seeds)
+        src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type, node_off, edge_off = st.induce(table)
+        widths = sorted({f.size(1) for f in dgraph.features if f is not None and f.size(0) > 0})
+        if len(widths) > 1:
+            raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (widths,))
+        feat = st.gather_features(type_off, node_id, n_per_type, widths[0] if widths else 0)
+        st.reset()
+        ids64, out = node_id.long(), []
+        for b in range(B):
+            n, e = slice(int(node_off[b]), int(node_off[b + 1])), slice(int(edge_off[b]), int(edge_off[b + 1]))
+            srt = (src[e], dst[e], etime[e], rel_ptr[b], type_off[b])
+            x = feat[n] if (n.start * feat.size(1)) % 4 == 0 else feat[n].clone()      # starts on 16 bytes, like a single call's
+            piece = _wire_tuple(_SampledDeviceGraph, dgraph, x, n_per_type[b], *srt)
+            piece.sorted = srt
+            offs = node_off[b] + np.concatenate([[0], np.cumsum(n_per_type[b])])
+            piece.indxs = {name: ids64[offs[t]:offs[t + 1]] for t, name in enumerate(dgraph.types)}
+            piece.times = {name: node_time[offs[t]:offs[t + 1]] for t, name in enumerate(dgraph.types)}
+            piece.n_seed = {name: int(n_seed[t]) for t, name in enumerate(dgraph.types)}
+            if plan:
+                piece.plan = GraphPlan.from_sorted(piece[1], piece[3], piece[4], piece[2], *piece.sorted, T, st.R)
+                GraphPlan.register(piece.plan, piece[1], piece[3], piece[4], piece[2], T, st.R)
+            out.append(piece)
     return out
 
 

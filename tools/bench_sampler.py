@@ -5,10 +5,15 @@ shapes: 128 seed papers, depth 6, width 128 (OAG/train_paper_field.py) and width
 
     python tools/bench_sampler.py [--papers 200000] [--reps 10] [--host-reps 2] [--out profiles/r11_device_sampler.json]
     python tools/bench_sampler.py --task [--out profiles/r12_task_batches.json]
+    python tools/bench_sampler.py --batch 1,4,16 [--reps 10] [--out profiles/r13_batched_sampler.json]
 
 --task times a task batch instead (the OAG workload only): the call with the label edges at the 128 seed papers masked out
 (mask=seed_edge_mask(...), the same launches as the plain call) against the plain call, alternating in one process, medians of 8 each;
 and LabelSpace.distribution / LabelSpace.index for the 128 seeds (one launch each).
+
+--batch B[,B...] times the batched call instead: for every B one sample_subgraphs_device call of B batches against B
+sample_subgraph_device calls in a loop (the same seeds and Philox seeds, alternating in one process, medians of --reps), the time per
+batch of both, and the launches of both counted from the calls the host loops make.
 
 Device time is wall-clock per call with a synchronisation after each (the call synchronises once by itself, for the sizes of the
 result); launches per batch are counted from the calls the host loop makes (every C entry point is a fixed number of launches).  One
@@ -25,7 +30,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "examples"))
-from pyhgt_amd import LabelSpace, sample_subgraph_device, sample_subgraph_host, seed_edge_mask  # noqa: E402
+from pyhgt_amd import LabelSpace, sample_subgraph_device, sample_subgraph_host, sample_subgraphs_device, seed_edge_mask  # noqa: E402
 from pyhgt_amd.sampled import SchemaGraph, to_device_graph  # noqa: E402
 from train_device_sampler import resident_graph  # noqa: E402
 
@@ -40,6 +45,46 @@ def launches_per_batch(dgraph, depth, n_seed_types=1):
     feature_gathers = T
     return (n_seed_types * (LAUNCHES["seed"] + LAUNCHES["add_budget"]) + depth * live * (LAUNCHES["select"] + LAUNCHES["add_budget"])
             + LAUNCHES["induce"] + LAUNCHES["reset"] + feature_gathers)
+
+
+def launches_per_batched_call(dgraph, depth, n_seed_types=1):
+    """the launches of one sample_subgraphs_device call, whatever B is: those of a single batch with one more in the fill pass (the
+    prefix sums over the replicas) and ONE feature gather for all types and replicas"""
+    T = len(dgraph.types)
+    live = sum(1 for t in range(T) if any(st == t for _, st, _ in dgraph.tri_types))
+    return (n_seed_types * (LAUNCHES["seed"] + LAUNCHES["add_budget"]) + depth * live * (LAUNCHES["select"] + LAUNCHES["add_budget"])
+            + LAUNCHES["induce"] + 1 + LAUNCHES["reset"] + 1)
+
+
+def batch_lines(a, dev):
+    """per workload and B: one batched call against B single calls in a loop"""
+    sizes = [int(v) for v in a.batch.split(",")]
+    lines = []
+    for name, (schema, depth, width, max_time) in WORKLOADS.items():
+        dgraph, n_nodes = resident_graph(schema, a.papers, a.feat_dim, dev, seed=1, mean_degree=a.mean_degree)
+        rng = np.random.default_rng(7)
+        draw = lambda: {"paper": np.stack([rng.choice(n_nodes["paper"], 128, replace=False), np.full(128, 2015)], axis=1)}
+        per_b = []
+        for B in sizes:
+            rounds = [([draw() for _ in range(B)], [1000 * r + b for b in range(B)]) for r in range(a.reps + 1)]
+            loop = lambda inps, keys: [sample_subgraph_device(dgraph, max_time, depth, width, i, seed=k, plan=False) for i, k in zip(inps, keys)]
+            one = lambda inps, keys: sample_subgraphs_device(dgraph, max_time, depth, width, inps, keys, plan=False)
+            loop(*rounds[0]), one(*rounds[0])                # warm-up: allocations of both states, first launches
+            torch.cuda.synchronize()
+            t_loop, t_one = [], []
+            for r in range(1, a.reps + 1):
+                for fn, t in ((loop, t_loop), (one, t_one)) if r % 2 else ((one, t_one), (loop, t_loop)):
+                    dt, out = _timed(lambda: fn(*rounds[r]))
+                    t.append(dt)
+            ms = lambda v: float(np.median(v) * 1e3)
+            per_b.append(dict(batch=B, batched_call_ms=ms(t_one), batched_ms_per_batch=ms(t_one) / B, batched_call_ms_min=float(np.min(t_one) * 1e3),
+                              loop_ms=ms(t_loop), loop_ms_per_batch=ms(t_loop) / B, launches_batched_call=launches_per_batched_call(dgraph, depth),
+                              launches_loop=B * launches_per_batch(dgraph, depth), nodes_last_call=int(sum(g[1].numel() for g in out))))
+        line = dict(workload=name, schema=schema, papers=a.papers, seeds=128, depth=depth, width=width, reps=a.reps, per_batch_size=per_b)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del dgraph
+    return lines
 
 
 def hand_over(res, dgraph):
@@ -115,12 +160,15 @@ def main():
     ap.add_argument("--mean-degree", type=float, default=3.0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--task", action="store_true")
+    ap.add_argument("--batch", default=None, help="batch sizes of the batched call, e.g. 1,4,16")
     a = ap.parse_args()
     dev, lines = "cuda:0", []
     if a.task:
         lines.append(task_line(a, dev))
         print(json.dumps(lines[0]), flush=True)
-    for name, (schema, depth, width, max_time) in ({} if a.task else WORKLOADS).items():
+    if a.batch:
+        lines += batch_lines(a, dev)
+    for name, (schema, depth, width, max_time) in ({} if a.task or a.batch else WORKLOADS).items():
         dgraph, n_nodes = resident_graph(schema, a.papers, a.feat_dim, dev, seed=1, mean_degree=a.mean_degree)
         rng = np.random.default_rng(7)
         inps = [{"paper": np.stack([rng.choice(n_nodes["paper"], 128, replace=False), np.full(128, 2015)], axis=1)} for _ in range(a.reps + 2)]
