@@ -975,6 +975,52 @@ int hgt_sampler_gather_features(const float* const* features_host, const int32_t
                                 int32_t width, const int32_t* type_off, const int32_t* offs, const int32_t* node_id, int64_t n_nodes,
                                 float* out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Scoring task batches (csrc/hgt_task_metrics.hip): what the reference's training scripts do with the model's output -- NDCG and MRR of
+ * every scored row (OAG/train_paper_field.py:272-275 and :303-308 and the same lines of train_paper_venue.py and
+ * train_author_disambiguation.py:335-345, 391-398, which take one argsort row at a time to the host and run pyHGT/utils.py:5-20 on it)
+ * and the pair-ranking loss mask_softmax (train_author_disambiguation.py:90-96).  Added under ABI 8 (new symbols only).
+ *
+ *   hgt_rank_metrics        per row of C scores s (float32) with relevances l >= 0: 0-based ranks, a tie goes to the lower position,
+ *                             score rank of p = #{ j : s_j > s_p or (s_j == s_p and j < p) }
+ *                             ideal rank of p = #{ j : l_j > l_p or (l_j == l_p and j < p) }
+ *                           and with w(0) = 1, w(i) = 1 / log2(i + 1), K = k > 0 ? k : C, over the positives (l_p > 0):
+ *                             DCG = sum of l_p * w(rank_p) where rank_p < K, IDCG the same over the ideal ranks,
+ *                             ndcg_out[r] = DCG / IDCG (0 when IDCG == 0), rr_out[r] = 1 / (1 + min rank_p) (0 without a positive).
+ *                           A NaN score in a row makes both of its results NaN; -inf is an ordinary score.
+ *                           Relevances: `labels` (float32, laid out like the scores) as given; or `index` (int64[n_rows]): l = 1 at
+ *                           that position, a value outside [0, C) = no positive; or neither: l = 1 at position 0.  Both: an error.
+ *                           Rows: row_ptr == NULL: n_rows rows of n_cols positions, row r at scores + r * ld_scores (labels + r *
+ *                           ld_labels), ld >= n_cols, any alignment (16-byte loads where the row's base allows).  row_ptr
+ *                           (int64[n_rows + 1], device): row r is scores[row_ptr[r] .. row_ptr[r + 1]) (and labels likewise; index is
+ *                           relative to the row), n_cols is the longest row and the leading dimensions are not read; a row the pointers
+ *                           make longer than n_cols, or negative, gives NaN.  Rows of at most 64 positions take a wavefront each,
+ *                           longer ones a workgroup each; the positives of a row go through an LDS list of HGT_RANK_LIST_CAP entries,
+ *                           a row with more takes further passes (no cap on their number).  Ranks are integer counts, the l * w terms
+ *                           fp64, summed in an order fixed by the row alone: no float atomic, and a row's bits do not depend on
+ *                           n_rows, the other rows or the launch geometry.  No allocation, no synchronisation; n_rows == 0: HGT_OK
+ *                           without a launch.  scores, labels, index, row_ptr and the two outputs (double[n_rows]) are device arrays.
+ *                           Negative n_rows / n_cols / k, labels and index together, NULL outputs or NULL scores with n_cols > 0,
+ *                           ld < n_cols: HGT_ERR_INVALID_ARG; n_cols > INT32_MAX - 1024: HGT_ERR_UNSUPPORTED; no launch.
+ *   hgt_segment_first_nll   segments s = scores[row_ptr[s] .. row_ptr[s + 1]) of lengths 2 .. max_len: with m = max and
+ *                           ls = log(sum exp(x - m)) in fp32 as torch.log_softmax forms them, loss_out[s] = (ls - (x_0 - m)) / ln(len)
+ *                           (ln(len) = the fp32 value nearest to it) and lse_out[2 s] = m, lse_out[2 s + 1] = ls -- the logsumexp in
+ *                           its two parts, so that the backward forms x - m - ls exactly as the forward did.  A segment the pointers
+ *                           make shorter than 2 or longer than max_len gives NaN.  A wavefront per segment up to 64 entries, a
+ *                           workgroup above; no atomics.
+ *   hgt_segment_first_nll_bwd   grad_scores[j] = grad_loss[s] * (exp(x_j - m - ls) - [j is the first of s]) / ln(len) for every j of
+ *                           every segment, each element written exactly once (grad_loss: float32[n_seg]).
+ *                           Both: n_seg == 0: HGT_OK without a launch; a negative size, max_len < 2 or a NULL array with n_seg > 0:
+ *                           HGT_ERR_INVALID_ARG, no launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_RANK_LIST_CAP 1024
+int hgt_rank_metrics(const float* scores, const float* labels, const int64_t* index, const int64_t* row_ptr, int32_t n_rows,
+                     int32_t n_cols, int64_t ld_scores, int64_t ld_labels, int32_t k, double* ndcg_out, double* rr_out, void* stream);
+int hgt_segment_first_nll(const float* scores, const int64_t* row_ptr, int32_t n_seg, int32_t max_len, float* loss_out, float* lse_out,
+                          void* stream);
+int hgt_segment_first_nll_bwd(const float* scores, const int64_t* row_ptr, int32_t n_seg, int32_t max_len, const float* lse,
+                              const float* grad_loss, float* grad_scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

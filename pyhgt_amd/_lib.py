@@ -99,6 +99,7 @@ class HgtSamplerMask(C.Structure):
     _fields_ = [("tgt_below", C.c_int32), ("src_below", C.c_int32)]
 
 
+RANK_LIST_CAP = 1024     # HGT_RANK_LIST_CAP: positives a pass of hgt_rank_metrics holds
 ABI_VERSION = 8          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
 
 _i32, _i64, _u64, _vp = C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
@@ -244,6 +245,12 @@ SIGNATURES = {
                                                          _vp, _vp, _vp, _vp, _vp]),
     "hgt_sampler_reset_batched": (C.c_int, [_vp, _i32, _i32, _vp]),
     "hgt_sampler_gather_features": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    # scoring task batches (csrc/hgt_task_metrics.hip): (scores, labels, index, row_ptr, n_rows, n_cols, ld_scores, ld_labels, k, ndcg_out,
+    # rr_out, stream); the loss: (scores, row_ptr, n_seg, max_len, loss_out, lse_out, stream) and (scores, row_ptr, n_seg, max_len, lse,
+    # grad_loss, grad_scores, stream)
+    "hgt_rank_metrics": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "hgt_segment_first_nll": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "hgt_segment_first_nll_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

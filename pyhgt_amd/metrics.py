@@ -1,0 +1,284 @@
+"""Scoring a task batch: NDCG, MRR and the pair-ranking loss of the reference's training scripts, on the device.
+
+After a step the scripts of the reference take one `argsort` row of the model's output at a time to the host and run `ndcg_at_k` and
+`mean_reciprocal_rank` (pyHGT/utils.py:5-20) on it (OAG/train_paper_field.py:272-275, 303-308 and its siblings); the author
+disambiguation script builds its loss, `mask_softmax`, from one `log_softmax` per paper (OAG/train_author_disambiguation.py:90-96).
+`rank_metrics` and `pair_rank_loss` are one call each on the current stream (csrc/hgt_task_metrics.hip), without a host copy of a row.
+
+The rule is the numpy code below, `np_rank_metrics` and `np_pair_rank_loss`; the kernels are tested against it.
+
+Ranks.  A row is a run of C >= 0 scores s_j (float32) with relevances l_j >= 0 (float32); P of them are positive.  Ranks are 0-based
+and a tie goes to the lower position (`torch.argsort(descending=True)` is not stable, so the reference leaves ties open):
+
+    score rank of p = #{ j : s_j > s_p or (s_j == s_p and j < p) }
+    ideal rank of p = #{ j : l_j > l_p or (l_j == l_p and j < p) }
+
+Metrics.  w(0) = 1, w(i) = 1 / log2(i + 1); K = C for k=None, else k >= 1:
+
+    DCG  = sum over the positives with rank < K of l_p * w(rank_p)
+    IDCG = sum over the positives with ideal rank < K of l_p * w(ideal rank_p)
+    ndcg = DCG / IDCG, 0 when IDCG == 0;    rr = 1 / (1 + min over the positives of rank_p), 0 when P == 0 (whatever k is)
+
+A row that holds a NaN score gives NaN for both; -inf is an ordinary score.
+
+Relevances: `labels` (float32, shaped like the scores: `ylabel` of the paper-field script), or `index` (int64 per row: l = 1 at that
+column, a value outside [0, C) -- such as LabelSpace.index's -1 -- means P = 0), or neither: l = 1 at position 0 of the row (author
+disambiguation: the true author comes first).  Rows: scores [n, C], or a flat [L] with `sizes`, the lengths of its consecutive rows.
+
+Loss.  For segments of lengths l_s >= 2 over a flat score vector:
+
+    loss = sum_s (logsumexp(seg_s) - seg_s[0]) / ln(l_s),    d loss / d s_j = g * (softmax(seg_s)_j - [j is first]) / ln(l_s)
+"""
+import numpy as np
+import torch
+
+from . import _lib
+
+__all__ = ["Segments", "rank_metrics", "pair_rank_loss", "np_rank_metrics", "np_pair_rank_loss", "np_ranks"]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the rule
+def np_ranks(values):
+    """0-based descending ranks of a 1-d array, a tie to the lower position (-0.0 == 0.0, as everywhere in IEEE comparisons)"""
+    values = np.asarray(values)
+    order = np.argsort(-values, kind="stable")
+    ranks = np.empty(values.size, np.int64)
+    ranks[order] = np.arange(values.size)
+    return ranks
+
+
+def _np_row(s, l, k):
+    if np.isnan(s).any():
+        return np.nan, np.nan
+    pos = np.flatnonzero(l > 0)
+    if pos.size == 0:
+        return 0.0, 0.0
+    K = s.size if k is None else k
+    rel = l[pos].astype(np.float64)
+
+    def dcg(rank):
+        w = np.ones(rank.size)
+        w[rank > 0] = 1.0 / np.log2(rank[rank > 0] + 1.0)
+        return float(np.sum((rel * w)[rank < K]))
+
+    rank = np_ranks(s)[pos]
+    ideal = dcg(np_ranks(np.where(l > 0, l, 0))[pos])
+    return (dcg(rank) / ideal if ideal else 0.0), 1.0 / (1.0 + int(rank.min()))
+
+
+def _check_k(k):
+    if k is not None and (int(k) != k or k < 1):
+        raise ValueError("pyhgt_amd: k is None or an integer >= 1")
+    return None if k is None else int(k)
+
+
+def _np_sizes(sizes, total, least):
+    sizes = np.asarray(sizes if not isinstance(sizes, Segments) else sizes.sizes, dtype=np.int64).reshape(-1)
+    if sizes.size and sizes.min() < least:
+        raise ValueError("pyhgt_amd: a segment shorter than %d" % least)
+    if int(sizes.sum()) != total:
+        raise ValueError("pyhgt_amd: sizes add up to %d, the scores have %d entries" % (int(sizes.sum()), total))
+    return sizes
+
+
+def np_rank_metrics(scores, labels=None, index=None, k=None, sizes=None):
+    """(ndcg, rr), float64 arrays of one value per row: the definition of this module's docstring in numpy"""
+    k = _check_k(k)
+    if labels is not None and index is not None:
+        raise ValueError("pyhgt_amd: labels or index, not both")
+    scores = np.asarray(scores, dtype=np.float32)
+    if sizes is None:
+        if scores.ndim != 2:
+            raise ValueError("pyhgt_amd: scores are [n, C], or flat with sizes")
+        rows = [(r * scores.shape[1], scores.shape[1]) for r in range(scores.shape[0])]
+    else:
+        if scores.ndim != 1:
+            raise ValueError("pyhgt_amd: with sizes the scores are flat")
+        sizes = _np_sizes(sizes, scores.size, 0)
+        rows = list(zip(np.concatenate([[0], np.cumsum(sizes)[:-1]]).tolist(), sizes.tolist())) if sizes.size else []
+    flat = scores.reshape(-1)
+    if labels is not None:
+        labels = np.asarray(labels, dtype=np.float32)
+        if labels.shape != scores.shape:
+            raise ValueError("pyhgt_amd: labels are shaped like the scores")
+        labels = labels.reshape(-1)
+    if index is not None:
+        index = np.asarray(index, dtype=np.int64).reshape(-1)
+        if index.size != len(rows):
+            raise ValueError("pyhgt_amd: one index per row")
+    ndcg, rr = np.zeros(len(rows)), np.zeros(len(rows))
+    for r, (beg, c) in enumerate(rows):
+        s = flat[beg:beg + c]
+        if labels is not None:
+            l = labels[beg:beg + c]
+        else:
+            l = np.zeros(c, np.float32)
+            t = 0 if index is None else int(index[r])
+            if 0 <= t < c:
+                l[t] = 1.0
+        ndcg[r], rr[r] = _np_row(s, l, k)
+    return ndcg, rr
+
+
+def np_pair_rank_loss(scores, sizes, return_grad=False):
+    """the loss of this module's docstring in float64 on the scores as given; with return_grad also d loss / d scores (g = 1)"""
+    x = np.asarray(scores).astype(np.float64).reshape(-1)
+    sizes = _np_sizes(sizes, x.size, 2)
+    loss, grad, beg = 0.0, np.zeros_like(x), 0
+    for l in sizes.tolist():
+        seg = x[beg:beg + l]
+        m = seg.max()
+        e = np.exp(seg - m)
+        loss += (m + np.log(e.sum()) - seg[0]) / np.log(l)
+        grad[beg:beg + l] = e / e.sum() / np.log(l)
+        grad[beg] -= 1.0 / np.log(l)
+        beg += l
+    return (loss, grad) if return_grad else loss
+
+
+# ---------------------------------------------------------------------------------------------------------------- the device calls
+class Segments:
+    """The rows of a flat score vector: `sizes` (a host sequence, `key_size` of the author script) with their offsets as an int64
+    device tensor, built once and good for any number of rank_metrics / pair_rank_loss calls on that device."""
+
+    def __init__(self, sizes, device=None):
+        self.sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+        if self.sizes.size and self.sizes.min() < 0:
+            raise ValueError("pyhgt_amd: a negative segment size")
+        self.n, self.total = int(self.sizes.size), int(self.sizes.sum())
+        self.longest, self.shortest = (int(self.sizes.max()), int(self.sizes.min())) if self.n else (0, 0)
+        if self.n >= 2 ** 31 or self.longest >= 2 ** 31 - 1024:
+            raise ValueError("pyhgt_amd: too many or too long segments")
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.row_ptr = None
+        if self.device is not None and self.device.type == "cuda":
+            self.row_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)).to(self.device)
+
+    @classmethod
+    def of(cls, sizes, like):
+        if isinstance(sizes, cls):
+            if like.is_cuda and (sizes.device is None or sizes.device != like.device):
+                raise ValueError("pyhgt_amd: the Segments were built for %s, the scores are on %s" % (sizes.device, like.device))
+            return sizes
+        return cls(sizes, like.device)
+
+
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _rows_f32(t, what):
+    """a float32 device tensor whose last dimension has unit stride (a column slice of a wider tensor stays as it is)"""
+    if t.dtype != torch.float32:
+        raise TypeError("pyhgt_amd: %s must be float32, got %s" % (what, t.dtype))
+    if t.dim() == 2 and t.size(0) > 0 and t.size(1) > 0 and (t.stride(1) != 1 and t.size(1) > 1 or t.stride(0) < t.size(1)):
+        t = t.contiguous()
+    elif t.dim() == 1 and t.numel() > 1 and t.stride(0) != 1:
+        t = t.contiguous()
+    return t
+
+
+def rank_metrics(scores, labels=None, index=None, k=None, sizes=None):
+    """(ndcg, rr) of every row: float64 tensors on the scores' device, one value per row (the definitions are in the module docstring).
+    scores: float32 [n, C] with unit column stride -- a column slice of a wider tensor is read in place -- or, with `sizes` (a host
+    sequence or a `Segments`), a flat float32 [L].  labels: float32 shaped like the scores; index: integers, one per row; neither: the
+    first position of every row is the positive.  One call of hgt_rank_metrics on the current stream, no synchronisation.  On CPU
+    tensors the result is np_rank_metrics's."""
+    k = _check_k(k)
+    if not isinstance(scores, torch.Tensor):
+        raise TypeError("pyhgt_amd: scores must be a torch tensor")
+    if scores.dtype != torch.float32:
+        raise TypeError("pyhgt_amd: scores must be float32, got %s" % scores.dtype)
+    if labels is not None and index is not None:
+        raise ValueError("pyhgt_amd: labels or index, not both")
+    if not scores.is_cuda:
+        host = lambda t: None if t is None else torch.as_tensor(t).detach().cpu().numpy()
+        ndcg, rr = np_rank_metrics(scores.detach().numpy(), host(labels), host(index), k, sizes)
+        return torch.from_numpy(ndcg), torch.from_numpy(rr)
+    scores = scores.detach()
+    if sizes is None:
+        if scores.dim() != 2:
+            raise ValueError("pyhgt_amd: scores are [n, C], or flat with sizes")
+        seg, (n, n_cols) = None, scores.shape
+        if n_cols >= 2 ** 31 - 1024 or n >= 2 ** 31:
+            raise ValueError("pyhgt_amd: too many rows or columns")
+    else:
+        if scores.dim() != 1:
+            raise ValueError("pyhgt_amd: with sizes the scores are flat")
+        seg = Segments.of(sizes, scores)
+        if seg.total != scores.numel():
+            raise ValueError("pyhgt_amd: sizes add up to %d, the scores have %d entries" % (seg.total, scores.numel()))
+        n, n_cols = seg.n, seg.longest
+    scores = _rows_f32(scores, "scores")
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or labels.device != scores.device or labels.shape != scores.shape:
+            raise ValueError("pyhgt_amd: labels are a tensor shaped like the scores, on their device")
+        labels = _rows_f32(labels.detach(), "labels")
+    if index is not None:
+        index = torch.as_tensor(index, device=scores.device).reshape(-1).to(torch.int64).contiguous()
+        if index.numel() != n:
+            raise ValueError("pyhgt_amd: one index per row")
+    ndcg = torch.empty(n, dtype=torch.float64, device=scores.device)
+    rr = torch.empty(n, dtype=torch.float64, device=scores.device)
+    ld = lambda t: 0 if t is None or t.dim() != 2 else max(int(t.stride(0)), n_cols)
+    with torch.cuda.device(scores.device):
+        _lib.check(_lib.load().hgt_rank_metrics(_ptr(scores), _ptr(labels), _ptr(index), None if seg is None else seg.row_ptr.data_ptr(), n,
+                                                n_cols, ld(scores), ld(labels), 0 if k is None else min(k, 2 ** 31 - 1), _ptr(ndcg), _ptr(rr),
+                                                _stream(scores)), "hgt_rank_metrics")
+    return ndcg, rr
+
+
+class _PairRankLoss(torch.autograd.Function):
+    """per-segment losses [n] of a flat float32 score vector (hgt_segment_first_nll / _bwd)"""
+
+    @staticmethod
+    def forward(ctx, scores, seg):
+        x = scores.detach().contiguous()
+        loss = torch.empty(seg.n, dtype=torch.float32, device=x.device)
+        lse = torch.empty(seg.n, 2, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().hgt_segment_first_nll(_ptr(x), seg.row_ptr.data_ptr(), seg.n, seg.longest, _ptr(loss), _ptr(lse), _stream(x)),
+                       "hgt_segment_first_nll")
+        ctx.save_for_backward(x, lse)
+        ctx.seg = seg
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        x, lse = ctx.saved_tensors
+        seg = ctx.seg
+        g = grad_loss.detach().float().contiguous()
+        grad = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().hgt_segment_first_nll_bwd(_ptr(x), seg.row_ptr.data_ptr(), seg.n, seg.longest, _ptr(lse), _ptr(g), _ptr(grad),
+                                                             _stream(x)), "hgt_segment_first_nll_bwd")
+        return grad, None
+
+
+def pair_rank_loss(scores, sizes, reduce=True):
+    """The pair-ranking loss of the author-disambiguation script (`mask_softmax`): scores flat float32 [L] on the device -- the output
+    of Matcher(pair=True) -- and `sizes`, a host sequence (`key_size`) or a `Segments`, every one >= 2 (ValueError otherwise: the
+    reference divides by log 1 = 0 there).  Differentiable; forward and backward are one call each on the current stream, without
+    atomics, so the result is the same bits every time.  reduce=False returns the per-segment terms [n] instead of their sum."""
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32:
+        raise TypeError("pyhgt_amd: scores must be a float32 tensor")
+    if scores.dim() != 1:
+        raise ValueError("pyhgt_amd: the scores are flat")
+    if not scores.is_cuda:
+        raise RuntimeError("pyhgt_amd: pair_rank_loss runs only on a ROCm GPU tensor; np_pair_rank_loss is the definition on the host")
+    seg = Segments.of(sizes, scores)
+    if seg.n and seg.shortest < 2:
+        raise ValueError("pyhgt_amd: a segment shorter than 2")
+    if seg.total != scores.numel():
+        raise ValueError("pyhgt_amd: sizes add up to %d, the scores have %d entries" % (seg.total, scores.numel()))
+    if seg.n == 0:
+        terms = scores.new_zeros(0) + scores.sum() * 0
+    else:
+        terms = _PairRankLoss.apply(scores, seg)
+    return terms.sum() if reduce else terms

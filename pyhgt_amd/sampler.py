@@ -350,6 +350,24 @@ class _SampledDeviceGraph(_Seeds, _DeviceGraph):
     """Result of sample_subgraph_device: a `_DeviceGraph` with `.indxs`, `.times` and `.n_seed`."""
 
 
+def candidate_pairs(g, name_label, target_type="paper", candidate_type="author"):
+    """The keys of the author-disambiguation script (OAG/train_author_disambiguation.py:280-289) for a sampled piece `g` whose seeds
+    are the papers and the candidate authors: `name_label[i]` = the serials among the `candidate_type` seeds of paper seed i's
+    candidates, the true one first.  -> (paper_key, author_key, sizes): two int64 row tensors on g's device, one entry per (paper,
+    candidate) pair in order -- `node_rep[paper_key]`, `node_rep[author_key]` feed Matcher(pair=True) -- and `sizes` (numpy int64, the
+    script's `key_size`).  One host array of serials goes to the device; the rows are gathered from `seed_rows` there."""
+    if len(name_label) != g.n_seed[target_type]:
+        raise ValueError("pyhgt_amd: %d candidate lists for %d %s seeds" % (len(name_label), g.n_seed[target_type], target_type))
+    sizes = np.fromiter((len(c) for c in name_label), dtype=np.int64, count=len(name_label))
+    flat = np.fromiter((a for c in name_label for a in c), dtype=np.int64, count=int(sizes.sum()))
+    if flat.size and (flat.min() < 0 or flat.max() >= g.n_seed[candidate_type]):
+        raise IndexError("pyhgt_amd: candidate serials outside [0, %d)" % g.n_seed[candidate_type])
+    targets, candidates = g.seed_rows(target_type), g.seed_rows(candidate_type)
+    dev = targets.device
+    paper_key = torch.repeat_interleave(targets, torch.from_numpy(sizes).to(dev), output_size=int(flat.size))
+    return paper_key, candidates[torch.from_numpy(flat).to(dev)], sizes
+
+
 def _wire_tuple(cls, dgraph, feat, n_per_type, src, dst, etime, rel_ptr, type_off):
     """the reference's int64 tensors, derived as to_device_graph derives them"""
     dev = src.device
