@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import hgt_oracle as O
+from oracle.task_steps import gnn_rep
 from pyhgt_amd import HGTConv, GNN, GraphPlan, _lib
 from pyhgt_amd.autograd import spmm_takes_items
 from pyhgt_amd.synth import synthetic_typed_graph
@@ -177,13 +178,7 @@ def test_gnn_training_step_matches_autograd_through_the_oracle():
     # the same computation in fp64 torch on the CPU
     P = {k: v.detach().cpu().double().requires_grad_(True) for k, v in list(gnn.named_parameters()) + [("head." + k, v) for k, v in
                                                                                                      head.named_parameters()]}
-    h = torch.zeros(N, d, dtype=torch.float64)
-    for t in range(T):
-        idx = (nt == t).nonzero().flatten()
-        h = h.index_add(0, idx, torch.tanh(x[idx].double() @ P["adapt_ws.%d.weight" % t].T + P["adapt_ws.%d.bias" % t]))
-    for li in range(2):
-        sd = {k[len("gcs.%d.base_conv." % li):]: v for k, v in P.items() if k.startswith("gcs.%d.base_conv." % li)}
-        h = O.forward_closed_form(sd, T, R, H, h, nt, ei, et, tm, use_norm=True, use_RTE=True)
+    h = gnn_rep(P, T, R, H, 2, x, nt, tm, ei, et)             # adapter + tanh + forward_closed_form per layer (oracle/task_steps.py)
     logp = torch.log_softmax(h[:200] @ P["head.linear.weight"].T + P["head.linear.bias"], dim=-1)
     ref_loss = torch.nn.functional.nll_loss(logp, y)
     ref_loss.backward()

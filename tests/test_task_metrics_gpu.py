@@ -1,6 +1,7 @@
 """The task-metric kernels (csrc/hgt_task_metrics.hip) on the GPU against the numpy rule of pyhgt_amd/metrics.py on the same inputs: both
 ranks are integers, so the reciprocal rank is bit-equal and NDCG agrees to 1e-12 (fp64 sums of at most P terms, test_task_metrics.py);
-the loss kernels against float64 autograd of the formula, gated by the fp32 error of torch.log_softmax on the CPU on the same inputs;
+the loss kernels against float64 autograd of the formula, gated by the fp32 error of torch.log_softmax on the CPU on the same inputs
+(also at every multiple of the block of 256, for one segment and for 100 000, through strided and offset views, and with inf / NaN scores);
 and three steps of examples/train_author_disambiguation_device.py.  Reads committed fixtures only."""
 import importlib.util
 import math
@@ -271,6 +272,171 @@ def test_loss_backward_writes_every_element_once_and_argument_errors(loss_case):
         M.pair_rank_loss(x[:4].double(), [2, 2])
     empty = M.pair_rank_loss(torch.zeros(0, device=DEV), [])
     assert empty.item() == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------- the loss at its line edges
+EDGE_SIZES = [255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 5000]                       # both sides of every multiple of the block of 256
+EQUAL_SIZES = [2, 64, 65, 256, 1000]                                                      # segments of equal scores: the term is 1
+
+
+def _both(x, sizes, wts, terms_fn=_terms):
+    """float64 terms and gradient of sum(wts * terms), and the same in torch float32 on the CPU: the truth and the yardstick"""
+    out = []
+    for dtype in (torch.float64, torch.float32):
+        t = torch.from_numpy(x).to(dtype).requires_grad_()
+        terms = terms_fn(t, sizes)
+        (terms * torch.from_numpy(wts).to(dtype)).sum().backward()
+        out += [terms.detach().double().numpy(), t.grad.double().numpy()]
+    return out
+
+
+def _device(x, sizes, wts):
+    scores = torch.from_numpy(x).to(DEV).requires_grad_()
+    terms = M.pair_rank_loss(scores, sizes, reduce=False)
+    (terms * torch.from_numpy(wts).to(DEV)).sum().backward()
+    return terms.detach().cpu().double().numpy(), scores.grad.cpu().double().numpy()
+
+
+def test_loss_on_both_sides_of_every_block_multiple_with_the_true_entry_at_either_end():
+    """Segments of 255 .. 1025 and 5000 scores: a thread of the workgroup kernel walks 1 .. 20 entries, some threads one fewer.  The
+    true (first) entry is the row maximum in every third segment and the row minimum in every third; five segments hold equal scores,
+    where the term is ln(l) / ln(l) = 1.  Gate: 4 x the largest float32 error of torch over the segments of the case."""
+    rng = np.random.default_rng(23)
+    sizes = EDGE_SIZES + EQUAL_SIZES
+    x = rng.uniform(-30, 30, size=sum(sizes)).astype(np.float32)
+    beg = np.concatenate([[0], np.cumsum(sizes)])
+    for i in range(len(EDGE_SIZES)):
+        if i % 3 == 0:
+            x[beg[i]] = 31.0
+        elif i % 3 == 1:
+            x[beg[i]] = -31.0
+    for i, v in zip(range(len(EDGE_SIZES), len(sizes)), (2.5, -30.0, 0.0, 1e4, -7.25)):
+        x[beg[i]:beg[i + 1]] = v
+    wts = rng.uniform(0.5, 2.0, size=len(sizes)).astype(np.float32)
+    t64, g64, t32, g32 = _both(x, sizes, wts)
+    terms, grad = _device(x, sizes, wts)
+    gate_t, gate_g = 4 * np.abs(t32 - t64).max(), 4 * np.abs(g32 - g64).max()
+    print("loss at the block lines: terms max err %.3e (gate %.3e), gradient %.3e (gate %.3e); equal scores: |term - 1| max %.3e"
+          % (np.abs(terms - t64).max(), gate_t, np.abs(grad - g64).max(), gate_g, np.abs(terms[len(EDGE_SIZES):] - 1).max()))
+    assert abs(t64.sum() - M.np_pair_rank_loss(x, sizes)) < 1e-9
+    assert np.abs(t64[len(EDGE_SIZES):] - 1).max() < 1e-12
+    assert np.abs(terms - t64).max() <= gate_t and np.abs(grad - g64).max() <= gate_g
+    assert np.abs(terms[len(EDGE_SIZES):] - 1).max() <= gate_t
+
+
+def test_loss_of_a_single_segment_on_either_kernel():
+    """n_seg = 1: one wavefront of a workgroup of four has a segment (lengths <= 64), or the grid is one workgroup (longer).  The case
+    is the family of these calls: each is gated by 4 x the largest float32 error of torch over the family."""
+    rng = np.random.default_rng(29)
+    lengths = [2, 5, 33, 64, 65, 300, 1024, 5000]
+    runs = []
+    for l in lengths:
+        x = rng.uniform(-30, 30, size=l).astype(np.float32)
+        wts = np.array([1.5], np.float32)
+        runs.append(_both(x, [l], wts) + list(_device(x, [l], wts)))
+    gate_t = 4 * max(np.abs(r[2] - r[0]).max() for r in runs)
+    gate_g = 4 * max(np.abs(r[3] - r[1]).max() for r in runs)
+    for l, (t64, g64, t32, g32, terms, grad) in zip(lengths, runs):
+        print("one segment of %d: term err %.3e (gate %.3e), gradient err %.3e (gate %.3e)" % (l, abs(terms[0] - t64[0]), gate_t,
+                                                                                                np.abs(grad - g64).max(), gate_g))
+        assert terms.shape == (1,) and abs(terms[0] - t64[0]) <= gate_t and np.abs(grad - g64).max() <= gate_g
+
+
+def test_loss_of_a_hundred_thousand_pairs():
+    """100 000 segments of two scores: 25 000 workgroups of the wavefront kernel, two live lanes each"""
+    n = 100000
+    rng = np.random.default_rng(31)
+    x = rng.uniform(-30, 30, size=2 * n).astype(np.float32)
+    wts = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
+    pairs = lambda t, sizes: -torch.log_softmax(t.view(-1, 2), dim=1)[:, 0] / math.log(2)     # _terms for equal lengths, in one call
+    t64, g64, t32, g32 = _both(x, None, wts, terms_fn=pairs)
+    probe = rng.choice(n, size=50, replace=False)
+    for r in probe:                                                                       # the one call is the formula of _terms
+        assert abs(_terms(torch.from_numpy(x[2 * r:2 * r + 2]).double(), [2])[0].item() - t64[r]) < 1e-12
+    terms, grad = _device(x, np.full(n, 2), wts)
+    print("100000 pairs: terms max err %.3e (torch float32 %.3e), gradient %.3e (torch float32 %.3e)"
+          % (np.abs(terms - t64).max(), np.abs(t32 - t64).max(), np.abs(grad - g64).max(), np.abs(g32 - g64).max()))
+    assert np.abs(terms - t64).max() <= 4 * np.abs(t32 - t64).max() and np.abs(grad - g64).max() <= 4 * np.abs(g32 - g64).max()
+    total = M.pair_rank_loss(torch.from_numpy(x).to(DEV), np.full(n, 2))
+    unit = _both(x, None, np.ones(n, np.float32), terms_fn=pairs)
+    assert abs(total.item() - unit[0].sum()) <= 4 * np.abs(unit[2] - unit[0]).sum() + (n - 1) * 2.0 ** -24 * np.abs(unit[0]).sum()
+
+
+@pytest.mark.parametrize("view", ["every_second", "offset"])
+def test_loss_gradient_reaches_a_strided_or_offset_view_and_nothing_else(view):
+    """scores = wide[1::2], or a slice that starts 5 elements into its storage: the gradient arrives at those elements of `wide`; every
+    other element gets its gradient from a second leaf alone, a sentinel that must come through bit for bit"""
+    sizes = [3, 64, 65, 300, 2]
+    L = sum(sizes)
+    rng = np.random.default_rng(37)
+    x = rng.uniform(-30, 30, size=L).astype(np.float32)
+    wts = rng.uniform(0.5, 2.0, size=len(sizes)).astype(np.float32)
+    t64, g64, t32, g32 = _both(x, sizes, wts)
+    if view == "every_second":
+        host, mine = np.full(2 * L, 99.0, np.float32), np.zeros(2 * L, bool)
+        mine[1::2] = True
+        pick = lambda w: w[1::2]
+    else:
+        host, mine = np.full(L + 12, 99.0, np.float32), np.zeros(L + 12, bool)
+        mine[5:5 + L] = True
+        pick = lambda w: w[5:][:L]
+    host[mine] = x
+    wide = torch.from_numpy(host).to(DEV).requires_grad_()
+    sentinel = torch.full((int((~mine).sum()),), -12345.5, device=DEV, requires_grad=True)
+    scores = pick(wide)
+    assert scores.data_ptr() != wide.data_ptr() and (scores.stride(0) == 2 or scores.storage_offset() == 5)
+    terms = M.pair_rank_loss(scores, sizes, reduce=False)
+    ((terms * torch.from_numpy(wts).to(DEV)).sum() + (wide[torch.from_numpy(~mine).to(DEV)] * sentinel).sum()).backward()
+    grad = wide.grad.cpu().numpy()
+    assert np.array_equal(grad[~mine], np.full(int((~mine).sum()), -12345.5, np.float32))
+    assert torch.equal(sentinel.grad, torch.full_like(sentinel, 99.0))
+    assert np.abs(terms.detach().cpu().double().numpy() - t64).max() <= 4 * np.abs(t32 - t64).max()
+    assert np.abs(grad[mine].astype(np.float64) - g64).max() <= 4 * np.abs(g32 - g64).max()
+    plain = _device(x, sizes, wts)                                                        # the same bits as from a contiguous vector
+    assert np.array_equal(plain[0], terms.detach().cpu().double().numpy()) and np.array_equal(plain[1], grad[mine].astype(np.float64))
+
+
+NONFINITE = [("minus_inf_inside", lambda seg: seg.__setitem__(len(seg) // 2, -np.inf)),
+             ("minus_inf_first", lambda seg: seg.__setitem__(0, -np.inf)),
+             ("all_minus_inf", lambda seg: seg.__setitem__(slice(None), -np.inf)),
+             ("plus_inf", lambda seg: seg.__setitem__(len(seg) - 1, np.inf)),
+             ("one_nan", lambda seg: seg.__setitem__(1, np.nan))]
+
+
+@pytest.mark.parametrize("length", [40, 64, 65, 300])
+def test_loss_with_non_finite_scores_agrees_with_torch_log_softmax(length):
+    """-inf inside a segment (an ordinary score: weight 0), -inf first (the term is +inf, the gradient finite), a whole segment of
+    -inf, +inf and one NaN (torch gives NaN throughout such a segment), each between two clean segments, in a segment a wavefront
+    takes and in one a workgroup takes.  Against torch.log_softmax in float32 on the CPU: inf and NaN sit at the same positions of the
+    terms and of the gradient, with the same sign; the finite entries are within 4 x torch's float32 error over the finite entries of
+    the case; and the clean segments come out bit for bit as from a call without the others."""
+    rng = np.random.default_rng(41 + length)
+    sizes = [length if i % 2 else (7, 70)[(i // 2) % 2] for i in range(2 * len(NONFINITE) + 1)]      # clean, special, clean, ...
+    beg = np.concatenate([[0], np.cumsum(sizes)])
+    x = rng.uniform(-20, 20, size=sum(sizes)).astype(np.float32)
+    for i, (_, put) in enumerate(NONFINITE):
+        put(x[beg[2 * i + 1]:beg[2 * i + 2]])
+    wts = rng.uniform(0.5, 2.0, size=len(sizes)).astype(np.float32)
+    t64, g64, t32, g32 = _both(x, sizes, wts)
+    terms, grad = _device(x, sizes, wts)
+    want_terms = {"minus_inf_inside": np.isfinite, "minus_inf_first": np.isposinf, "all_minus_inf": np.isnan, "plus_inf": np.isnan,
+                  "one_nan": np.isnan}
+    for i, (name, _) in enumerate(NONFINITE):                                             # what torch gives is what the docstring says
+        assert want_terms[name](t32[2 * i + 1]), name
+        seg = g32[beg[2 * i + 1]:beg[2 * i + 2]]
+        assert np.isfinite(seg).all() if name.startswith("minus_inf") else np.isnan(seg).all(), name
+    for got, f32, f64, what in ((terms, t32, t64, "terms"), (grad, g32, g64, "gradient")):
+        assert np.array_equal(np.isnan(got), np.isnan(f32)), what
+        assert np.array_equal(np.isposinf(got), np.isposinf(f32)) and np.array_equal(np.isneginf(got), np.isneginf(f32)), what
+        fin = np.isfinite(f32)
+        assert np.array_equal(np.isfinite(f64), fin)
+        err, yard = np.abs(got[fin] - f64[fin]).max(), np.abs(f32[fin] - f64[fin]).max()
+        print("non-finite scores, length %d: %s: %d finite entries, max err %.3e, torch float32 %.3e" % (length, what, fin.sum(), err, yard))
+        assert err <= 4 * yard, what
+    clean = np.arange(0, len(sizes), 2)
+    keep = np.concatenate([np.arange(beg[i], beg[i + 1]) for i in clean])
+    alone = _device(x[keep], [sizes[i] for i in clean], wts[clean])
+    assert np.array_equal(alone[0], terms[clean]) and np.array_equal(alone[1], grad[keep])
 
 
 def test_author_disambiguation_example_runs_three_steps():
