@@ -1021,6 +1021,56 @@ int hgt_segment_first_nll(const float* scores, const int64_t* row_ptr, int32_t n
 int hgt_segment_first_nll_bwd(const float* scores, const int64_t* row_ptr, int32_t n_seg, int32_t max_len, const float* lse,
                               const float* grad_loss, float* grad_scores, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Classification losses (csrc/hgt_task_loss.hip, csrc/hgt_sampler_labels.hip): what the reference's paper-venue, ogbn-mag and
+ * paper-field scripts do with the Classifier's output -- log_softmax followed by nll_loss (OAG/train_paper_venue.py:86,
+ * ogbn-mag/train_ogbn_mag.py:116) or KLDivLoss(reduction='batchmean') (OAG/train_paper_field.py:87) -- on the raw logits, and the
+ * paper-field labels as a short list of class columns per row in place of a dense [n, C] distribution (train_paper_field.py:133-137).
+ * Added under ABI 8 (new symbols only).
+ *
+ *   hgt_class_loss          per row x of n_cols logits (float32): m = max x, ls = log(sum exp(x - m)), logp_j = (x_j - m) - ls, in fp32
+ *                           as torch.log_softmax forms them.  lse_out[2 r] = m, lse_out[2 r + 1] = ls (the logsumexp in its two parts,
+ *                           so that the backward forms the same difference).  Exactly one label form is given:
+ *                             index (int64[n_rows])     loss_out[r] = -logp_y, wsum_out[r] = 1;  y < 0: the row is ignored -- term 0,
+ *                                                       W 0;  y >= n_cols: NaN, and nothing out of range is read
+ *                             labels (float32, row r at labels + r * ld_labels)   loss_out[r] = sum over l_j > 0 of
+ *                                                       l_j (log l_j - logp_j), the rows of kl_div(reduction='none').sum(1);
+ *                                                       wsum_out[r] = sum l_j;  an entry < 0 or NaN: NaN
+ *                             columns (int32[n_rows, width], -1 = padding)   with c = the number of entries >= 0 of the row (distinct
+ *                                                       by contract): -log c - (1 / c) sum logp_col, the dense form with l = 1 / c on
+ *                                                       those columns; W = 1;  c = 0: term 0, W 0;  an entry >= n_cols: NaN;  with
+ *                                                       `count` (int32[n_rows], optional: the true number of classes of the row)
+ *                                                       count[r] > width: NaN -- a truncated list is never scored silently
+ *                           A NaN term is saved with W = NaN.  The label-weighted terms are summed in fp64 in an order fixed by the
+ *                           row alone and rounded once to float32.
+ *   hgt_class_loss_bwd      grad_logits[r * ld_grad + j] = grad_loss[r] * (W_r * exp((x_j - m) - ls) - l_rj) for j < n_cols, l the
+ *                           row's label distribution (1 at the index, the dense entries, 1 / c on the listed columns); the columns
+ *                           n_cols .. ld_grad of a row are left untouched.  A row with W = 0 and no dense labels gets exact zeros, a
+ *                           row with W = NaN gets NaN.  One launch, no float atomic.
+ *                           Both: row r is at logits + r * ld, ld >= n_cols, any alignment (16-byte loads where the row's base
+ *                           allows).  Rows of at most HGT_CLASS_LOSS_WAVE_COLS columns take a wavefront each, longer ones a workgroup
+ *                           each, streamed twice; a position always belongs to the same thread, so a row's bits do not depend on its
+ *                           alignment, n_rows, the other rows or the launch geometry.  No allocation, no synchronisation.  All arrays
+ *                           are device arrays.  n_rows == 0: HGT_OK without a launch.  No label form or more than one, count without
+ *                           columns, a negative size, ld (ld_labels, ld_grad) < n_cols, width < 1 with columns, a NULL output or
+ *                           NULL logits with n_cols > 0: HGT_ERR_INVALID_ARG; n_cols > INT32_MAX - 1024: HGT_ERR_UNSUPPORTED; no launch.
+ *   hgt_sampler_label_columns   hgt_sampler_labels's arguments and row rule; the set C of row r is written as a list:
+ *                           columns_out[r * width + i] = the i-th smallest column of C for i < min(|C|, width), -1 behind it;
+ *                           count_out[r] = |C| whether it fitted or not (count_out may be NULL).  One launch, one workgroup per row:
+ *                           a prefix popcount over the LDS bitmap of hgt_sampler_labels, chunk after chunk.  The argument errors of
+ *                           hgt_sampler_labels, and width < 1 or columns_out == NULL with n > 0: HGT_ERR_INVALID_ARG, no launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_CLASS_LOSS_WAVE_COLS 256
+int hgt_class_loss(const float* logits, int64_t ld, int32_t n_rows, int32_t n_cols, const float* labels, int64_t ld_labels,
+                   const int64_t* index, const int32_t* columns, int32_t width, const int32_t* count, float* loss_out, float* lse_out,
+                   float* wsum_out, void* stream);
+int hgt_class_loss_bwd(const float* logits, int64_t ld, int32_t n_rows, int32_t n_cols, const float* labels, int64_t ld_labels,
+                       const int64_t* index, const int32_t* columns, int32_t width, const int32_t* count, const float* lse,
+                       const float* wsum, const float* grad_loss, float* grad_logits, int64_t ld_grad, void* stream);
+int hgt_sampler_label_columns(const hgt_sampler_triple* triple_host, int32_t n_tgt_nodes, int32_t n_src_nodes, const int32_t* ids,
+                              int32_t n, const int32_t* col_of, int32_t n_cols, int32_t has_window, int32_t t_min, int32_t t_max,
+                              int32_t* columns_out, int32_t width, int32_t* count_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,9 +8,9 @@ from .model import GNN, Classifier, Matcher  # noqa: F401
 from .autograd import set_deterministic, set_recompute  # noqa: F401
 from .sampler import (DeviceHeteroGraph, sample_subgraph_device, sample_subgraph_host, sample_subgraphs_device,  # noqa: F401
                       sample_subgraphs_host)
-from .sampler import LabelSpace, seed_edge_mask, np_label_distribution, np_label_index, np_label_counts  # noqa: F401
+from .sampler import LabelSpace, seed_edge_mask, np_label_distribution, np_label_index, np_label_counts, np_label_columns  # noqa: F401
 from .sampler import candidate_pairs  # noqa: F401
-from .metrics import Segments, rank_metrics, pair_rank_loss, np_rank_metrics, np_pair_rank_loss  # noqa: F401
+from .metrics import Segments, rank_metrics, pair_rank_loss, class_loss, np_rank_metrics, np_pair_rank_loss, np_class_loss  # noqa: F401
 
 __all__ = ["HGTConv", "DenseHGTConv", "GeneralConv", "RelTemporalEncoding", "GraphPlan", "install_into", "GNN", "Classifier", "Matcher",
            "set_deterministic", "set_recompute", "DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "sample_subgraphs_device",

@@ -100,6 +100,7 @@ class HgtSamplerMask(C.Structure):
 
 
 RANK_LIST_CAP = 1024     # HGT_RANK_LIST_CAP: positives a pass of hgt_rank_metrics holds
+CLASS_LOSS_WAVE_COLS = 256   # HGT_CLASS_LOSS_WAVE_COLS: the longest row of hgt_class_loss that takes a wavefront
 ABI_VERSION = 8          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
 
 _i32, _i64, _u64, _vp = C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
@@ -251,6 +252,12 @@ SIGNATURES = {
     "hgt_rank_metrics": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
     "hgt_segment_first_nll": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "hgt_segment_first_nll_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # classification losses (csrc/hgt_task_loss.hip): (logits, ld, n_rows, n_cols, labels, ld_labels, index, columns, width, count, loss_out,
+    # lse_out, wsum_out, stream) and (..., count, lse, wsum, grad_loss, grad_logits, ld_grad, stream); the labels as column lists
+    # (csrc/hgt_sampler_labels.hip): hgt_sampler_labels's arguments up to t_max, then (columns_out, width, count_out, stream)
+    "hgt_class_loss": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "hgt_class_loss_bwd": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hgt_sampler_label_columns": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
 }
 
 _lib = None

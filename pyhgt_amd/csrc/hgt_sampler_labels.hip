@@ -9,11 +9,15 @@
 //   dist[r, c]          1.0f / (float)|C| for c in C, 0 for every other c < n_cols (the whole row is written; the padding is not)
 //   index[r]            the column of the first qualifying neighbour in adjacency order, -1 without one
 //   count[r]            |C|
+//   columns[r, i]       hgt_sampler_label_columns: the i-th smallest column of C for i < min(|C|, width), -1 behind it -- the same set
+//                       as a list, for hgt_class_loss, in place of a dense row that holds a handful of non-zeros
 //
 // One workgroup per row.  C is a bitmap in LDS (integer atomicOr: the same bits whatever the order), LABEL_CHUNK columns a pass; the
 // first qualifying position is an integer atomicMin.  The count is known before a value is written, so a row is written once, each
 // element by one thread: no float atomics, and nothing depends on the launch geometry.  Compiled without fast-math like the rest of
-// the library: 1.0f / count is the IEEE quotient.
+// the library: 1.0f / count is the IEEE quotient.  The list form walks the same bitmap: a thread owns LABEL_WORDS / LABEL_BLOCK
+// consecutive words, a prefix sum of their popcounts over the workgroup gives the place of its first column, and the columns of a
+// chunk follow those of the chunks in front of it -- ascending, each written by one thread.
 #include "hgt_common.h"
 
 namespace {
@@ -21,6 +25,7 @@ namespace {
 constexpr int LABEL_BLOCK = 256;
 constexpr int LABEL_WORDS = 4096;                       // 16 KB of LDS
 constexpr int LABEL_CHUNK = LABEL_WORDS * 32;           // columns a pass of the bitmap covers
+constexpr int LABEL_OWN = LABEL_WORDS / LABEL_BLOCK;    // list form: consecutive words a thread owns
 
 struct LabelArgs {
     const int32_t* indptr;
@@ -31,13 +36,16 @@ struct LabelArgs {
     float* dist;
     int32_t* index;
     int32_t* count;
+    int32_t* columns;
     int64_t ld;
+    int32_t width;
     int32_t n_tgt, n_src, n, n_cols, has_window, t_min, t_max;
 };
 
+template <bool LIST>
 __global__ void __launch_bounds__(LABEL_BLOCK) k_labels(LabelArgs A) {
     __shared__ uint32_t bits[LABEL_WORDS];
-    __shared__ int first, total;
+    __shared__ int first, total, wtot[LABEL_BLOCK / 64];
     const int r = blockIdx.x, k = threadIdx.x;
     if (r >= A.n) return;                                                         // workgroup-uniform
     const int v = A.ids[r];
@@ -78,6 +86,45 @@ __global__ void __launch_bounds__(LABEL_BLOCK) k_labels(LabelArgs A) {
     auto words_of = [&](int c0) { return (min(A.n_cols - c0, LABEL_CHUNK) + 31) >> 5; };
     const bool one_pass = A.n_cols <= LABEL_CHUNK;
     __syncthreads();
+    if constexpr (LIST) {
+        int32_t* out = A.columns + (int64_t)r * A.width;
+        const int lane = k & 63, wave = k >> 6;
+        int seen = 0;                                                             // classes in the chunks in front of this one
+        for (int c0 = 0; c0 < A.n_cols; c0 += LABEL_CHUNK) {
+            const int words = words_of(c0);
+            mark(c0, words, false);
+            int mine = 0;
+            for (int i = 0; i < LABEL_OWN; ++i) {
+                const int w = k * LABEL_OWN + i;
+                if (w < words) mine += __popc(bits[w]);
+            }
+            int inc = mine;
+            for (int o = 1; o < 64; o <<= 1) {
+                const int up = __shfl_up(inc, o);
+                if (lane >= o) inc += up;
+            }
+            if (lane == 63) wtot[wave] = inc;
+            __syncthreads();
+            int at = seen + inc - mine;
+            for (int q = 0; q < LABEL_BLOCK / 64; ++q) {
+                if (q < wave) at += wtot[q];
+                seen += wtot[q];
+            }
+            for (int i = 0; i < LABEL_OWN; ++i) {
+                const int w = k * LABEL_OWN + i;
+                uint32_t word = w < words ? bits[w] : 0u;
+                while (word) {
+                    if (at < A.width) out[at] = c0 + w * 32 + (__ffs(word) - 1);
+                    ++at;
+                    word &= word - 1u;
+                }
+            }
+            __syncthreads();                                                      // bits and wtot are written again by the next chunk
+        }
+        for (int i = seen + k; i < A.width; i += LABEL_BLOCK) out[i] = -1;
+        if (k == 0 && A.count) A.count[r] = seen;
+        return;
+    }
     for (int c0 = 0; c0 < A.n_cols; c0 += LABEL_CHUNK) {
         const int words = words_of(c0);
         mark(c0, words, c0 == 0);
@@ -102,25 +149,50 @@ __global__ void __launch_bounds__(LABEL_BLOCK) k_labels(LabelArgs A) {
     }
 }
 
-}  // namespace
-
-extern "C" int hgt_sampler_labels(const hgt_sampler_triple* triple_host, int32_t n_tgt_nodes, int32_t n_src_nodes, const int32_t* ids, int32_t n,
-                                  const int32_t* col_of, int32_t n_cols, int32_t has_window, int32_t t_min, int32_t t_max, float* dist_out,
-                                  int64_t ld, int32_t* index_out, int32_t* count_out, void* stream) {
+// the checks and the input half of the arguments that both entry points share (n == 0: HGT_OK with nothing filled in)
+int label_args(const hgt_sampler_triple* triple_host, int32_t n_tgt_nodes, int32_t n_src_nodes, const int32_t* ids, int32_t n,
+               const int32_t* col_of, int32_t n_cols, int32_t has_window, int32_t t_min, int32_t t_max, LabelArgs& A) {
     if (n < 0 || n_tgt_nodes < 0 || n_src_nodes < 0 || n_cols < 0) return HGT_ERR_INVALID_ARG;
-    if (dist_out && ld < n_cols) return HGT_ERR_INVALID_ARG;
     if (has_window && t_min > t_max) return HGT_ERR_INVALID_ARG;
     if (n == 0) return HGT_OK;
     if (!triple_host || !ids) return HGT_ERR_INVALID_ARG;
     const hgt_sampler_triple& tr = *triple_host;
     if (!tr.indptr) return HGT_ERR_INVALID_ARG;                                   // [n_tgt_nodes + 1] entries even without a node
     if (n_tgt_nodes > 0 && n_src_nodes > 0 && (!tr.src || !col_of || (has_window && !tr.time))) return HGT_ERR_INVALID_ARG;
-    LabelArgs A;
     A.indptr = tr.indptr; A.src = tr.src; A.time = tr.time; A.ids = ids; A.col_of = col_of;
-    A.dist = dist_out; A.index = index_out; A.count = count_out; A.ld = ld;
     A.n_tgt = n_tgt_nodes; A.n_src = n_src_nodes; A.n = n; A.n_cols = n_cols;
     A.has_window = has_window != 0; A.t_min = t_min; A.t_max = t_max;
-    k_labels<<<(unsigned)n, LABEL_BLOCK, 0, (hipStream_t)stream>>>(A);
+    return HGT_OK;
+}
+
+}  // namespace
+
+extern "C" int hgt_sampler_labels(const hgt_sampler_triple* triple_host, int32_t n_tgt_nodes, int32_t n_src_nodes, const int32_t* ids, int32_t n,
+                                  const int32_t* col_of, int32_t n_cols, int32_t has_window, int32_t t_min, int32_t t_max, float* dist_out,
+                                  int64_t ld, int32_t* index_out, int32_t* count_out, void* stream) {
+    if (dist_out && ld < n_cols) return HGT_ERR_INVALID_ARG;
+    LabelArgs A;
+    const int rc = label_args(triple_host, n_tgt_nodes, n_src_nodes, ids, n, col_of, n_cols, has_window, t_min, t_max, A);
+    if (rc != HGT_OK || n == 0) return rc;
+    A.dist = dist_out; A.index = index_out; A.count = count_out; A.ld = ld;
+    A.columns = nullptr; A.width = 0;
+    k_labels<false><<<(unsigned)n, LABEL_BLOCK, 0, (hipStream_t)stream>>>(A);
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+extern "C" int hgt_sampler_label_columns(const hgt_sampler_triple* triple_host, int32_t n_tgt_nodes, int32_t n_src_nodes, const int32_t* ids,
+                                         int32_t n, const int32_t* col_of, int32_t n_cols, int32_t has_window, int32_t t_min, int32_t t_max,
+                                         int32_t* columns_out, int32_t width, int32_t* count_out, void* stream) {
+    LabelArgs A;
+    const int rc = label_args(triple_host, n_tgt_nodes, n_src_nodes, ids, n, col_of, n_cols, has_window, t_min, t_max, A);
+    if (rc != HGT_OK) return rc;
+    if (width < 1) return HGT_ERR_INVALID_ARG;
+    if (n == 0) return HGT_OK;
+    if (!columns_out) return HGT_ERR_INVALID_ARG;
+    A.dist = nullptr; A.index = nullptr; A.count = count_out; A.ld = 0;
+    A.columns = columns_out; A.width = width;
+    k_labels<true><<<(unsigned)n, LABEL_BLOCK, 0, (hipStream_t)stream>>>(A);
     HGT_CHECK_LAUNCH();
     return HGT_OK;
 }

@@ -1,4 +1,4 @@
-"""Scoring a task batch: NDCG, MRR and the pair-ranking loss of the reference's training scripts, on the device.
+"""Scoring a task batch: NDCG, MRR, the pair-ranking loss and the classification losses of the reference's training scripts, on the device.
 
 After a step the scripts of the reference take one `argsort` row of the model's output at a time to the host and run `ndcg_at_k` and
 `mean_reciprocal_rank` (pyHGT/utils.py:5-20) on it (OAG/train_paper_field.py:272-275, 303-308 and its siblings); the author
@@ -28,13 +28,26 @@ disambiguation: the true author comes first).  Rows: scores [n, C], or a flat [L
 Loss.  For segments of lengths l_s >= 2 over a flat score vector:
 
     loss = sum_s (logsumexp(seg_s) - seg_s[0]) / ln(l_s),    d loss / d s_j = g * (softmax(seg_s)_j - [j is first]) / ln(l_s)
+
+Classification losses (`class_loss`, csrc/hgt_task_loss.hip; the rule is `np_class_loss`).  The paper-venue, ogbn-mag and paper-field
+scripts put log_softmax + nll_loss (OAG/train_paper_venue.py:86, ogbn-mag/train_ogbn_mag.py:116) or KLDivLoss('batchmean')
+(OAG/train_paper_field.py:87) on the Classifier's output.  Here the raw logits x [n, C] go in; logp_j = x_j - max x - log sum exp(x - max x),
+and a row's term and label weight W come from one of three label forms:
+
+    index y      term = -logp_y, W = 1;   y < 0: the row is ignored (term 0, W 0, gradient row 0);   y >= C: NaN
+    labels l     term = sum over l_j > 0 of l_j (log l_j - logp_j), W = sum l_j;   an entry < 0 or NaN: NaN
+    columns      [n, width] class columns, -1 = padding, distinct within a row; c = the number of entries >= 0:
+                 term = -log c - (1 / c) sum logp_col = the dense form with l = 1 / c on those columns, W = 1;   c = 0: term 0, W 0;
+                 an entry >= C: NaN;   with `count` (the true number of classes of a row) count > width: NaN
+
+    d term / d x_j = W softmax(x)_j - l_j;   a NaN term has a NaN gradient row
 """
 import numpy as np
 import torch
 
 from . import _lib
 
-__all__ = ["Segments", "rank_metrics", "pair_rank_loss", "np_rank_metrics", "np_pair_rank_loss", "np_ranks"]
+__all__ = ["Segments", "rank_metrics", "pair_rank_loss", "class_loss", "np_rank_metrics", "np_pair_rank_loss", "np_class_loss", "np_ranks"]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rule
@@ -134,6 +147,69 @@ def np_pair_rank_loss(scores, sizes, return_grad=False):
         grad[beg] -= 1.0 / np.log(l)
         beg += l
     return (loss, grad) if return_grad else loss
+
+
+def _one_label_form(labels, index, columns, count):
+    if (labels is not None) + (index is not None) + (columns is not None) != 1:
+        raise ValueError("pyhgt_amd: exactly one of labels, index and columns")
+    if count is not None and columns is None:
+        raise ValueError("pyhgt_amd: count goes with columns")
+
+
+def np_class_loss(logits, labels=None, index=None, columns=None, count=None, return_grad=False):
+    """the per-row terms of this module's docstring in float64 on the logits as given: float64 [n]; with return_grad also
+    d(sum of the terms) / d logits, float64 [n, C]"""
+    _one_label_form(labels, index, columns, count)
+    x = np.asarray(logits).astype(np.float64)
+    if x.ndim != 2:
+        raise ValueError("pyhgt_amd: logits are [n, C]")
+    n, C = x.shape
+    if labels is not None:
+        labels = np.asarray(labels).astype(np.float64)
+        if labels.shape != x.shape:
+            raise ValueError("pyhgt_amd: labels are shaped like the logits")
+    if index is not None:
+        index = np.asarray(index, dtype=np.int64).reshape(-1)
+        if index.size != n:
+            raise ValueError("pyhgt_amd: one index per row")
+    if columns is not None:
+        columns = np.asarray(columns, dtype=np.int64)
+        if columns.ndim != 2 or columns.shape[0] != n or columns.shape[1] < 1:
+            raise ValueError("pyhgt_amd: columns are [n, width >= 1]")
+        if count is not None:
+            count = np.asarray(count, dtype=np.int64).reshape(-1)
+            if count.size != n:
+                raise ValueError("pyhgt_amd: one count per row")
+    terms, grad = np.zeros(n), np.zeros((n, C))
+    with np.errstate(all="ignore"):
+        for r in range(n):
+            m = x[r].max() if C else -np.inf
+            e = np.exp(x[r] - m)
+            logp = x[r] - m - np.log(e.sum())
+            p, l, W = e / e.sum(), np.zeros(C), 0.0
+            if index is not None:
+                y = int(index[r])
+                if y >= C:
+                    W = np.nan
+                elif y >= 0:
+                    l[y], W, terms[r] = 1.0, 1.0, -logp[y]
+            elif labels is not None:
+                l = labels[r]
+                pos = l > 0
+                W = np.nan if not (l >= 0).all() else float(l[pos].sum())
+                terms[r] = float(np.sum(l[pos] * (np.log(l[pos]) - logp[pos])))
+            else:
+                ent = columns[r][columns[r] >= 0]
+                if (ent >= C).any() or (count is not None and count[r] > columns.shape[1]):
+                    W = np.nan
+                elif ent.size:
+                    l[ent], W = 1.0 / ent.size, 1.0
+                    terms[r] = -np.log(ent.size) - float(np.sum(logp[ent])) / ent.size
+            if np.isnan(W):
+                terms[r], grad[r] = np.nan, np.nan
+            elif W != 0 or labels is not None:
+                grad[r] = W * p - l
+    return (terms, grad) if return_grad else terms
 
 
 # ---------------------------------------------------------------------------------------------------------------- the device calls
@@ -282,3 +358,83 @@ def pair_rank_loss(scores, sizes, reduce=True):
     else:
         terms = _PairRankLoss.apply(scores, seg)
     return terms.sum() if reduce else terms
+
+
+class _ClassLoss(torch.autograd.Function):
+    """per-row terms [n] and label weights [n] of float32 logits [n, C] (hgt_class_loss / _bwd); the labels are constants"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, index, columns, count):
+        x = _rows_f32(logits.detach(), "logits")
+        n, n_cols = x.shape
+        loss = torch.empty(n, dtype=torch.float32, device=x.device)
+        lse = torch.empty(n, 2, dtype=torch.float32, device=x.device)
+        wsum = torch.empty(n, dtype=torch.float32, device=x.device)
+        ld = lambda t: 0 if t is None else max(int(t.stride(0)), n_cols)
+        ctx.call = (_ptr(x), ld(x), n, n_cols, _ptr(labels), ld(labels), _ptr(index), _ptr(columns), 0 if columns is None else columns.size(1),
+                    _ptr(count))
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().hgt_class_loss(*ctx.call, _ptr(loss), _ptr(lse), _ptr(wsum), _stream(x)), "hgt_class_loss")
+        ctx.save_for_backward(x, lse, wsum, *(t for t in (labels, index, columns, count) if t is not None))
+        ctx.mark_non_differentiable(wsum)
+        return loss, wsum
+
+    @staticmethod
+    def backward(ctx, grad_loss, _):
+        x, lse, wsum = ctx.saved_tensors[:3]
+        g = grad_loss.detach().float().contiguous()
+        grad = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().hgt_class_loss_bwd(*ctx.call, _ptr(lse), _ptr(wsum), _ptr(g), _ptr(grad), x.size(1), _stream(x)),
+                       "hgt_class_loss_bwd")
+        return grad, None, None, None, None
+
+
+def class_loss(logits, labels=None, index=None, columns=None, count=None, reduce="mean"):
+    """The classification losses of the paper-venue / ogbn-mag scripts (`index`: log_softmax + NLLLoss) and of the paper-field script
+    (`labels`, or the same distribution as `columns` [n, width] with -1 padding and optionally `count`, as LabelSpace.columns gives
+    them: log_softmax + KLDivLoss) on the raw logits: float32 [n, C] on the device with unit column stride -- a column slice of a wider
+    tensor is read in place.  Differentiable in the logits; forward and backward are one call each on the current stream, without
+    atomics, so the result is the same bits every time.  reduce: "mean" = NLLLoss() for `index` (the sum over the rows with
+    index >= 0 divided by their number, NaN without one) and 'batchmean' (sum / n) for `labels` / `columns`; "sum"; None = the
+    per-row terms [n] of the module docstring."""
+    _one_label_form(labels, index, columns, count)
+    if reduce not in ("mean", "sum", None):
+        raise ValueError("pyhgt_amd: reduce is 'mean', 'sum' or None")
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32:
+        raise TypeError("pyhgt_amd: logits must be a float32 tensor")
+    if labels is not None and (not isinstance(labels, torch.Tensor) or labels.dtype != torch.float32):
+        raise TypeError("pyhgt_amd: labels must be a float32 tensor")
+    if logits.dim() != 2:
+        raise ValueError("pyhgt_amd: logits are [n, C]")
+    if not logits.is_cuda:
+        raise RuntimeError("pyhgt_amd: class_loss runs only on a ROCm GPU tensor; np_class_loss is the definition on the host")
+    n, n_cols = logits.shape
+    if n_cols >= 2 ** 31 - 1024 or n >= 2 ** 31:
+        raise ValueError("pyhgt_amd: too many rows or columns")
+    integers = lambda t, dtype: torch.as_tensor(t, device=logits.device).to(dtype).contiguous()
+    if labels is not None:
+        if labels.device != logits.device or labels.shape != logits.shape:
+            raise ValueError("pyhgt_amd: labels are a tensor shaped like the logits, on their device")
+        labels = _rows_f32(labels.detach(), "labels")
+    if index is not None:
+        index = integers(index, torch.int64).reshape(-1)
+        if index.numel() != n:
+            raise ValueError("pyhgt_amd: one index per row")
+    if columns is not None:
+        columns = integers(columns, torch.int32)
+        if columns.dim() != 2 or columns.size(0) != n or columns.size(1) < 1:
+            raise ValueError("pyhgt_amd: columns are [n, width >= 1]")
+        if count is not None:
+            count = integers(count, torch.int32).reshape(-1)
+            if count.numel() != n:
+                raise ValueError("pyhgt_amd: one count per row")
+    if n == 0:
+        terms, wsum = logits.new_zeros(0) + logits.sum() * 0, logits.new_zeros(0)
+    else:
+        terms, wsum = _ClassLoss.apply(logits, labels, index, columns, count)
+    if reduce is None:
+        return terms
+    if reduce == "sum":
+        return terms.sum()
+    return terms.sum() / (wsum.sum() if index is not None else terms.new_tensor(float(n)))

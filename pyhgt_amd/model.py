@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import _lib
 from .conv import GeneralConv, GraphPlan, _ptr, _stream
+from .metrics import _one_label_form, class_loss
 
 __all__ = ["GNN", "Classifier", "Matcher"]
 
@@ -215,6 +216,14 @@ class Classifier(nn.Module):
         out = torch.empty_like(tx)
         _lib.check(_lib.load().hgt_log_softmax_rows(_ptr(tx), tx.size(0), tx.size(1), _ptr(out), _stream()), "hgt_log_softmax_rows")
         return out.reshape(*x.shape[:-1], self.n_out).squeeze()
+
+    def loss(self, x, labels=None, index=None, columns=None, count=None, reduce="mean"):
+        """The training loss of the scripts on the seed rows x [n, n_hid] without the [n, n_out] log-probabilities: the linear layer
+        (differentiable, honours `deterministic`), then metrics.class_loss on its raw logits -- NLLLoss() with `index`
+        (train_paper_venue.py:86), KLDivLoss('batchmean') with `labels` or `columns` / `count` (train_paper_field.py:87)."""
+        _one_label_form(labels, index, columns, count)
+        tx = _dense_linear(x.reshape(-1, self.n_hid), self.linear.weight, self.linear.bias, deterministic=_det(self))
+        return class_loss(tx, labels=labels, index=index, columns=columns, count=count, reduce=reduce)
 
     def __repr__(self):
         return '{}(n_hid={}, n_out={})'.format(self.__class__.__name__, self.n_hid, self.n_out)

@@ -42,7 +42,7 @@ from .conv import GraphPlan
 from .sampled import _DeviceGraph
 
 __all__ = ["DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "sample_subgraphs_device", "sample_subgraphs_host",
-           "philox4x32_10", "seed_edge_mask", "LabelSpace", "np_label_distribution", "np_label_index", "np_label_counts"]
+           "philox4x32_10", "seed_edge_mask", "LabelSpace", "np_label_distribution", "np_label_index", "np_label_counts", "np_label_columns"]
 
 TIME_NONE = _lib.HGT_SAMPLER_TIME_NONE
 _SUBSET_TAG, _SELECT_TAG = 0x10000, 0x20000
@@ -969,6 +969,23 @@ def np_label_distribution(dgraph, triple, col_of, n_cols, ids, t_min=None, t_max
     return np.where(member, value[:, None], np.float32(0.0)).astype(np.float32)
 
 
+def np_label_columns(dgraph, triple, col_of, ids, t_min=None, t_max=None, width=None):
+    """C as a list: (columns int32 [n, width], count int32 [n]) -- the distinct columns of each row in ascending order, the first
+    `width` of them, -1 behind; count = |C| whether it fitted or not.  width=None: the largest count (at least 1)."""
+    ids = np.asarray(ids).reshape(-1)
+    row, col, _ = _np_qualifying(dgraph.csr[dgraph.triples.index(tuple(triple))], col_of, ids, t_min, t_max)
+    pairs = np.unique(np.stack([row, col], axis=1), axis=0) if row.size else np.zeros((0, 2), np.int64)      # sorted by (row, column)
+    count = np.bincount(pairs[:, 0], minlength=ids.size).astype(np.int32)
+    width = max(int(count.max()) if count.size else 0, 1) if width is None else int(width)
+    if width < 1:
+        raise ValueError("pyhgt_amd: width >= 1")
+    place = np.arange(pairs.shape[0]) - np.concatenate([[0], np.cumsum(count)[:-1]])[pairs[:, 0]]
+    columns = np.full((ids.size, width), -1, np.int32)
+    keep = place < width
+    columns[pairs[keep, 0], place[keep]] = pairs[keep, 1]
+    return columns, count
+
+
 def np_label_index(dgraph, triple, col_of, ids, t_min=None, t_max=None):
     """the class of train_paper_venue.py:159-170 + :134 (the first source in the window wins): int64 [n], -1 without one"""
     ids = np.asarray(ids).reshape(-1)
@@ -1045,6 +1062,33 @@ class LabelSpace:
         out = torch.empty(ids.numel(), dtype=torch.int32, device=self.device)
         self._launch(ids, t_min, t_max, index=out)
         return out.long()
+
+    def columns(self, ids, t_min=None, t_max=None, width=None):
+        """(columns int32 [n, width], count int32 [n]): row r's classes as a list in ascending order, -1 behind them -- the labels of
+        `distribution` without the dense [n, C] matrix, for class_loss(columns=, count=).  count is the true number of classes; a row
+        with more than `width` holds the first `width`.  width=None takes the largest count (at least 1), which costs one more launch
+        and one host read; a given width makes no synchronisation."""
+        if width is not None and int(width) < 1:
+            raise ValueError("pyhgt_amd: width >= 1")
+        if self.device is None:
+            columns, count = np_label_columns(self.g, self.triple, self.col_of, ids, t_min, t_max, width)
+            return torch.from_numpy(columns), torch.from_numpy(count)
+        ids = self._device_ids(ids)
+        count = torch.empty(ids.numel(), dtype=torch.int32, device=self.device)
+        if width is None:
+            self._launch(ids, t_min, t_max, count=count)
+            width = max(int(count.max()) if ids.numel() else 0, 1)
+        columns = torch.empty(ids.numel(), int(width), dtype=torch.int32, device=self.device)
+        has, lo, hi = _window(t_min, t_max)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().hgt_sampler_label_columns(C.byref(self._triple_c), self.n_tgt, self.n_src,
+                                                             ids.data_ptr() if ids.numel() else None, ids.numel(),
+                                                             self.col_of_dev.data_ptr() if self.n_src else None, self.n_cols, has, lo, hi,
+                                                             columns.data_ptr() if ids.numel() else None, int(width),
+                                                             count.data_ptr() if ids.numel() else None,
+                                                             torch.cuda.current_stream(self.device).cuda_stream), "hgt_sampler_label_columns")
+            ids.record_stream(torch.cuda.current_stream(self.device))
+        return columns, count
 
     def counts(self, ids, t_min=None, t_max=None):
         """int64 [n]: the number of distinct classes per row"""
