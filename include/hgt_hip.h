@@ -1071,6 +1071,58 @@ int hgt_sampler_label_columns(const hgt_sampler_triple* triple_host, int32_t n_t
                               int32_t n, const int32_t* col_of, int32_t n_cols, int32_t has_window, int32_t t_min, int32_t t_max,
                               int32_t* columns_out, int32_t width, int32_t* count_out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Voted evaluation (csrc/hgt_task_vote.hip): what the reference's ogbn-mag scripts do with the Classifier's output besides the
+ * loss -- the train / valid / test accuracies of a step, argmax of each split's rows against y (ogbn-mag/train_ogbn_mag.py:165-191),
+ * and the vote of ogbn-mag/eval_ogbn_mag.py:128-191: every test paper owns a vector of n_cols sums, each sampled sub-graph adds the
+ * log-probabilities of the test papers it contains, the answer is the argmax of the sums.  Added under ABI 8 (new symbols only).
+ *
+ *   hgt_class_predict       pred_out[r] (int64) = np.argmax of row r of the scores (float32): the lowest position among the maxima;
+ *                           a NaN beats every number, so the first NaN wins; -inf and +inf are ordinary values.  The prediction is
+ *                           taken on the scores as given.  The scripts take argmax of log-probabilities; on the raw logits that
+ *                           is the same position except where the float32 rounding of (x - m) - ls makes two log-probabilities
+ *                           equal that come from different logits (the script then answers the lower position of the two).
+ *                           Scoring (optional): `label` (int64) and `split` (int32, needs label) are per-row arrays when
+ *                           ids == NULL; with `ids` (int64[n_rows]) they are resident tables of n_table entries read at ids[r] --
+ *                           graph.y and the split id of a batch's papers without per-batch label tensors.  A row is scored in
+ *                           split s iff label >= 0 and 0 <= split < n_splits; without `split` every row with label >= 0 goes to
+ *                           split 0 and n_splits must be 1; with it 1 <= n_splits <= HGT_PREDICT_MAX_SPLITS.
+ *                           counts_out[2 s] = rows scored in split s, counts_out[2 s + 1] = those with pred == label (a label
+ *                           >= n_cols is scored and never correct).  counts_out (int32[2 n_splits]) needs no initialisation: it
+ *                           is zeroed on the stream inside the call and filled with integer atomics, whose sum has no order.  A row
+ *                           whose ids[r] lies outside [0, n_table) is not scored and nothing out of range is read; it, and a row
+ *                           with split < 0, still gets its pred_out.  pred_out or counts_out may be NULL, not both.
+ *                           n_rows == 0: HGT_OK, counts_out zeroed if given.  NULL scores with n_rows > 0, NULL pred_out and NULL
+ *                           counts_out, counts_out or split without label, n_cols < 1 with n_rows > 0, ld < n_cols, a negative
+ *                           size, n_splits out of range: HGT_ERR_INVALID_ARG; n_cols > INT32_MAX - 1024: HGT_ERR_UNSUPPORTED; no launch.
+ *   hgt_vote_add            rows piece_ptr_host[b] .. piece_ptr_host[b + 1] of the logits form piece b (a host array of
+ *                           n_pieces + 1 entries).  For row r with s = slot_of[ids[r]]: if ids[r] is in [0, n_nodes) and
+ *                           0 <= s < n_slots, votes[s * ld_votes + j] += logp_j for j < n_cols and count[s] += 1, logp the float32
+ *                           log-softmax of hgt_class_loss: m = max x, ls = log(sum exp(x - m)), (x_j - m) - ls.  Any other row is
+ *                           skipped, nothing out of range is read or written, and the columns n_cols .. ld_votes of the table are
+ *                           left untouched.  One launch per piece, in piece order on the stream; an empty piece gets none.  Within a
+ *                           piece the ids that map to a slot are distinct BY CONTRACT (the sampler returns each node of a type
+ *                           once): no two threads of a launch touch the same slot, so there are no atomics.  Different pieces may
+ *                           carry the same node; stream order fixes the order of the additions into its slot, so the bits of
+ *                           `votes` depend only on the sequence of calls and their inputs.  NaN and infinite logits propagate into
+ *                           the slot, as they do in the script.  slot_of: int32[n_nodes], count: int32[n_slots].
+ *                           No rows: HGT_OK without a launch.  A NULL array with work to do, n_pieces < 0, piece_ptr_host not
+ *                           non-decreasing from a non-negative start, ld or ld_votes < n_cols, n_cols < 1 with rows, a negative
+ *                           size: HGT_ERR_INVALID_ARG; n_cols > INT32_MAX - 1024: HGT_ERR_UNSUPPORTED; no launch.
+ *                           Both: row r is at base + r * ld, ld >= n_cols, any alignment (16-byte loads where the row's base
+ *                           allows).  Rows of at most HGT_CLASS_LOSS_WAVE_COLS columns take a wavefront each, longer ones a
+ *                           workgroup each; a position always belongs to the same thread, so a row's result does not depend on its
+ *                           alignment, the other rows, n_rows or the launch geometry.  No float atomics, no allocation, no
+ *                           synchronisation.  Every array is a device array unless its name ends in _host.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_PREDICT_MAX_SPLITS 8
+int hgt_class_predict(const float* scores, int64_t ld, int32_t n_rows, int32_t n_cols, const int64_t* ids, int64_t n_table,
+                      const int64_t* label, const int32_t* split, int32_t n_splits, int64_t* pred_out, int32_t* counts_out,
+                      void* stream);
+int hgt_vote_add(const float* logits, int64_t ld, int32_t n_cols, const int64_t* ids, const int32_t* piece_ptr_host, int32_t n_pieces,
+                 const int32_t* slot_of, int64_t n_nodes, float* votes, int64_t ld_votes, int32_t* count, int32_t n_slots,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,7 @@ class HgtSamplerMask(C.Structure):
 
 RANK_LIST_CAP = 1024     # HGT_RANK_LIST_CAP: positives a pass of hgt_rank_metrics holds
 CLASS_LOSS_WAVE_COLS = 256   # HGT_CLASS_LOSS_WAVE_COLS: the longest row of hgt_class_loss that takes a wavefront
+PREDICT_MAX_SPLITS = 8     # HGT_PREDICT_MAX_SPLITS: the most splits hgt_class_predict counts in one call
 ABI_VERSION = 8          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
 
 _i32, _i64, _u64, _vp = C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
@@ -258,6 +259,10 @@ SIGNATURES = {
     "hgt_class_loss": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "hgt_class_loss_bwd": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hgt_sampler_label_columns": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    # voted evaluation (csrc/hgt_task_vote.hip): (scores, ld, n_rows, n_cols, ids, n_table, label, split, n_splits, pred_out, counts_out,
+    # stream) and (logits, ld, n_cols, ids, piece_ptr_host, n_pieces, slot_of, n_nodes, votes, ld_votes, count, n_slots, stream)
+    "hgt_class_predict": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "hgt_vote_add": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp]),
 }
 
 _lib = None

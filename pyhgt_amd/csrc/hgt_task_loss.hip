@@ -25,12 +25,9 @@
 #include <math.h>
 
 #include "hgt_common.h"
+#include "hgt_row_common.h"
 
 namespace {
-
-constexpr int CL_BLOCK = 256;
-constexpr int CL_WAVES = CL_BLOCK / 64;
-static_assert(HGT_CLASS_LOSS_WAVE_COLS == 4 * 64, "a wavefront row is one quad per lane");
 
 struct ClassArgs {
     const float* x;
@@ -54,42 +51,6 @@ struct Scratch {
     double d[2][CL_WAVES];
     int i[2][CL_WAVES];
 };
-
-// positions j .. j + 3 of a row (j a multiple of 4): one 16-byte load where the base is aligned and the four lie inside
-__device__ __forceinline__ void load4(const float* p, int j, int C, bool vec, float fill, float (&v)[4]) {
-    if (vec && j + 3 < C) {
-        const float4 t = *reinterpret_cast<const float4*>(p + j);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = j + e < C ? p[j + e] : fill;
-    }
-}
-
-// T threads (a wavefront or the workgroup) join their values: a shuffle tree, then the wavefronts in order; every thread gets the result
-template <int T>
-__device__ __forceinline__ float group_max(float v, Scratch& S) {
-    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    if (T == 64) return v;
-    if ((threadIdx.x & 63) == 0) S.f[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = S.f[0];
-    for (int q = 1; q < CL_WAVES; ++q) v = fmaxf(v, S.f[q]);
-    __syncthreads();
-    return v;
-}
-
-template <int T>
-__device__ __forceinline__ float group_sum(float v, Scratch& S) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    if (T == 64) return v;
-    if ((threadIdx.x & 63) == 0) S.f[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = S.f[0];
-    for (int q = 1; q < CL_WAVES; ++q) v += S.f[q];
-    __syncthreads();
-    return v;
-}
 
 template <int T>
 __device__ __forceinline__ int group_count(int v, Scratch& S) {
@@ -134,39 +95,8 @@ __global__ void __launch_bounds__(CL_BLOCK) k_class_loss(ClassArgs A) {
     const bool vec = ((uintptr_t)x & 15) == 0;
 
     // ---- m and ls; a wavefront row stays in registers
-    float own[4];
-    if (T == 64) load4(x, 4 * k, C, vec, -INFINITY, own);
-    float m = -INFINITY;
-    if (T == 64) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m = fmaxf(m, own[e]);
-    } else {
-        for (int j = 4 * k; j < C; j += 4 * T) {
-            float v[4];
-            load4(x, j, C, vec, -INFINITY, v);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) m = fmaxf(m, v[e]);
-        }
-    }
-    m = group_max<T>(m, S);
-    float sum = 0.0f;                                                             // (fmaxf drops a NaN logit, exp(NaN - m) keeps it)
-    if (T == 64) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (4 * k + e < C) sum += expf(own[e] - m);
-        }
-    } else {
-        for (int j = 4 * k; j < C; j += 4 * T) {
-            float v[4];
-            load4(x, j, C, vec, -INFINITY, v);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (j + e < C) sum += expf(v[e] - m);
-            }
-        }
-    }
-    sum = group_sum<T>(sum, S);
-    const float ls = logf(sum);
+    float own[4], m, ls;
+    row_lse<T>(x, C, vec, k, own, S, m, ls);
 
     // ---- the label-weighted terms, fp64
     double acc = 0.0, w = 0.0;

@@ -41,13 +41,27 @@ and a row's term and label weight W come from one of three label forms:
                  an entry >= C: NaN;   with `count` (the true number of classes of a row) count > width: NaN
 
     d term / d x_j = W softmax(x)_j - l_j;   a NaN term has a NaN gradient row
+
+Voted evaluation (`class_predict`, `VoteTable`, csrc/hgt_task_vote.hip; the rules are `np_class_predict` and `np_vote_add`).  The
+ogbn-mag scripts report three accuracies per step, argmax of each split's rows against y (ogbn-mag/train_ogbn_mag.py:165-191), and
+evaluate by vote (ogbn-mag/eval_ogbn_mag.py:128-191): every test paper owns C sums, each sampled sub-graph adds the log-probabilities
+of the test papers it contains through `res.tolist()` and a dict, and the answer is the argmax of the sums.
+
+    pred_r = np.argmax(scores_r): the lowest position among the maxima; a NaN beats every number, the first NaN wins
+    row r is scored in split s iff label >= 0 and 0 <= split < n_splits (no split: s = 0); counts[s] = (scored, pred == label)
+    labels / split are per-row arrays, or with `ids` tables read at ids[r]; an id outside the table is not scored
+    vote: for every row whose id is in [0, n_nodes) and has a slot s: votes[s] += log_softmax(logits_r), count[s] += 1
+
+The prediction is taken on the scores as given.  The scripts take argmax of log-probabilities; on raw logits that is the same
+position except where the float32 rounding of (x - m) - ls makes the log-probabilities of two different logits equal.
 """
 import numpy as np
 import torch
 
 from . import _lib
 
-__all__ = ["Segments", "rank_metrics", "pair_rank_loss", "class_loss", "np_rank_metrics", "np_pair_rank_loss", "np_class_loss", "np_ranks"]
+__all__ = ["Segments", "rank_metrics", "pair_rank_loss", "class_loss", "np_rank_metrics", "np_pair_rank_loss", "np_class_loss", "np_ranks",
+           "class_predict", "VoteTable", "np_class_predict", "np_vote_add"]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rule
@@ -210,6 +224,94 @@ def np_class_loss(logits, labels=None, index=None, columns=None, count=None, ret
             elif W != 0 or labels is not None:
                 grad[r] = W * p - l
     return (terms, grad) if return_grad else terms
+
+
+def np_class_predict(scores, labels=None, split=None, n_splits=1, ids=None):
+    """pred (int64 [n]) = np.argmax of every row of scores [n, C >= 1]; with `labels` also counts (int32 [n_splits, 2]): per split
+    the rows scored and those with pred == label, by the rule of this module's docstring.  labels (and split) hold one entry per row,
+    or with `ids` (one id per row) one entry per node of a table, read at the id."""
+    scores = np.asarray(scores)
+    if scores.ndim != 2 or (scores.shape[0] and scores.shape[1] < 1):
+        raise ValueError("pyhgt_amd: scores are [n, C >= 1]")
+    n = scores.shape[0]
+    pred = np.argmax(scores, axis=1).astype(np.int64) if n else np.zeros(0, np.int64)
+    if labels is None:
+        if split is not None:
+            raise ValueError("pyhgt_amd: split goes with labels")
+        return pred
+    n_splits = _check_splits(split, n_splits)
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    split = np.zeros(labels.size, np.int64) if split is None else np.asarray(split, dtype=np.int64).reshape(-1)
+    if split.size != labels.size:
+        raise ValueError("pyhgt_amd: one split id per label")
+    if ids is None:
+        if labels.size != n:
+            raise ValueError("pyhgt_amd: one label per row, or a table with ids")
+        y, s = labels, split
+    else:
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size != n:
+            raise ValueError("pyhgt_amd: one id per row")
+        inside = (ids >= 0) & (ids < labels.size)
+        at = np.where(inside, ids, 0)
+        y = np.where(inside, labels[at], -1) if labels.size else np.full(n, -1, np.int64)
+        s = np.where(inside, split[at], -1) if labels.size else np.full(n, -1, np.int64)
+    scored = (y >= 0) & (s >= 0) & (s < n_splits)
+    counts = np.zeros((n_splits, 2), np.int32)
+    np.add.at(counts[:, 0], s[scored], 1)
+    np.add.at(counts[:, 1], s[scored & (pred == y)], 1)
+    return pred, counts
+
+
+def _check_splits(split, n_splits):
+    if int(n_splits) != n_splits or not 1 <= n_splits <= (_lib.PREDICT_MAX_SPLITS if split is not None else 1):
+        raise ValueError("pyhgt_amd: 1 <= n_splits <= %d with split, 1 without" % _lib.PREDICT_MAX_SPLITS)
+    return int(n_splits)
+
+
+def _piece_ptr(piece_sizes, n):
+    """host offsets (int32 [B + 1]) of the pieces of n rows; None: one piece"""
+    sizes = np.asarray([n] if piece_sizes is None else piece_sizes, dtype=np.int64).reshape(-1)
+    if sizes.size and sizes.min() < 0:
+        raise ValueError("pyhgt_amd: a negative piece size")
+    if int(sizes.sum()) != n:
+        raise ValueError("pyhgt_amd: the piece sizes add up to %d, there are %d rows" % (int(sizes.sum()), n))
+    if n >= 2 ** 31:
+        raise ValueError("pyhgt_amd: too many rows")
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
+def np_vote_add(votes, count, slot_of, logits, ids, piece_sizes=None):
+    """The vote of eval_ogbn_mag.py:148-150 / 177-179 in float64, in place on a numpy table: votes float64 [n_slots, C], count an
+    integer array [n_slots], slot_of [n_nodes] (-1 = no slot).  For every row of logits [n, C] whose id lies in [0, n_nodes) and has
+    a slot s in [0, n_slots): votes[s] += log_softmax(row), count[s] += 1; the pieces (consecutive runs of `piece_sizes` rows, None =
+    one) are added in order.  ValueError if a piece holds a slotted node twice: the device path has one writer per slot and launch."""
+    if not isinstance(votes, np.ndarray) or votes.dtype != np.float64 or votes.ndim != 2:
+        raise TypeError("pyhgt_amd: votes is a float64 numpy array [n_slots, C]")
+    if not isinstance(count, np.ndarray) or count.dtype.kind != "i" or count.shape != votes.shape[:1]:
+        raise TypeError("pyhgt_amd: count is an integer numpy array [n_slots]")
+    x = np.asarray(logits).astype(np.float64)
+    if x.ndim != 2 or x.shape[1] != votes.shape[1]:
+        raise ValueError("pyhgt_amd: logits are [n, C] with the table's C")
+    slot_of = np.asarray(slot_of, dtype=np.int64).reshape(-1)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if ids.size != x.shape[0]:
+        raise ValueError("pyhgt_amd: one id per row")
+    ptr = _piece_ptr(piece_sizes, x.shape[0])
+    inside = (ids >= 0) & (ids < slot_of.size)
+    slot = np.where(inside, slot_of[np.where(inside, ids, 0)], -1) if slot_of.size else np.full(ids.size, -1, np.int64)
+    has = (slot >= 0) & (slot < votes.shape[0])
+    for b in range(ptr.size - 1):
+        rows = np.arange(ptr[b], ptr[b + 1])[has[ptr[b]:ptr[b + 1]]]
+        if np.unique(slot[rows]).size != rows.size:
+            raise ValueError("pyhgt_amd: piece %d holds a node with a slot more than once" % b)
+    with np.errstate(all="ignore"):
+        m = x.max(axis=1, keepdims=True) if x.size else x
+        logp = x - m - np.log(np.exp(x - m).sum(axis=1, keepdims=True)) if x.size else x
+    for b in range(ptr.size - 1):
+        rows = np.arange(ptr[b], ptr[b + 1])[has[ptr[b]:ptr[b + 1]]]
+        votes[slot[rows]] += logp[rows]
+        count[slot[rows]] += 1
 
 
 # ---------------------------------------------------------------------------------------------------------------- the device calls
@@ -438,3 +540,144 @@ def class_loss(logits, labels=None, index=None, columns=None, count=None, reduce
     if reduce == "sum":
         return terms.sum()
     return terms.sum() / (wsum.sum() if index is not None else terms.new_tensor(float(n)))
+
+
+def _ids_i64(t, n, device, what):
+    t = torch.as_tensor(t, device=device).reshape(-1)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError("pyhgt_amd: %s must be integers, got %s" % (what, t.dtype))
+    if n is not None and t.numel() != n:
+        raise ValueError("pyhgt_amd: %s has %d entries, expected %d" % (what, t.numel(), n))
+    return t.to(torch.int64).contiguous()
+
+
+def class_predict(scores, labels=None, split=None, n_splits=1, ids=None):
+    """pred = argmax of every row of scores (float32 [n, C >= 1] on the device with unit column stride; a column slice of a wider tensor
+    is read in place), as np.argmax takes it: int64 [n].  With `labels` (integers) also counts, int32 [n_splits, 2] on the device: per
+    split the rows scored and the rows with pred == label -- the three accuracies of a step of train_ogbn_mag.py:165-191 are
+    counts[:, 1] / counts[:, 0].  A row is scored iff label >= 0 and 0 <= split < n_splits (`split`: int32 ids; None: everything in
+    split 0).  labels / split hold one entry per row; with `ids` (int64 [n]) they are resident tables -- graph.y and the split id of
+    every node -- read at ids[r], and an id outside the table is not scored.  One call of hgt_class_predict on the current stream, no
+    synchronisation, no [n, C] temporary; the definition is np_class_predict."""
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32:
+        raise TypeError("pyhgt_amd: scores must be a float32 tensor")
+    if scores.dim() != 2 or (scores.size(0) and scores.size(1) < 1):
+        raise ValueError("pyhgt_amd: scores are [n, C >= 1]")
+    if split is not None and labels is None:
+        raise ValueError("pyhgt_amd: split goes with labels")
+    if ids is not None and labels is None:
+        raise ValueError("pyhgt_amd: ids go with labels")
+    n_splits = _check_splits(split, n_splits)
+    for what, t in (("labels", labels), ("split", split), ("ids", ids)):
+        if isinstance(t, torch.Tensor) and (t.dtype.is_floating_point or t.dtype == torch.bool):
+            raise TypeError("pyhgt_amd: %s must be integers, got %s" % (what, t.dtype))
+    if not scores.is_cuda:
+        raise RuntimeError("pyhgt_amd: class_predict runs only on a ROCm GPU tensor; np_class_predict is the definition on the host")
+    n, n_cols = scores.shape
+    if n_cols >= 2 ** 31 - 1024 or n >= 2 ** 31:
+        raise ValueError("pyhgt_amd: too many rows or columns")
+    x = _rows_f32(scores.detach(), "scores")
+    dev, n_table, counts = x.device, 0, None
+    if labels is not None:
+        if ids is not None:
+            ids = _ids_i64(ids, n, dev, "ids")
+        labels = _ids_i64(labels, n if ids is None else None, dev, "labels")
+        n_table = labels.numel()
+        if split is not None:
+            split = _ids_i64(split, n_table, dev, "split").to(torch.int32)
+        counts = (torch.zeros if n == 0 or n_table == 0 else torch.empty)(n_splits, 2, dtype=torch.int32, device=dev)
+    pred = torch.empty(n, dtype=torch.int64, device=dev)
+    if n:
+        tables = (_ptr(ids), n_table, _ptr(labels), _ptr(split), n_splits) if n_table else (None, 0, None, None, 1)      # (no label: no scoring)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().hgt_class_predict(x.data_ptr(), max(int(x.stride(0)), n_cols), n, n_cols, *tables, pred.data_ptr(),
+                                                     counts.data_ptr() if n_table else None, _stream(x)), "hgt_class_predict")
+    return pred if labels is None else (pred, counts)
+
+
+class VoteTable:
+    """The sums of a voted evaluation (eval_ogbn_mag.py:110, 128-191) on the device.  `nodes`: the int64 ids that own a slot, e.g. the
+    test papers; slot i belongs to nodes[i]; None: every one of the n_nodes nodes.  Duplicate entries raise ValueError.
+    .votes float32 [n_slots, n_classes] (zeros), .count int32 [n_slots], .slot_of int32 [n_nodes] (-1 = no slot), .nodes int64.
+    `.votes` may be replaced by a column slice (unit column stride) of a wider float32 tensor: its other columns are left alone."""
+
+    def __init__(self, n_nodes, n_classes, nodes=None, device=None):
+        n_nodes, n_classes = int(n_nodes), int(n_classes)
+        if n_nodes < 0 or n_classes < 1 or n_classes >= 2 ** 31 - 1024:
+            raise ValueError("pyhgt_amd: n_nodes >= 0 and 1 <= n_classes < 2^31 - 1024")
+        if nodes is None:
+            host = np.arange(n_nodes, dtype=np.int64)
+        else:
+            host = (nodes.detach().cpu().numpy() if isinstance(nodes, torch.Tensor) else np.asarray(nodes)).reshape(-1)
+            if host.dtype.kind not in "iu":
+                raise TypeError("pyhgt_amd: nodes are integer ids")
+            host = host.astype(np.int64)
+            if host.size and (host.min() < 0 or host.max() >= n_nodes):
+                raise ValueError("pyhgt_amd: nodes outside [0, %d)" % n_nodes)
+            if np.unique(host).size != host.size:
+                raise ValueError("pyhgt_amd: a node is listed twice")
+        if host.size >= 2 ** 31:
+            raise ValueError("pyhgt_amd: too many slots")
+        slot_of = np.full(n_nodes, -1, np.int32)
+        slot_of[host] = np.arange(host.size, dtype=np.int32)
+        self.n_nodes, self.n_classes, self.n_slots = n_nodes, n_classes, int(host.size)
+        self.device = torch.device("cpu" if device is None else device)
+        self.nodes = torch.from_numpy(host).to(self.device)
+        self.slot_of = torch.from_numpy(slot_of).to(self.device)
+        self.votes = torch.zeros(self.n_slots, n_classes, dtype=torch.float32, device=self.device)
+        self.count = torch.zeros(self.n_slots, dtype=torch.int32, device=self.device)
+
+    def reset(self):
+        self.votes.zero_()
+        self.count.zero_()
+
+    def add(self, logits, ids, piece_sizes=None, check=False):
+        """votes[slot_of[ids[r]]] += log_softmax(logits[r]), count += 1, for every row whose id has a slot: raw logits float32 [n, C] on
+        the table's device, ids int64 [n].  piece_sizes: a host sequence of row counts, e.g. the papers of each piece of a stack (None:
+        one piece); one launch per piece, in order.  Within a piece the slotted ids must be distinct (a sampled sub-graph holds a node
+        once); check=True verifies that with one host read and raises ValueError.  No atomics: the same calls give the same bits."""
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32:
+            raise TypeError("pyhgt_amd: logits must be a float32 tensor")
+        if logits.dim() != 2 or logits.size(1) != self.n_classes:
+            raise ValueError("pyhgt_amd: logits are [n, %d]" % self.n_classes)
+        if not logits.is_cuda or not self.votes.is_cuda:
+            raise RuntimeError("pyhgt_amd: VoteTable.add runs only on a ROCm GPU tensor and table; np_vote_add is the definition on the host")
+        if logits.device != self.votes.device:
+            raise ValueError("pyhgt_amd: the logits are on %s, the table on %s" % (logits.device, self.votes.device))
+        n = logits.size(0)
+        ids = _ids_i64(ids, n, logits.device, "ids")
+        ptr = _piece_ptr(piece_sizes, n)
+        if n == 0:
+            return self
+        if check:
+            inside = (ids >= 0) & (ids < self.n_nodes)
+            slot = torch.where(inside, self.slot_of[torch.where(inside, ids, 0)].long(), -1) if self.n_nodes else torch.full_like(ids, -1)
+            piece = torch.repeat_interleave(torch.arange(ptr.size - 1, device=ids.device), torch.from_numpy(np.diff(ptr)).to(ids.device),
+                                            output_size=n)
+            key = torch.where(slot >= 0, piece * max(self.n_slots, 1) + slot, -1 - torch.arange(n, device=ids.device)).sort().values
+            if bool((key[1:] == key[:-1]).any()):
+                raise ValueError("pyhgt_amd: a piece holds a node with a slot more than once")
+        x = _rows_f32(logits.detach(), "logits")
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().hgt_vote_add(x.data_ptr(), max(int(x.stride(0)), self.n_classes), self.n_classes, ids.data_ptr(),
+                                                ptr.ctypes.data, int(ptr.size - 1), _ptr(self.slot_of), self.n_nodes, _ptr(self.votes),
+                                                max(int(self.votes.stride(0)), self.n_classes), _ptr(self.count), self.n_slots, _stream(x)),
+                       "hgt_vote_add")
+        return self
+
+    def predict(self, labels=None):
+        """pred int64 [n_slots]: the argmax of every slot's sums, -1 for a slot that was never voted on.  With `labels` (one per slot,
+        < 0 = not scored) also a device int32 pair (n_voted, n_correct) over the voted slots.  One hgt_class_predict launch on
+        .votes; the slots of zero count are left out through its `split`."""
+        if not self.votes.is_cuda:
+            raise RuntimeError("pyhgt_amd: VoteTable.predict runs only on a ROCm GPU table; np_class_predict is the definition on the host")
+        voted = self.count > 0
+        if labels is None:
+            return torch.where(voted, class_predict(self.votes), -1)
+        pred, counts = class_predict(self.votes, labels=labels, split=voted.to(torch.int32) - 1, n_splits=1)
+        return torch.where(voted, pred, -1), counts[0]
+
+    def accuracy(self, labels):
+        """the share of the voted (and labelled) slots whose prediction equals its label: a Python float after one host read"""
+        n_voted, n_correct = self.predict(labels)[1].tolist()
+        return n_correct / n_voted if n_voted else float("nan")

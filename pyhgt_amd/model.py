@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from . import _lib
 from .conv import GeneralConv, GraphPlan, _ptr, _stream
-from .metrics import _one_label_form, class_loss
+from .metrics import _one_label_form, class_loss, class_predict
 
 __all__ = ["GNN", "Classifier", "Matcher"]
 
@@ -224,6 +224,23 @@ class Classifier(nn.Module):
         _one_label_form(labels, index, columns, count)
         tx = _dense_linear(x.reshape(-1, self.n_hid), self.linear.weight, self.linear.bias, deterministic=_det(self))
         return class_loss(tx, labels=labels, index=index, columns=columns, count=count, reduce=reduce)
+
+    def logits(self, x, what="logits", rule="torch.nn.functional.linear"):
+        """the raw logits [n, n_out] of the linear layer on rows x [n, n_hid], without a graph: what predict and vote work on"""
+        if not x.is_cuda:
+            raise RuntimeError("pyhgt_amd: Classifier.%s runs only on a ROCm GPU tensor; %s is the definition on the host" % (what, rule))
+        with torch.no_grad():
+            return _dense_linear(x.reshape(-1, self.n_hid), self.linear.weight, self.linear.bias, deterministic=_det(self))
+
+    def predict(self, x, **kw):
+        """The predictions of the rows x [n, n_hid] and, with labels, the per-split accuracy counts of train_ogbn_mag.py:165-191: the
+        linear layer, then metrics.class_predict(logits, **kw) on its raw logits -- no [n, n_out] log-probabilities.  Not differentiable."""
+        return class_predict(self.logits(x, "predict", "np_class_predict"), **kw)
+
+    def vote(self, x, table, ids, piece_sizes=None):
+        """One sampled sub-graph's (or one stack's) share of a voted evaluation (eval_ogbn_mag.py:148-150): the linear layer, then
+        table.add(logits, ids, piece_sizes) -- the log-softmax is formed inside the add, no [n, n_out] log-probabilities."""
+        return table.add(self.logits(x, "vote", "np_vote_add"), ids, piece_sizes)
 
     def __repr__(self):
         return '{}(n_hid={}, n_out={})'.format(self.__class__.__name__, self.n_hid, self.n_out)
