@@ -277,6 +277,28 @@ int hgt_edge_logits(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t 
 int hgt_edge_logits_mfma(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations,
                          int32_t n_heads, int32_t dk_pad, const float* Q, const float* K, const float* rte_k,
                          const float* att_t, const void* att_frag, int32_t frag_f16, float* logits, void* stream);
+/* The same logits with the relation transform on the SOURCE operand, per edge, on the matrix cores:
+ *   s_e,h = < q_i,h , A'[r,h]^T k_j,h >,  32 edges of a work item x one head = one v_mfma_f32_32x32x16_f16 product (two k-steps, three
+ *   fp16 hi / lo terms), the edge on the lane; no target segments (csrc/hgt_edge_logits_kside.hip).  The form for graphs with short
+ *   (target, relation) segments at d_k <= 32.
+ * att_kside = hgt_relation_kside_pack(att_t): hgt_relation_kside_bytes bytes (0: the layout is not covered), the A operands of every
+ *   (relation, head) block as fp16 hi / lo of att_t * 2^s with one power-of-two scale per block, and the blocks' exponents behind them.
+ *   The K rows are scaled per (row, head) and the Q rows per (row, head) by exact powers of two inside the kernel, so the result is
+ *   finite whenever the fp32 logit is, whatever the magnitudes; the same image and arithmetic serve both split precisions
+ *   (frag_f16 is accepted and ignored; att_t is not read).
+ * Covered: dk_pad == 32, n_heads (layout heads) 2, 4 or 8 (rows of at most 256 padded columns), rte_k == NULL, and
+ *   n_nodes * n_heads * dk_pad * 4 < 2^32 (every Q / K row below 4 GiB from its base).  HGT_ERR_UNSUPPORTED otherwise: the caller
+ *   takes hgt_edge_logits / hgt_edge_logits_mfma.  Edges of the unclaimed bucket get logit 0.  No atomics: bit-reproducible. */
+int hgt_relation_kside_bytes(int32_t n_relations, int32_t n_heads, int32_t dk_pad, uint64_t* out_host);
+int hgt_relation_kside_pack(const float* att_t, int32_t n_relations, int32_t n_heads, int32_t dk_pad, void* att_kside, void* stream);
+int hgt_edge_logits_kside(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations,
+                          int32_t n_heads, int32_t dk_pad, const float* Q, const float* K, const float* rte_k,
+                          const float* att_t, const void* att_kside, int32_t frag_f16, float* logits, void* stream);
+/* Host only (no GPU): the index maps of that image and of the kernel's lanes (csrc/hgt_kside_map.h), for tests.
+ *   image_map[p][4] = {block, term (0 hi, 1 lo), output, k} of f16 element p, p < n_blocks * 2048 (block = relation * n_heads + head);
+ *   b_col[k-step 2][lane 64][8] = the column of the head a lane supplies as element j of the B operand;
+ *   c_out[lane 64][16] = the output a lane receives in accumulator register reg.  Any of the three may be NULL. */
+int hgt_kside_image_map(int32_t n_blocks, int32_t* image_map, int32_t* b_col, int32_t* c_out);
 /* ABI 6: the work items [item_begin, item_end) only = the items of a range of destination tiles (hgt_plan_tile_items_offset): the
  * logits of ONE target block of the multi-GPU path.  att_frag may be NULL (vector-ALU kernel). */
 int hgt_edge_logits_range(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations,
@@ -686,6 +708,10 @@ typedef struct hgt_conv_args {
 #define HGT_FLAG_VALU_AGGREGATE  2   /* relation transforms of the aggregation on the vector ALU (round-1 kernel) instead of MFMA */
 #define HGT_FLAG_MFMA_LOGITS     4   /* hgt_edge_logits_mfma for every layout it covers (default: d_k >= 64 only) */
 #define HGT_FLAG_VALU_LOGITS     8   /* never hgt_edge_logits_mfma */
+#define HGT_FLAG_KSIDE_LOGITS 65536  /* hgt_edge_logits_kside wherever it is covered (see there), whatever the size of the work items (default: whole-layer,
+                                      * plain staged and target-block (stage 5) calls with a split precision whose work items have at least 64 edges, and neither of the
+                                      * two flags above) */
+#define HGT_FLAG_NO_KSIDE_LOGITS 131072 /* never hgt_edge_logits_kside */
 #define HGT_FLAG_ITEM_AGGREGATE 16   /* hgt_edge_aggregate_items wherever it applies.  It applies -- and is the default -- when ALL of these hold: a split
                                       * precision; fewer than 65536 NODES (n_nodes: the workspace only then holds its scratch) and fewer than 65536
                                       * targets (n_q_rows); a scratch of at most 1 GiB (hgt_edge_aggregate_items_bytes <= 1 << 30: ~986 k edges at

@@ -16,10 +16,14 @@
                                           // 330 vs 356 at 8k ... 1409 vs 1501 at 48k, d = 512)
 #endif
 
+// hgt_edge_logits_kside.hip: that kernel on the work items [item_lo, item_hi) (a target block of the multi-GPU path), or all of them (0, -1)
+int hgt_edge_logits_kside_items(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad, const float* Q,
+                                const float* K, const float* rte_k, const void* att_kside, float* logits, int item_lo, int item_hi, void* stream);
+
 namespace {
 
 struct ConvWorkspace {
-    uint64_t off_q, off_k, off_v, off_logits, off_agg, off_trans, off_att_t, off_msg_p, off_msg_f, off_att_f, off_hub;
+    uint64_t off_q, off_k, off_v, off_logits, off_agg, off_trans, off_att_t, off_msg_p, off_msg_f, off_att_f, off_att_k, off_hub;
     uint64_t off_rte_lin, off_rte_k, off_rte_v, off_rte_rows, off_rte_off, off_ws_qkv, off_ws_a, off_ws_rte, off_off2, off_pending, off_state, off_zitems, zitems_bytes, total;
     // the same layout without the item-aggregation scratch: it is the last region, every other offset stays
     void drop_item_scratch() { zitems_bytes = 0; total = off_zitems; }
@@ -44,6 +48,9 @@ static ConvWorkspace conv_workspace(int64_t N, int64_t NQ, int64_t E, int in_dim
     hgt_relation_frag_bytes(R, H, lay.dk_pad, &fb);
     w.off_msg_f = take(fb);
     w.off_att_f = take(fb);
+    uint64_t kb = 0;
+    hgt_relation_kside_bytes(R, H, lay.dk_pad, &kb);      // (0: a layout hgt_edge_logits_kside does not cover)
+    w.off_att_k = take(kb);
     uint64_t hb = 0;
     hgt_hub_workspace_bytes_ex(E, H, lay.dk_pad, R, det_hubs ? 1 : 0, &hb);
     w.off_hub = take(hb);
@@ -89,7 +96,7 @@ static ConvWorkspace conv_workspace(int64_t N, int64_t NQ, int64_t E, int in_dim
 }
 
 struct PreparedLayout {
-    uint64_t off_att_t, off_msg_p, off_msg_f, off_att_f, off_ws_qkv, off_ws_upd, off_rte_k, off_rte_v, total;
+    uint64_t off_att_t, off_msg_p, off_msg_f, off_att_f, off_att_k, off_ws_qkv, off_ws_upd, off_rte_k, off_rte_v, total;
 };
 
 static PreparedLayout prepared_layout(int in_dim, int out_dim, int T, int R, int /*n_heads*/, int use_rte, const hgt_layout& lay) {
@@ -102,6 +109,8 @@ static PreparedLayout prepared_layout(int in_dim, int out_dim, int T, int R, int
     hgt_relation_frag_bytes(R, H, lay.dk_pad, &b);
     p.off_msg_f = take(b);
     p.off_att_f = take(b);
+    hgt_relation_kside_bytes(R, H, lay.dk_pad, &b);
+    p.off_att_k = take(b);
     hgt_split_weights_bytes(T, in_dim, 3 * lay.d_pad, &b);
     p.off_ws_qkv = take(b);
     hgt_split_weights_bytes(T, lay.d_pad, out_dim, &b);
@@ -120,11 +129,13 @@ __global__ void k_rte_row_lists(int T, int32_t* __restrict__ rows, int32_t* __re
 }
 
 // The kernels of one call, decided once (Conv::route).  AGG_FUSED and AGG_ITEMS_UPDATE run the update themselves.
-enum LogitsForm { LOGITS_VALU, LOGITS_MFMA, LOGITS_SLICE, LOGITS_RANGE };
+enum LogitsForm { LOGITS_VALU, LOGITS_MFMA, LOGITS_SLICE, LOGITS_RANGE, LOGITS_KSIDE };
 enum AggForm { AGG_SINGLE_PASS, AGG_FUSED, AGG_ITEMS_UPDATE, AGG_ITEMS, AGG_SLICE, AGG_SUBTILE };
 enum UpdateForm { UPDATE_IN_AGGREGATION, UPDATE_LINEAR_FUSED, UPDATE_LINEAR_NODE, UPDATE_DENSE };
 struct ConvRoute {
     LogitsForm logits;
+    bool kside_range;        // (the range form of stage 5 takes hgt_edge_logits_kside where the one-call layer of the same graph does:
+                             //  its blocks are bit-identical to that layer)
     bool mfma_logits;        // (the range form of stage 5 takes the fragment image of att_t when set)
     // aggregation forms in the order they are tried: a kernel that answers HGT_ERR_UNSUPPORTED (a head-group layout it is not
     // instantiated for -- the kernels decide that themselves) hands over to the next.  The last one is the slice or sub-tile form.
@@ -143,13 +154,13 @@ struct Conv {
     hgt_plan_rows pr;
     int64_t N, E, NQ;
     int T, R, H, din, dout, dp, dkp, stage, fmode, sl_lo, sl_hi, sl_more;
-    bool f16, split, dense, det_hubs, no_unknown_rows, have_frags, mfma_agg;
+    bool f16, split, dense, det_hubs, no_unknown_rows, have_frags, have_kside, mfma_agg;
     decltype(&hgt_split_weights) split_weights;
     bool fresh;              // this call derives the weight images (written where they live, below)
     bool wa_prepared;        // the image of W_a lives in the prepared buffer (see wa_written)
     char* wb;
     float *Q, *K, *V, *logits, *agg, *trans, *att_t, *msg_p, *rte_k, *rte_v;
-    void *msg_f_buf, *att_f_buf, *msg_f, *hub_ws, *ws_qkv, *ws_upd, *ws_a;
+    void *msg_f_buf, *att_f_buf, *att_k_buf, *msg_f, *hub_ws, *ws_qkv, *ws_upd, *ws_a;
     ConvRoute r;
 
     // Every check of the arguments, in the order that decides which code a call with several faults returns; nothing is
@@ -190,6 +201,9 @@ struct Conv {
         uint64_t frag_bytes = 0;
         hgt_relation_frag_bytes(R, H, dkp, &frag_bytes);
         have_frags = split && frag_bytes > 0;
+        uint64_t kside_bytes = 0;
+        hgt_relation_kside_bytes(R, H, dkp, &kside_bytes);
+        have_kside = kside_bytes > 0;      // (the image of hgt_edge_logits_kside: made for every precision, like the fragment images for the split ones)
         mfma_agg = have_frags && !(a->flags & HGT_FLAG_VALU_AGGREGATE);
         if (stage == 5) {   // one target block: the fused kernel pair of the single-GPU layer on a range of destination tiles
             if (a->q_begin < 0 || a->q_end < a->q_begin || a->q_end > NQ || (a->q_begin % HGT_TD) != 0 || a->item_begin < 0 ||
@@ -229,6 +243,7 @@ struct Conv {
         msg_p = (float*)(pb ? pb + pl.off_msg_p : wb + w.off_msg_p);
         msg_f_buf = pb ? pb + pl.off_msg_f : wb + w.off_msg_f;
         att_f_buf = pb ? pb + pl.off_att_f : wb + w.off_att_f;
+        att_k_buf = pb ? pb + pl.off_att_k : wb + w.off_att_k;
         rte_k = a->use_rte ? (float*)(pb ? pb + pl.off_rte_k : wb + w.off_rte_k) : nullptr;
         rte_v = a->use_rte ? (float*)(pb ? pb + pl.off_rte_v : wb + w.off_rte_v) : nullptr;
         ws_qkv = pb ? (void*)(pb + pl.off_ws_qkv) : (void*)(wb + w.off_ws_qkv);   // tiles of the full [Q|K|V] weight
@@ -247,6 +262,16 @@ struct Conv {
         // logits: the target-side transforms on the matrix cores where the vector-ALU kernel is instruction-bound (d_k >= 64)
         r.mfma_logits = have_frags && !(fl & HGT_FLAG_VALU_LOGITS) && stage != 4 && (dkp >= 64 || (fl & HGT_FLAG_MFMA_LOGITS));
         r.logits = stage == 5 ? LOGITS_RANGE : sliced ? LOGITS_SLICE : r.mfma_logits ? LOGITS_MFMA : LOGITS_VALU;
+        // ... and the transform on the source side, per edge (hgt_edge_logits_kside), where that kernel is covered: 32-column heads in
+        // one head group, no temporal rows, rows below 4 GiB; whole-layer and plain staged calls with a split precision.  By default
+        // from 64-edge work items on (the 16- and 32-edge items of sampled batches are ragged batches of 32 lanes) and only when neither
+        // logits flag names another kernel; HGT_FLAG_KSIDE_LOGITS: whatever the item size, HGT_FLAG_NO_KSIDE_LOGITS: never
+        const bool kside_covered = have_kside && split && !a->use_rte && stage != 4 &&
+                                   (uint64_t)N * (uint64_t)H * (uint64_t)dkp * 4u < (1ull << 32);
+        const bool kside = kside_covered && !(fl & HGT_FLAG_NO_KSIDE_LOGITS) &&
+                           ((fl & HGT_FLAG_KSIDE_LOGITS) || (hgt_item_edges(E) >= 64 && !(fl & (HGT_FLAG_MFMA_LOGITS | HGT_FLAG_VALU_LOGITS))));
+        r.kside_range = kside && stage == 5;
+        if (kside && stage != 5) r.logits = LOGITS_KSIDE;
         // (graphs below HGT_FUSED_MIN_NODES targets take the unfused kernels: the latency regime, see items)
         const bool fused = split && !dense && dp <= 256 && dout <= dp && (dout & 3) == 0 && (din & 3) == 0 &&
                            (NQ >= HGT_FUSED_MIN_NODES || (fl & HGT_FLAG_FUSED_ANY_SIZE)) &&
@@ -315,6 +340,7 @@ struct Conv {
         if (!fresh) return HGT_OK;
         int rc = hgt_relation_pack(a->relation_att, a->relation_msg, a->relation_pri, R, a->n_heads, H, lay.d_k, dkp, att_t, msg_p, stream);
         auto frag_pack = f16 ? hgt_relation_frag_pack_f16 : hgt_relation_frag_pack;
+        if (rc == HGT_OK && have_kside) rc = hgt_relation_kside_pack(att_t, R, H, dkp, att_k_buf, stream);
         if (rc != HGT_OK || !have_frags || (rc = frag_pack(msg_p, R, H, dkp, msg_f_buf, stream)) != HGT_OK) return rc;
         return frag_pack(att_t, R, H, dkp, att_f_buf, stream);
     }
@@ -362,8 +388,17 @@ struct Conv {
     }
 
     int edge_logits() const {
+        if (r.logits == LOGITS_KSIDE) {      // (route() checked the coverage; an answer of "unsupported" still takes the other kernels)
+            const int rc = hgt_edge_logits_kside(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_t, att_k_buf, fmode, logits, stream);
+            if (rc != HGT_ERR_UNSUPPORTED) return rc;
+            if (r.mfma_logits) return hgt_edge_logits_mfma(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_t, att_f_buf, fmode, logits, stream);
+        }
         switch (r.logits) {
             case LOGITS_RANGE:
+                if (r.kside_range) {
+                    const int rc = hgt_edge_logits_kside_items(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_k_buf, logits, a->item_begin, a->item_end, stream);
+                    if (rc != HGT_ERR_UNSUPPORTED) return rc;
+                }
                 return hgt_edge_logits_range(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_t, r.mfma_logits ? att_f_buf : nullptr, fmode, logits,
                                              a->item_begin, a->item_end, stream);
             case LOGITS_SLICE: return hgt_edge_logits_slice(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_t, logits, sl_lo, sl_hi, stream);
