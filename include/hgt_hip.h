@@ -40,11 +40,12 @@ extern "C" {
 
 const char* hgt_strerror(int code);
 int hgt_abi_version(void);
-/* Bit mask of optional parts compiled into this library.  Bit 0 (HGT_FEATURE_LAB_KERNELS): the measured-and-not-adopted kernels of
- * csrc/lab/ (make LAB=1) -- only then do HGT_FLAG_RING_AGGREGATE / HGT_FLAG_SINGLE_PASS select anything; the shipped library is
- * built without them and ignores both flags. */
-#define HGT_FEATURE_LAB_KERNELS 1
-/* Bit 1: the atomic-free training entry points (hgt_*_det below): every reduction of the backward pass in an order fixed by the
+/* Bit mask of optional parts compiled into this library.  Bit 0 is retired (it announced two experimental kernels that no shipped
+ * library ever contained) and is never set.
+ * ABI note: with those kernels the export hgt_edge_single_pass_items left the library while HGT_ABI_VERSION stayed 8 -- in a
+ * shipped library it answered HGT_ERR_UNSUPPORTED for every call with edges, so no working caller loses anything, and a stale one
+ * fails at link time.
+ * Bit 1: the atomic-free training entry points (hgt_*_det below): every reduction of the backward pass in an order fixed by the
  * problem sizes alone. */
 #define HGT_FEATURE_DETERMINISTIC_TRAINING 2
 int hgt_build_features(void);
@@ -334,18 +335,6 @@ int hgt_edge_aggregate_items_update(const void* plan, int64_t n_nodes, int64_t n
                                     const int32_t* rows, const int32_t* group_off, int32_t n_groups, const void* w_a_split,
                                     const float* b_a, const float* x_skip, int64_t ld_skip, const float* skip, const float* ln_w,
                                     const float* ln_b, int32_t use_norm, int32_t n_out, float* out, void* stream);
-/* ABI 6: logits AND the item-parallel aggregation in one walk over the edges (sampled sub-graphs): per group of <= 16 runs the
- * target-side transform q~ = q A'[r] on the matrix cores (att_frag = hgt_relation_frag_pack[_f16](att_t)), then per edge K and V
- * gathered together, the logit, the run's online softmax and the weighted sum, then the message transform (msg_frag) -- no [E][H]
- * logits array, one launch less per layer.  Same scratch, same fixed-order merge and (up to the fp32 summation order of the
- * logits) the same result as hgt_edge_logits_mfma + hgt_edge_aggregate_items.  rte_k / rte_v: both tables or both NULL.
- * HGT_ERR_UNSUPPORTED for layouts it is not instantiated for (the caller takes the two-kernel form) -- and, in the shipped library,
- * for every call that has work to do (n_edges > 0 and target rows > 0; an empty call returns HGT_OK like every entry point): the
- * kernel (csrc/lab/hgt_edge_single_pass.hip, measured not faster) is compiled into LAB builds only (hgt_build_features). */
-int hgt_edge_single_pass_items(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations,
-                               int32_t n_heads, int32_t dk_pad, const float* Q, const float* K, const float* V, const float* rte_k,
-                               const float* rte_v, const void* att_frag, const void* msg_frag, int32_t frag_f16, float* agg,
-                               int64_t n_q_rows, int32_t apply_gelu, void* scratch, uint64_t scratch_bytes, void* stream);
 /* ABI 4: one slice [rel_lo, rel_hi) of the plan's n_relations + 1 relation buckets (bucket n_relations = unclaimed edges).
  * hgt_edge_logits_slice writes the logits of the slice's edges only.  hgt_edge_aggregate_slice (matrix-core kernel: msg_frag
  * required) aggregates the slice and combines it with what earlier slices left: state = f32[n_q_rows][n_heads][2] (softmax
@@ -723,9 +712,7 @@ typedef struct hgt_conv_args {
 #define HGT_FLAG_NO_ITEM_AGGREGATE 32 /* never hgt_edge_aggregate_items */
 #define HGT_FLAG_FUSED_ANY_SIZE 64   /* hgt_edge_aggregate_update below its default size too (default: n_q_rows >= 16384 -- targets, not nodes --, a
                                       * split precision, HGTConv, rows of at most 256 padded columns, fewer than 64 relations) */
-#define HGT_FLAG_SINGLE_PASS 256     /* LAB builds only (ignored otherwise: the two-kernel form runs).  ABI 6: hgt_edge_single_pass_items instead of logits + item-parallel aggregation where it applies (sampled
-                                      * sub-graphs, attention weights not exported).  Off by default: measured equal at c3 and 5 % slower at c5
-                                      * (its two LDS tiles cap it at 4 wavefronts per CU) */
+/* (bits 256 and 512, like feature bit 0, are retired: hgt_conv_forward ignores them, as every shipped library always did; do not reuse them) */
 #define HGT_FLAG_XS_GEMM_ALWAYS 1024 /* ABI 6: the x-stationary split GEMM (hgt_gemm_xs.hip) for every typed linear of the layer it covers, whatever
                                       * the row count (HGT_LINEAR_FORCE_XS); */
 #define HGT_FLAG_XS_GEMM_NEVER 2048  /* ... never (HGT_LINEAR_NO_XS): the slab kernels.  Bit-identical results either way: tests / A/B timings */
@@ -738,9 +725,6 @@ typedef struct hgt_conv_args {
                                       * (identical output bit for bit; tests / A/B timings).  The same switch is bit 1 of `frag_f16` of those calls */
 #define HGT_FLAG_COOP_EDGE_ALWAYS 32768 /* ... the shared-transform forms for work items of more than 16 edges too (default: the 16-edge items
                                       * of sampled batches only; larger items measured slower in lock-step rounds).  Bit 2 of `frag_f16` */
-#define HGT_FLAG_RING_AGGREGATE 512 /* LAB builds only (hgt_build_features() & HGT_FEATURE_LAB_KERNELS; ignored otherwise): the LDS-ring form of the fused
-                                     * aggregation kernel (round 5, csrc/lab/hgt_edge_agg_ring.h: rows by LDS-DMA, U tile in registers) where it exists
-                                     * (d = 256 / 8 heads, no temporal rows, bf16 split): bit-identical, measured 9 % slower at c2 */
 #define HGT_FLAG_DETERMINISTIC_HUBS 128 /* ABI 6: targets with more than 1024 in-edges ("hubs") are aggregated WITHOUT atomics: every piece of a
                                       * (hub, relation) range writes its partial row / exp-sum to its own slot and the finalize kernel sums
                                       * the slots in (relation, piece) order, so two forwards are bit-identical on every row (the default

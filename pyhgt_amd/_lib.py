@@ -20,8 +20,7 @@ HGT_FLAG_ITEM_AGGREGATE = 16
 HGT_FLAG_NO_ITEM_AGGREGATE = 32
 HGT_FLAG_FUSED_ANY_SIZE = 64
 HGT_FLAG_DETERMINISTIC_HUBS = 128
-HGT_FLAG_SINGLE_PASS = 256
-HGT_FLAG_RING_AGGREGATE = 512
+# (bits 256 and 512 are retired -- include/hgt_hip.h)
 HGT_FLAG_XS_GEMM_ALWAYS = 1024
 HGT_FLAG_XS_GEMM_NEVER = 2048
 HGT_FLAG_NO_TILE_GEMM = 4096
@@ -34,7 +33,6 @@ HGT_LINEAR_FORCE_XS = 0x100
 HGT_LINEAR_NO_XS = 0x200
 HGT_LINEAR_NO_TILE = 0x400
 HGT_LINEAR_TANH = 0x1000
-HGT_FEATURE_LAB_KERNELS = 1
 HGT_FEATURE_DETERMINISTIC_TRAINING = 2
 HGT_STACK_MAX_PIECES = 256
 HGT_SAMPLER_MAX_TYPES = 16
@@ -162,8 +160,6 @@ SIGNATURES = {
     "hgt_edge_aggregate_items_update": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _u64, _vp, _vp, _i32,
                                                   _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "hgt_edge_aggregate_items": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _u64, _vp]),
-    "hgt_edge_single_pass_items": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32,
-                                             _vp, _u64, _vp]),
     "hgt_plan_header_to_host": (C.c_int, [_vp, _vp, _vp]),
     "hgt_relation_frag_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_u64)]),
     "hgt_relation_frag_pack": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),

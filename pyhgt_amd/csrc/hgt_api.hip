@@ -130,7 +130,7 @@ __global__ void k_rte_row_lists(int T, int32_t* __restrict__ rows, int32_t* __re
 
 // The kernels of one call, decided once (Conv::route).  AGG_FUSED and AGG_ITEMS_UPDATE run the update themselves.
 enum LogitsForm { LOGITS_VALU, LOGITS_MFMA, LOGITS_SLICE, LOGITS_RANGE, LOGITS_KSIDE };
-enum AggForm { AGG_SINGLE_PASS, AGG_FUSED, AGG_ITEMS_UPDATE, AGG_ITEMS, AGG_SLICE, AGG_SUBTILE };
+enum AggForm { AGG_FUSED, AGG_ITEMS_UPDATE, AGG_ITEMS, AGG_SLICE, AGG_SUBTILE };
 enum UpdateForm { UPDATE_IN_AGGREGATION, UPDATE_LINEAR_FUSED, UPDATE_LINEAR_NODE, UPDATE_DENSE };
 struct ConvRoute {
     LogitsForm logits;
@@ -139,7 +139,7 @@ struct ConvRoute {
     bool mfma_logits;        // (the range form of stage 5 takes the fragment image of att_t when set)
     // aggregation forms in the order they are tried: a kernel that answers HGT_ERR_UNSUPPORTED (a head-group layout it is not
     // instantiated for -- the kernels decide that themselves) hands over to the next.  The last one is the slice or sub-tile form.
-    AggForm agg[5];
+    AggForm agg[4];
     int n_agg;
     UpdateForm update;
 };
@@ -283,9 +283,6 @@ struct Conv {
                            !(fl & HGT_FLAG_NO_ITEM_AGGREGATE) &&
                            (NQ < HGT_ITEM_AGG_DEFAULT_NODES || (fl & HGT_FLAG_ITEM_AGGREGATE));
         r.n_agg = 0;
-        // ... and, on request (HGT_FLAG_SINGLE_PASS) and when nobody asks for the attention weights, logits + runs in ONE walk
-        // (lab/hgt_edge_single_pass.hip, LAB builds only): one kernel and the [E][H] logits array less; measured equal at c3, 5 % slower at c5
-        if (items && !fused && !a->want_att && have_frags && E > 0 && (fl & HGT_FLAG_SINGLE_PASS)) r.agg[r.n_agg++] = AGG_SINGLE_PASS;
         if (fused) r.agg[r.n_agg++] = AGG_FUSED;   // preferred form: one kernel that never writes agg (hgt_edge_aggregate_update)
         // sampled batches (round 6): the merge pass of the item-parallel aggregation IS the node update (k_merge_update) -- two of the
         // layer's five dependent kernels become one and `agg` is never written
@@ -411,17 +408,13 @@ struct Conv {
     int aggregate_update(int64_t q0, int64_t q1, int hub_det) const {
         return hgt_edge_aggregate_update_sel(a->plan, N, E, T, R, H, dkp, logits, V, rte_v, msg_p, msg_f, agg, NQ, hub_ws,
                                              (int32_t*)(wb + w.off_pending), a->node_type, ws_upd, a->b_a, a->x, din, a->skip, a->ln_w,
-                                             a->ln_b, a->use_norm, dout, a->out, stream, q0, q1, f16 ? 1 : 0, hub_det,
-                                             (a->flags & HGT_FLAG_RING_AGGREGATE) ? 1 : 0);
+                                             a->ln_b, a->use_norm, dout, a->out, stream, q0, q1, f16 ? 1 : 0, hub_det);
     }
 
     // runs for E == 0 too: it writes the zero rows of isolated targets; HGTConv stores gelu(agg) (conv.py:119), DenseHGTConv agg
     int aggregate(AggForm form) const {
         void* zitems = wb + w.off_zitems;
         switch (form) {
-            case AGG_SINGLE_PASS:
-                return hgt_edge_single_pass_items(a->plan, N, E, T, R, H, dkp, Q, K, V, rte_k, rte_v, att_f_buf, msg_f, f16 ? 1 : 0, agg, NQ,
-                                                  dense ? 0 : 1, zitems, w.zitems_bytes, stream);
             case AGG_FUSED:
                 if (det_hubs && hub_ws && !msg_f)
                     return HGT_ERR_UNSUPPORTED;      // (vector-ALU aggregation: the unfused kernels carry the deterministic hub mode)
@@ -442,11 +435,10 @@ struct Conv {
         }
     }
 
-    // edge phase: logits, then softmax fused into the aggregation (online, per target sub-tile); a single pass makes its own logits
+    // edge phase: logits, then softmax fused into the aggregation (online, per target sub-tile)
     int edge_phase(AggForm* used) const {
         int i = 0, rc = HGT_ERR_UNSUPPORTED;
-        if (r.agg[0] == AGG_SINGLE_PASS && (rc = aggregate(r.agg[i++])) != HGT_OK && rc != HGT_ERR_UNSUPPORTED) return rc;
-        if (rc == HGT_ERR_UNSUPPORTED && E > 0) {
+        if (E > 0) {
             const int lrc = edge_logits();
             if (lrc != HGT_OK) return lrc;
         }
@@ -543,13 +535,7 @@ extern "C" const char* hgt_strerror(int code) {
 }
 
 extern "C" int hgt_abi_version(void) { return HGT_ABI_VERSION; }
-extern "C" int hgt_build_features(void) {
-#ifdef HGT_LAB_KERNELS
-    return HGT_FEATURE_LAB_KERNELS | HGT_FEATURE_DETERMINISTIC_TRAINING;
-#else
-    return HGT_FEATURE_DETERMINISTIC_TRAINING;
-#endif
-}
+extern "C" int hgt_build_features(void) { return HGT_FEATURE_DETERMINISTIC_TRAINING; }
 
 extern "C" int hgt_layout_for(int32_t d_out, int32_t n_heads, hgt_layout* out) {
     if (!out) return HGT_ERR_INVALID_ARG;

@@ -18,9 +18,6 @@
 #include "hgt_split_common.h"
 #include "hgt_wt_store.h"
 
-#ifndef HGT_LOGITS_XCD
-#define HGT_LOGITS_XCD 1
-#endif
 #ifndef HGT_AGI_GS
 #define HGT_AGI_GS 8      // column-tile steps whose fragments are requested together (16 loads in flight)
 #endif
@@ -59,13 +56,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_runs_mfma(
 
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if HGT_LOGITS_XCD     // XCD-aware item order, see k_edge_logits
-    constexpr int XC = 16;
-    const int q8 = (int)(blockIdx.x >> 3), vblock = (q8 / XC) * (8 * XC) + (int)(blockIdx.x & 7u) * XC + (q8 % XC);
-#else
-    const int vblock = blockIdx.x;
-#endif
-    const int item = vblock * 4 + wib;
+    const int item = hgt_item_block() * 4 + wib;      // (XCD-aware item order: hgt_edge_common.h)
     const HgtItem it = items[min(item, items_cap - 1)];      // (requested together with the header's item count: see k_edge_logits)
     const int n_items = hdr->n_items;
     if (item >= n_items) return;
@@ -274,13 +265,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_runs_coop(
 
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if HGT_LOGITS_XCD
-    constexpr int XC = 16;
-    const int q8 = (int)(blockIdx.x >> 3), vblock = (q8 / XC) * (8 * XC) + (int)(blockIdx.x & 7u) * XC + (q8 % XC);
-#else
-    const int vblock = blockIdx.x;
-#endif
-    const int item = vblock * 4 + wib;
+    const int item = hgt_item_block() * 4 + wib;      // (XCD-aware item order: hgt_edge_common.h)
     const HgtItem it = items[min(item, items_cap - 1)];
     const int n_items = hdr->n_items;
     const int beg = __builtin_amdgcn_readfirstlane(it.beg), end = __builtin_amdgcn_readfirstlane(it.end);
@@ -993,7 +978,7 @@ static int launch_runs(int mode, const HgtPlanView& pv, const float* logits, con
                        float* zrows, float* zstat, unsigned char* zflag, int R, int HT, hipStream_t stream, int raw = 0) {
     const bool f16 = (mode & 1) != 0;
     const int item_edges = mode >> 8;
-    const unsigned blocks = ((unsigned)((pv.L.max_items + 3) / 4) + 127u) & ~127u;
+    const unsigned blocks = hgt_item_grid((pv.L.max_items + 3) / 4);
     dim3 grid(blocks, (unsigned)(HT / (64 / LPH)));
 #define AGI_LAUNCH(KERNEL, RTE_, F16_)                                                                                     \
     KERNEL<VEC, LPH, RTE_, F16_><<<grid, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, pv.ertei, logits, V, rteV, msgF, \
@@ -1024,34 +1009,12 @@ extern "C" int hgt_edge_aggregate_items_bytes(int64_t n_edges, int32_t n_heads, 
     return HGT_OK;
 }
 
-// lab/hgt_edge_single_pass.hip (logits inside the runs kernel: correct, not faster -- DESIGN.md section 10): part of LAB builds only
-// (make LAB=1); the shipped library answers HGT_ERR_UNSUPPORTED and the caller takes the two-kernel form
-#ifdef HGT_LAB_KERNELS
-int hgt_launch_single_pass_runs(int vec, int lph, bool f16, const HgtPlanView& pv, const float* Q, const float* K, const float* V,
-                                const float* rteK, const float* rteV, const unsigned short* attF, const unsigned short* msgF, float* zrows,
-                                float* zstat, unsigned char* zflag, int R, int HT, hipStream_t stream);
-#else
-static int hgt_launch_single_pass_runs(int, int, bool, const HgtPlanView&, const float*, const float*, const float*, const float*, const float*,
-                                       const unsigned short*, const unsigned short*, float*, float*, unsigned char*, int, int, hipStream_t) {
-    return HGT_ERR_UNSUPPORTED;
-}
-#endif
-
-// sp != nullptr: the single-pass form (logits computed inside the runs kernel from Q, K and the attention fragments)
-struct SinglePassArgs {
-    const float* Q;
-    const float* K;
-    const float* rte_k;
-    const void* att_frag;
-};
-
 static int aggregate_items_impl(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
                                 const float* logits, const float* V, const float* rte_v, const void* msg_frag, int32_t frag_f16,
                                 float* agg, int64_t n_q_rows, int32_t apply_gelu, void* scratch, uint64_t scratch_bytes,
-                                void* stream_, const SinglePassArgs* spa, const MergeUpdateArgs* mu = nullptr, int64_t ld_out = 0) {
-    if (!plan || !V || !msg_frag || (!agg && !mu) || (E > 0 && ((!spa && !logits) || !scratch)) || H <= 0 || 64 % H != 0 || dk_pad <= 0)
+                                void* stream_, const MergeUpdateArgs* mu = nullptr, int64_t ld_out = 0) {
+    if (!plan || !V || !msg_frag || (!agg && !mu) || (E > 0 && (!logits || !scratch)) || H <= 0 || 64 % H != 0 || dk_pad <= 0)
         return HGT_ERR_INVALID_ARG;
-    if (spa && (!spa->Q || !spa->K || !spa->att_frag || ((spa->rte_k == nullptr) != (rte_v == nullptr)))) return HGT_ERR_INVALID_ARG;
     if (apply_gelu < 0 || apply_gelu > 2) return HGT_ERR_INVALID_ARG;
     const int64_t NQ = (n_q_rows > 0 && n_q_rows <= N) ? n_q_rows : N;
     if (NQ == 0) return HGT_OK;
@@ -1067,16 +1030,10 @@ static int aggregate_items_impl(const void* plan, int64_t N, int64_t E, int32_t 
     float* zstat = (float*)((char*)scratch + hgt_align_up((uint64_t)E * d * 4, 256));
     unsigned char* zflag = (unsigned char*)zstat + hgt_align_up((uint64_t)E * H * 8, 256);
     // the wavefront's layout after the head-group split of the matrix-core kernels (<= 256 columns per wavefront)
-    int sp = 1;
-    const int vec_full = dk_pad / lph;
-    while (vec_full / sp > 4 && lph * sp * 2 <= 64) sp *= 2;
-    if (vec_full / sp > 4) return HGT_ERR_UNSUPPORTED;
-    const int vec = vec_full / sp, lphs = lph * sp;
-    if (E > 0 && spa) {
-        int rc = hgt_launch_single_pass_runs(vec, lphs, (frag_f16 & 1) != 0, pv, spa->Q, spa->K, V, spa->rte_k, rte_v, (const unsigned short*)spa->att_frag,
-                                             (const unsigned short*)msg_frag, zrows, zstat, zflag, (int)R, (int)H, stream);
-        if (rc != HGT_OK) return rc;
-    } else if (E > 0) {
+    const int sp = mfma_split_for(dk_pad / lph, lph);
+    if (sp == 0) return HGT_ERR_UNSUPPORTED;
+    const int vec = dk_pad / lph / sp, lphs = lph * sp;
+    if (E > 0) {
         int rc = HGT_ERR_UNSUPPORTED;
 #define AGI_CASE(V_, L_) \
         if (vec == V_ && lphs == L_) rc = launch_runs<V_, L_>((frag_f16 & 7) | (hgt_item_edges(E) << 8), pv, logits, V, rte_v, (const unsigned short*)msg_frag, zrows, zstat, zflag, (int)R, (int)H, stream, apply_gelu == 2 ? 1 : 0);
@@ -1129,20 +1086,7 @@ extern "C" int hgt_edge_aggregate_items(const void* plan, int64_t N, int64_t E, 
                                         float* agg, int64_t n_q_rows, int32_t apply_gelu, void* scratch, uint64_t scratch_bytes,
                                         void* stream_) {
     return aggregate_items_impl(plan, N, E, T, R, H, dk_pad, logits, V, rte_v, msg_frag, frag_f16, agg, n_q_rows, apply_gelu, scratch,
-                                scratch_bytes, stream_, nullptr);
-}
-
-// ABI 6: logits + item-parallel aggregation in ONE walk (hgt_edge_single_pass.hip) for sampled sub-graphs: no [E][H] logits array.
-// att_frag / msg_frag = hgt_relation_frag_pack[_f16] of att_t / msg_p; rte_k and rte_v both or neither; same scratch and the same
-// result (up to fp32 rounding of the logits' summation order) as hgt_edge_logits_mfma + hgt_edge_aggregate_items.
-// HGT_ERR_UNSUPPORTED for layouts the kernel is not instantiated for.
-extern "C" int hgt_edge_single_pass_items(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad,
-                                          const float* Q, const float* K, const float* V, const float* rte_k, const float* rte_v,
-                                          const void* att_frag, const void* msg_frag, int32_t frag_f16, float* agg, int64_t n_q_rows,
-                                          int32_t apply_gelu, void* scratch, uint64_t scratch_bytes, void* stream_) {
-    const SinglePassArgs spa = {Q, K, rte_k, att_frag};
-    return aggregate_items_impl(plan, N, E, T, R, H, dk_pad, nullptr, V, rte_v, msg_frag, frag_f16, agg, n_q_rows, apply_gelu, scratch,
-                                scratch_bytes, stream_, &spa);
+                                scratch_bytes, stream_);
 }
 
 // ABI 7: item-parallel aggregation whose merge pass IS the node update: hgt_edge_aggregate_items followed by hgt_linear_update_* (a_linear +
@@ -1167,7 +1111,7 @@ extern "C" int hgt_edge_aggregate_items_update(const void* plan, int64_t N, int6
     m.wsplit = (const unsigned short*)w_a_split; m.bias = b_a; m.xs = x_skip; m.ldxs = ld_skip; m.skip = skip; m.lnw = ln_w; m.lnb = ln_b;
     m.use_norm = use_norm; m.out = out;
     return aggregate_items_impl(plan, N, E, T, R, H, dk_pad, logits, V, rte_v, msg_frag, frag_f16, nullptr, n_q_rows, 1, scratch, scratch_bytes,
-                                stream_, nullptr, &m);
+                                stream_, &m);
 }
 
 // ABI 7: hgt_edge_spmm (GIVEN edge weights, plain weighted sum: the gather passes of the backward) on the item-parallel kernels -- the
@@ -1180,5 +1124,5 @@ extern "C" int hgt_edge_spmm_items(const void* plan, int64_t N, int64_t E, int32
                                    int64_t ld_out, int64_t n_q_rows, void* scratch, uint64_t scratch_bytes, void* stream_) {
     if (!out || ld_out < (int64_t)H * dk_pad || (ld_out & 3) != 0 || (((uintptr_t)out) & 15) != 0) return HGT_ERR_UNSUPPORTED;
     return aggregate_items_impl(plan, N, E, T, R, H, dk_pad, weights, rows, rte_rows, f_frag, 0, out, n_q_rows, 2, scratch, scratch_bytes, stream_,
-                                nullptr, nullptr, ld_out);
+                                nullptr, ld_out);
 }

@@ -1083,12 +1083,6 @@ __global__ __launch_bounds__(256, 2) void k_edge_aggregate_hub_workgroups(
                                                smem + wib * 2 * G::PLANE, s_m, s_m + 256, s_scale + wib * 16, s_sig + wib * 16);
 }
 
-// the LDS-ring form of the fused kernel (lab/hgt_edge_agg_ring.h: bit-identical, measured slower -- DESIGN.md section 10): LAB builds only
-#if defined(HGT_LAB_KERNELS) && defined(HGT_MFMA_PART_VEC) && HGT_MFMA_PART_VEC == 4 && HGT_MFMA_PART_RTE == 0 && HGT_MFMA_PART_F16 == 0
-#define HGT_HAVE_RING 1
-#include "lab/hgt_edge_agg_ring.h"
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // Launchers.  This file is compiled THIRTEEN times (csrc/Makefile): once as the main translation unit (C entry points, dispatch) and
 // once per (VEC, RTE, F16) PART, which instantiates the kernels of its five lane layouts -- the 60 x 2 kernel instantiations are then
@@ -1134,24 +1128,12 @@ static int launch_aggupd_mfma(HGT_MFMA_AGGUPD_ARGS) {
     const int64_t tiles = (NQ - fu.q_lo + 63) / 64;      // NQ = end of the launch's target range
     dim3 grid((unsigned)tiles, 1);
     const int32_t* hub_slot = hb.mx ? pv.hub_slot : nullptr;
-    bool ring = false;
-#ifdef HGT_HAVE_RING
-    // d = 256 / 8 heads, no temporal rows, bf16 split, on request (HGT_FLAG_RING_AGGREGATE): the ring form (hgt_edge_agg_ring.h)
-    if constexpr (VEC == 4 && LPH == 8 && !RTE && !F16) {
-      if (fu.ring) {
-        ring = true;
-        k_edge_aggregate_update_ring<false><<<grid, 256, 0, stream>>>(pv.segptr, pv.esrc, pv.edst, logits, V, msgF, R, NQ, hub_slot, pending, fu);
-      }
-    }
-#endif
-    if (!ring) {
-        if (fu.small32)
-            k_edge_aggregate_update_mfma<VEC, LPH, RTE, F16, true><<<grid, 256, 0, stream>>>(pv.segptr, pv.esrc, pv.edst, pv.ertei, logits, V, rteV, msgF,
-                                                                                            agg, R, NQ, HT, hub_slot, pending, fu);
-        else
-            k_edge_aggregate_update_mfma<VEC, LPH, RTE, F16, false><<<grid, 256, 0, stream>>>(pv.segptr, pv.esrc, pv.edst, pv.ertei, logits, V, rteV, msgF,
-                                                                                             agg, R, NQ, HT, hub_slot, pending, fu);
-    }
+    if (fu.small32)
+        k_edge_aggregate_update_mfma<VEC, LPH, RTE, F16, true><<<grid, 256, 0, stream>>>(pv.segptr, pv.esrc, pv.edst, pv.ertei, logits, V, rteV, msgF,
+                                                                                        agg, R, NQ, HT, hub_slot, pending, fu);
+    else
+        k_edge_aggregate_update_mfma<VEC, LPH, RTE, F16, false><<<grid, 256, 0, stream>>>(pv.segptr, pv.esrc, pv.edst, pv.ertei, logits, V, rteV, msgF,
+                                                                                         agg, R, NQ, HT, hub_slot, pending, fu);
     if (hb.mx) {   // workgroups with a hub target: their other targets, then the hub path + the update of those workgroups
         k_edge_aggregate_hub_workgroups<VEC, LPH, RTE, F16><<<dim3((unsigned)tiles * (16 / HGT_HUBWG_SUB), 1), 256, 0, stream>>>(pv.segptr, pv.esrc, pv.edst, pv.ertei, logits, V, rteV, msgF,
                                                                                      agg, R, NQ, HT, hub_slot, pending, fu.q_lo);
@@ -1162,13 +1144,6 @@ static int launch_aggupd_mfma(HGT_MFMA_AGGUPD_ARGS) {
     return HGT_OK;
 }
 #endif
-
-// head-group split of the matrix-core kernels: the wave's slice must be <= 256 columns (VEC <= 4): 16 KB of U tile per wave
-static int mfma_split_for(int vec_full, int lph_full) {
-    int s = 1;
-    while (vec_full / s > 4 && lph_full * s * 2 <= 64) s *= 2;
-    return (vec_full / s <= 4) ? s : 0;   // 0: not covered (one head wider than 256 columns)
-}
 
 // det: the deterministic hub mode (one partial slot per piece behind the atomic accumulators; hgt_hub_workspace_bytes_ex)
 static HgtHubBuffers carve_hub(void* hub_ws, const HgtPlanView& pv, int H, int64_t E, int dk_pad = 0, int R = 0, bool det = false) {
@@ -1397,7 +1372,7 @@ static int edge_aggregate_update_impl(bool f16, const void* plan, int64_t N, int
                                       const int64_t* node_type, const void* w_a_split, const float* b_a, const float* x_skip,
                                       int64_t ld_skip, const float* skip, const float* ln_w, const float* ln_b, int32_t use_norm,
                                       int32_t n_out, float* out, void* stream, int64_t q_begin = 0, int64_t q_end = -1,
-                                      bool det_hubs = false, bool use_ring = false) {
+                                      bool det_hubs = false) {
     if (f16 && !msg_frag) return HGT_ERR_INVALID_ARG;
     if (!plan || !V || !msg_p || !agg || !pending || !node_type || !w_a_split || !b_a || !x_skip || !skip || !out || H <= 0 ||
         64 % H != 0 || dk_pad <= 0 || n_out <= 0)
@@ -1420,7 +1395,7 @@ static int edge_aggregate_update_impl(bool f16, const void* plan, int64_t N, int
     HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
     HgtHubBuffers hb = carve_hub(hub_ws, pv, H, E, dk_pad, R, det_hubs);
     HgtFusedUpdate fu = {node_type, (const unsigned short*)w_a_split, b_a, x_skip, ld_skip, skip, ln_w, ln_b, use_norm, T, n_out, out,
-                         ranged ? q_begin : 0, use_ring ? 1 : 0,
+                         ranged ? q_begin : 0,
                          // every gathered row / logit / temporal row sits below 4 GiB from its base: the fused kernels address them
                          // with 32-bit lane offsets
                          ((uint64_t)N * (uint64_t)dp * 4u < (1ull << 32) && (uint64_t)E * (uint64_t)H * 4u < (1ull << 32)) ? 1 : 0};
@@ -1454,8 +1429,8 @@ extern "C" int hgt_edge_aggregate_update_range(HGT_AGGUPD_PARAMS, int64_t q_begi
     return edge_aggregate_update_impl(frag_f16 != 0, HGT_AGGUPD_PASS, q_begin, q_end, hub_deterministic != 0);
 }
 
-int hgt_edge_aggregate_update_sel(HGT_AGGUPD_PARAMS, int64_t q_begin, int64_t q_end, int32_t frag_f16, int32_t hub_deterministic, int32_t use_ring) {
-    return edge_aggregate_update_impl(frag_f16 != 0, HGT_AGGUPD_PASS, q_begin, q_end, hub_deterministic != 0, use_ring != 0);
+int hgt_edge_aggregate_update_sel(HGT_AGGUPD_PARAMS, int64_t q_begin, int64_t q_end, int32_t frag_f16, int32_t hub_deterministic) {
+    return edge_aggregate_update_impl(frag_f16 != 0, HGT_AGGUPD_PASS, q_begin, q_end, hub_deterministic != 0);
 }
 
 // out[i][ld_out] = sum_rel ( sum_{e in (i,rel)} w_e rows[src_e] ) F[rel]  -- the aggregation kernel without the softmax: the edge

@@ -1,6 +1,7 @@
 // Helpers shared by the edge-phase translation units (hgt_edge_logits.hip, hgt_edge_agg_valu.hip, hgt_edge_agg_mfma.hip,
 // hgt_edge_hub.hip): lane-group reductions, row loads, the register-resident relation mat-vec of the vector-ALU kernels, the
-// (vec, lanes-per-head) layout dispatch, and the structs that cross translation units.
+// (vec, lanes-per-head) layout dispatch, the head-group split rules, the item order of the item-parallel kernels with its grid
+// rule, and the structs that cross translation units.
 #pragma once
 #include "hgt_common.h"
 
@@ -38,7 +39,6 @@ struct HgtFusedUpdate {
     int use_norm, n_types, n_out;
     float* out;                      // [NQ][n_out]
     int64_t q_lo;                    // first target row of the launch (a multiple of 64): workgroup b owns rows q_lo + 64 b ..
-    int ring;                        // HGT_FLAG_RING_AGGREGATE: k_edge_aggregate_update_ring where it is instantiated
     int small32;                     // V / logits / temporal rows lie below 4 GiB from their bases (launcher: the S32 instantiation, 32-bit lane offsets)
 };
 
@@ -177,5 +177,40 @@ static int head_split_for(int vec_full, int lph_full, int dk_pad) {
     while (dk_pad * (vec_full / s) > 128 && (vec_full / s) > 1 && lph_full * s * 2 <= 64) s *= 2;
     return s;
 }
+
+// Head-group split of the matrix-core kernels (logits, aggregation, item-parallel aggregation -- they share one fragment image, so
+// they must agree): the wave's slice must be <= 256 columns (VEC <= 4): 16 KB of U tile per wave.
+// 0: not covered (one head wider than 256 columns).
+static int mfma_split_for(int vec_full, int lph_full) {
+    int s = 1;
+    while (vec_full / s > 4 && lph_full * s * 2 <= 64) s *= 2;
+    return (vec_full / s <= 4) ? s : 0;
+}
+
+// XCD-aware item order of the item-parallel kernels (k_edge_logits, k_edge_logits_mfma, k_edge_logits_coop, k_edge_logits_kside,
+// k_edge_runs_mfma, k_edge_runs_coop): the virtual block of blockIdx.x; the workgroup takes the items of that block.
+// Workgroups are dealt to the 8 XCDs round-robin (linear id % 8), and the R + 1 items of a target tile (adjacent in the item list)
+// all read the tile's Q rows.  The XCDs take runs of XC consecutive item groups in turn, so a tile's items meet in one L2 at
+// about the same time instead of pulling the tile through eight of them (HGT_LOGITS_XCD=0: the plain order).
+// (chunks of XC workgroups, dealt to the XCDs in turn: contiguous EIGHTHS of the list put all the heavy items of a skewed graph --
+//  its hub tiles come first -- on one XCD: Zipf(0.8) logits 2.2 -> 3.2 ms)
+// A permutation only of a grid that is a multiple of 8 * XC workgroups: launch with hgt_item_grid().
+#ifndef HGT_LOGITS_XCD
+#define HGT_LOGITS_XCD 1
+#endif
+__device__ __forceinline__ int hgt_item_block() {
+#if HGT_LOGITS_XCD
+    constexpr int XC = 16;
+    const int q8 = (int)(blockIdx.x >> 3);
+    return (q8 / XC) * (8 * XC) + (int)(blockIdx.x & 7u) * XC + (q8 % XC);
+#else
+    return blockIdx.x;
+#endif
+}
+
+// gridDim.x of a kernel that orders its items with hgt_item_block(): n_blocks rounded up to 8 XCDs x 16, the period of that
+// permutation -- on any other grid two workgroups would take one virtual block and another would be left out.  The workgroups past
+// n_blocks find no item and return.
+static unsigned hgt_item_grid(int64_t n_blocks) { return ((unsigned)n_blocks + 127u) & ~127u; }
 
 }  // namespace

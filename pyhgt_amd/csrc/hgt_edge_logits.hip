@@ -17,10 +17,6 @@
 // lanes with DPP.  Rows for the next UN edges are requested before the current ones are consumed.
 #include "hgt_edge_common.h"
 
-#ifndef HGT_LOGITS_XCD
-#define HGT_LOGITS_XCD 1
-#endif
-
 namespace {
 
 // ---------------------------------------------------------------------------------------------
@@ -49,21 +45,9 @@ __global__ __launch_bounds__(256) void k_edge_logits(
 
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // XCD-aware item order: workgroups are dealt to the 8 XCDs round-robin (linear id % 8), and the R + 1 items of a target tile
-    // (adjacent in the item list) all read the tile's Q rows.  The XCDs take runs of 16 consecutive item groups in turn, so a
-    // tile's items meet in one L2 at about the same time instead of pulling the tile through eight of them (HGT_LOGITS_XCD=0:
-    // the plain order; gridDim.x is a multiple of 128)
     // (the item is requested TOGETHER with the header's item count -- index clamped to the table -- not behind it: one dependent
     //  round trip less in front of every wavefront's first row; sampled batches are a chain of such round trips, r6)
-#if HGT_LOGITS_XCD
-    // (chunks of HGT_XCD_CHUNK workgroups, dealt to the XCDs in turn: contiguous EIGHTHS of the list put all the heavy items of a
-    //  skewed graph -- its hub tiles come first -- on one XCD: Zipf(0.8) logits 2.2 -> 3.2 ms)
-    constexpr int XC = 16;
-    const int q8 = (int)(blockIdx.x >> 3), vblock = (q8 / XC) * (8 * XC) + (int)(blockIdx.x & 7u) * XC + (q8 % XC);
-#else
-    const int vblock = blockIdx.x;
-#endif
-    const int item = item_lo + vblock * 4 + wib;
+    const int item = item_lo + hgt_item_block() * 4 + wib;
     const HgtItem it = items[min(item, items_cap - 1)];
     const int n_items = item_hi >= 0 ? item_hi : hdr->n_items;      // (item_lo, item_hi): the items of a target block, or (0, -1)
     if (item >= n_items) return;
@@ -221,7 +205,7 @@ struct LaunchLogits {
     static int run(const HgtPlanView& pv, const float* Q, const float* K, const float* rteK, const float* attT, float* logits,
                    int R, int HT, int rel_lo, int rel_hi, int item_lo, int item_hi, int small32, hipStream_t stream) {
         const int64_t n_launch = item_hi >= 0 ? (int64_t)(item_hi - item_lo) : pv.L.max_items;
-        const unsigned blocks = ((unsigned)((n_launch + 3) / 4) + 127u) & ~127u;      // (a multiple of 8 XCDs x 16: XCD-aware item order)
+        const unsigned blocks = hgt_item_grid((n_launch + 3) / 4);
         dim3 grid(blocks, (unsigned)(HT / (64 / LPH)));
         if (small32 && grid.y == 1) {
             if (rteK)
@@ -253,13 +237,6 @@ extern "C" int hgt_relation_pack(const float* relation_att, const float* relatio
 int hgt_launch_logits_mfma(int vec, int lph, int mode, const HgtPlanView& pv, const float* Q, const float* K, const float* rteK,
                            const unsigned short* attF, float* logits, int R, int HT, int rel_lo, int rel_hi, int item_lo, int item_hi, hipStream_t stream);
 
-// head-group split of the matrix-core kernels (hgt_edge_agg_mfma.hip): the wave's slice must be <= 256 columns
-static int mfma_logits_split_for(int vec_full, int lph_full) {
-    int s = 1;
-    while (vec_full / s > 4 && lph_full * s * 2 <= 64) s *= 2;
-    return (vec_full / s <= 4) ? s : 0;
-}
-
 static int edge_logits_impl(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad, const float* Q,
                             const float* K, const float* rte_k, const float* att_t, float* logits, int rel_lo, int rel_hi, void* stream,
                             const void* att_frag = nullptr, int frag_f16 = 0, int item_lo = 0, int item_hi = -1) {
@@ -271,7 +248,7 @@ static int edge_logits_impl(const void* plan, int64_t N, int64_t E, int32_t T, i
     if (dk_pad % lph != 0) return HGT_ERR_INVALID_ARG;
     HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
     if (att_frag) {      // target-side transforms on the matrix cores; layouts it does not cover take the vector-ALU kernel below
-        const int spm = mfma_logits_split_for(dk_pad / lph, lph);
+        const int spm = mfma_split_for(dk_pad / lph, lph);
         if (spm != 0) {
             int rc = hgt_launch_logits_mfma(dk_pad / lph / spm, lph * spm, (frag_f16 & 7) | (hgt_item_edges(E) << 8), pv, Q, K, rte_k, (const unsigned short*)att_frag,
                                             logits, (int)R, (int)H, rel_lo, rel_hi, item_lo, item_hi, (hipStream_t)stream);

@@ -28,10 +28,6 @@
 #include "hgt_split_common.h"
 #include "hgt_kside_map.h"
 
-#ifndef HGT_LOGITS_XCD
-#define HGT_LOGITS_XCD 1
-#endif
-
 namespace {
 
 typedef unsigned hgt_u32x2 __attribute__((ext_vector_type(2)));
@@ -194,13 +190,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_logits_kside(
     constexpr unsigned ROWB = H * 128;                   // bytes of a Q / K row
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if HGT_LOGITS_XCD     // XCD-aware item order, see k_edge_logits
-    constexpr int XC = 16;
-    const int q8 = (int)(blockIdx.x >> 3), vblock = (q8 / XC) * (8 * XC) + (int)(blockIdx.x & 7u) * XC + (q8 % XC);
-#else
-    const int vblock = blockIdx.x;
-#endif
-    const int item = item_lo + vblock * (4 / WPI) + wib / WPI;
+    const int item = item_lo + hgt_item_block() * (4 / WPI) + wib / WPI;      // (XCD-aware item order: hgt_edge_common.h)
     const int h0 = (wib % WPI) * HW;                         // first head of this wavefront
     const HgtItem it = items[min(item, items_cap - 1)];      // (requested together with the header's item count: see k_edge_logits)
     if (item >= (item_hi >= 0 ? item_hi : hdr->n_items)) return;      // (item_lo, item_hi): the items of a target block, or (0, -1)
@@ -277,7 +267,7 @@ static void launch_kside(const HgtPlanView& pv, const float* Q, const float* K, 
                          int item_lo, int item_hi, hipStream_t stream) {
     constexpr int IPW = H == 8 ? 2 : 4;                                             // items per workgroup
     const int64_t n_launch = item_hi >= 0 ? (int64_t)(item_hi - item_lo) : pv.L.max_items;
-    const unsigned blocks = ((unsigned)((n_launch + IPW - 1) / IPW) + 127u) & ~127u;      // (a multiple of 8 XCDs x 16: XCD-aware item order)
+    const unsigned blocks = hgt_item_grid((n_launch + IPW - 1) / IPW);
     k_edge_logits_kside<H><<<blocks, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, Q, K, table_bytes, img, logits, R, item_lo, item_hi, (int)pv.L.max_items);
 }
 

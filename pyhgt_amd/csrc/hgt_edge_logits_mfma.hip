@@ -20,9 +20,6 @@
 #include "hgt_edge_common.h"
 #include "hgt_split_common.h"
 
-#ifndef HGT_LOGITS_XCD
-#define HGT_LOGITS_XCD 1
-#endif
 #ifndef HGT_LGM_GS
 #define HGT_LGM_GS 8      // column-tile steps whose fragments are requested together (16 loads in flight)
 #endif
@@ -69,15 +66,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_logits_mfma(
 
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if HGT_LOGITS_XCD     // XCD-aware item order, see k_edge_logits
-    // (chunks of HGT_XCD_CHUNK workgroups, dealt to the XCDs in turn: contiguous EIGHTHS of the list put all the heavy items of a
-    //  skewed graph -- its hub tiles come first -- on one XCD: Zipf(0.8) logits 2.2 -> 3.2 ms)
-    constexpr int XC = 16;
-    const int q8 = (int)(blockIdx.x >> 3), vblock = (q8 / XC) * (8 * XC) + (int)(blockIdx.x & 7u) * XC + (q8 % XC);
-#else
-    const int vblock = blockIdx.x;
-#endif
-    const int item = item_lo + vblock * 4 + wib;
+    const int item = item_lo + hgt_item_block() * 4 + wib;      // (XCD-aware item order: hgt_edge_common.h)
     const HgtItem it = items[min(item, items_cap - 1)];              // (requested together with the header's item count: see k_edge_logits)
     const int n_items = item_hi >= 0 ? item_hi : hdr->n_items;      // (item_lo, item_hi): the items of a target block, or (0, -1)
     if (item >= n_items) return;
@@ -316,13 +305,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_logits_coop(
 
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if HGT_LOGITS_XCD
-    constexpr int XC = 16;
-    const int q8 = (int)(blockIdx.x >> 3), vblock = (q8 / XC) * (8 * XC) + (int)(blockIdx.x & 7u) * XC + (q8 % XC);
-#else
-    const int vblock = blockIdx.x;
-#endif
-    const int item = item_lo + vblock * 4 + wib;
+    const int item = item_lo + hgt_item_block() * 4 + wib;      // (XCD-aware item order: hgt_edge_common.h)
     const HgtItem it = items[min(item, items_cap - 1)];
     const int n_items = item_hi >= 0 ? item_hi : hdr->n_items;
     const int beg = __builtin_amdgcn_readfirstlane(it.beg), end = __builtin_amdgcn_readfirstlane(it.end);
@@ -556,7 +539,7 @@ static int launch_logits_mfma(int mode, const HgtPlanView& pv, const float* Q, c
     const bool f16 = (mode & 1) != 0;
     const int item_edges = mode >> 8;
     const int64_t n_launch = item_hi >= 0 ? (int64_t)(item_hi - item_lo) : pv.L.max_items;
-    const unsigned blocks = ((unsigned)((n_launch + 3) / 4) + 127u) & ~127u;      // (a multiple of 8 XCDs x 16: XCD-aware item order)
+    const unsigned blocks = hgt_item_grid((n_launch + 3) / 4);
     dim3 grid(blocks, (unsigned)(HT / (64 / LPH)));
     using G = LG<VEC, LPH>;
     // d_k >= 64 and the 16-edge items of a sampled batch: the transform shared by the workgroup (a wavefront's quarter of the fragment

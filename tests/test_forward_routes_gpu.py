@@ -135,7 +135,7 @@ def _layout(d, n_heads):
 
 
 def _mfma_split(vec_full, lph):
-    """mfma_split_for (hgt_edge_agg_mfma.hip): head groups per row so that a wavefront's slice is <= 256 columns; 0 = not covered."""
+    """mfma_split_for (hgt_edge_common.h): head groups per row so that a wavefront's slice is <= 256 columns; 0 = not covered."""
     s = 1
     while vec_full // s > 4 and lph * s * 2 <= 64:
         s *= 2

@@ -92,8 +92,7 @@ final)
     python -m pytest tests -m gpu -q 2>&1 | tail -25 > $OUT/pytest_$TAG.log
     grep -E "^FAILED|^ERROR| passed| failed" $OUT/pytest_$TAG.log | tail -10
     # the x-stationary GEMM (1024) and the fused sub-tile aggregation (64) forced onto every layer of the backward / staged / oracle tests
-    # (their size thresholds keep them off small graphs otherwise).  The LDS-ring aggregation / single-pass runs (512 / 256) exist in LAB
-    # builds only (make LAB=1: tools/lab/build_lab.sh compiles them; the shipped library ignores the bits)
+    # (their size thresholds keep them off small graphs otherwise)
     HGT_TEST_KERNEL_FLAGS=$((1024 + 64)) timeout 900 python -m pytest tests -m gpu -q -k "backward or staged or two_rank or matches_oracle or fused or golden" 2>&1 | tail -3
     timeout 300 python tools/bench_xs.py > $OUT/${TAG}_xs_check.log 2>&1; grep -v "BIT-IDENTICAL (" $OUT/${TAG}_xs_check.log | tail -12
     tools/profile_pmc.sh $TAG > $OUT/prof_$TAG.log 2>&1
