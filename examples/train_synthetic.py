@@ -10,7 +10,7 @@ forward and one backward for the launch count of one batch.  It is ONE optimizer
 and its dropout masks are drawn over the stacked rows: another draw than B separate steps'.
 
 Everything on the hot path runs on the HIP kernels of pyhgt_amd (forward and backward); torch supplies the optimizer, the loss
-and the autograd boundary."""
+and the autograd boundary.  --device-optimizer: the clip and the AdamW update run on pyhgt_amd's kernels as well."""
 import argparse
 import os
 import sys
@@ -24,7 +24,7 @@ from pyhgt_amd.sampled import stack_device_graphs, synthetic_sampled_batch, to_d
 
 
 def run(schema="mag", steps=30, conv="hgt", n_hid=128, n_heads=8, n_layers=2, n_classes=16, batch_size=128, lr=2e-3, seed=0,
-        device="cuda:0", verbose=True, deterministic=False, recompute=False, stack=1):
+        device="cuda:0", verbose=True, deterministic=False, recompute=False, stack=1, device_optimizer=False):
     torch.manual_seed(seed)      # (already seeds the parameters and the dropout masks; deterministic=True makes the gradients repeat too)
     feat_dim = 129 if schema == "mag" else 256
     batches = []
@@ -51,7 +51,11 @@ def run(schema="mag", steps=30, conv="hgt", n_hid=128, n_heads=8, n_layers=2, n_
     if deterministic:      # every reduction of the backward in a fixed order: two runs with one seed give the same bits
         import pyhgt_amd
         pyhgt_amd.set_deterministic(gnn, True), pyhgt_amd.set_deterministic(head, True)
-    opt = torch.optim.AdamW(list(gnn.parameters()) + list(head.parameters()), lr=lr)
+    if device_optimizer:   # clip + AdamW in three launches of pyhgt_amd's own kernels; the head stays out of the norm, as below
+        import pyhgt_amd
+        opt = pyhgt_amd.AdamW([dict(params=list(gnn.parameters())), dict(params=list(head.parameters()), clip=False)], lr=lr, max_norm=0.5)
+    else:
+        opt = torch.optim.AdamW(list(gnn.parameters()) + list(head.parameters()), lr=lr)
     losses, t0 = [], time.perf_counter()
     for step in range(steps):
         (x, nt, tm, ei, et, _, _), y, seeds = batches[step % len(batches)]
@@ -60,7 +64,8 @@ def run(schema="mag", steps=30, conv="hgt", n_hid=128, n_heads=8, n_layers=2, n_
         loss = torch.nn.functional.nll_loss(head(rep[seeds]), y)
         opt.zero_grad()
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(gnn.parameters(), 0.5)
+        if not device_optimizer:
+            torch.nn.utils.clip_grad_norm_(gnn.parameters(), 0.5)
         opt.step()
         losses.append(loss.item())
         if verbose and (step % 5 == 0 or step == steps - 1):
@@ -83,5 +88,7 @@ if __name__ == "__main__":
     ap.add_argument("--recompute", action="store_true", help="memory-lean training: Q|K|V and the dropout masks are recomputed in the backward")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--stack", type=int, default=1, help="sampled batches per optimizer step, stacked on the device into one graph")
+    ap.add_argument("--device-optimizer", action="store_true", help="pyhgt_amd.AdamW(max_norm=0.5) in place of clip_grad_norm_ + torch.optim.AdamW")
     a = ap.parse_args()
-    run(a.schema, a.steps, a.conv, n_hid=a.n_hid, n_heads=a.n_heads, seed=a.seed, deterministic=a.deterministic, recompute=a.recompute, stack=a.stack)
+    run(a.schema, a.steps, a.conv, n_hid=a.n_hid, n_heads=a.n_heads, seed=a.seed, deterministic=a.deterministic, recompute=a.recompute, stack=a.stack,
+        device_optimizer=a.device_optimizer)

@@ -1133,6 +1133,87 @@ int hgt_vote_add(const float* logits, int64_t ld, int32_t n_cols, const int64_t*
                  const int32_t* slot_of, int64_t n_nodes, float* votes, int64_t ld_votes, int32_t* count, int32_t n_slots,
                  void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * The optimizer step (csrc/hgt_optim.hip): the line every training script of the reference ends a step with --
+ *   torch.nn.utils.clip_grad_norm_(model.parameters(), args.clip); optimizer.step()     (OAG/train_paper_field.py:251-252,
+ *   OAG/train_paper_venue.py:249-250, OAG/train_author_disambiguation.py:292-293, ogbn-mag/train_ogbn_mag.py:225-226)
+ * with optimizer = torch.optim.AdamW (OAG/train_paper_field.py:194, ogbn-mag/train_ogbn_mag.py:169) -- global-norm clip and the
+ * AdamW update of torch/optim/adamw.py (single-tensor form, amsgrad off) over all parameter tensors of a model in three launches,
+ * whatever their number.  Added under ABI 8 (new symbols only).  float32 parameters, gradients and moments.
+ *
+ * Tables.  tensors: one hgt_optim_tensor per parameter tensor, the device pointers of its p, g, exp_avg, exp_avg_sq (dense,
+ *   numel elements each), its group, its own step count (the count INCLUDING this step, >= 1) and `aligned` = all four bases are
+ *   16-byte aligned (16-byte loads and stores then, scalar ones otherwise; element i gets the same bits on either path).  A row
+ *   whose g is NULL has no gradient this step: it adds 0 to the norm and nothing of it is read or written.
+ *   groups: one hgt_optim_group per parameter group: the hyper-parameters as the doubles Python holds, maximize, and clip = the
+ *   group's tensors count in the norm and get the coefficient.  chunks: chunk c covers elements [first, min(first +
+ *   HGT_OPTIM_CHUNK, numel)) of tensor `row`; a chunk never spans two tensors, chunks are in tensor order, a tensor of 4 elements is
+ *   a chunk of its own (hgt_optim_chunk_table writes the table; it depends on the numels alone).  All three tables are DEVICE
+ *   arrays; tensors and groups may be two parts of one buffer (hgt_optim_tables_bytes gives the sizes and the offset of the groups),
+ *   so that a step needs one host-to-device copy.
+ *
+ *   hgt_optim_constants     *chunk_host = HGT_OPTIM_CHUNK as this library was built (host only; NULL: HGT_ERR_INVALID_ARG).
+ *   hgt_optim_chunk_table   host only, no device call: *n_chunks_host = the number of chunks of tensors of numel_host[0 .. n_tensors);
+ *                           with chunks_host != NULL the table is written there (capacity entries; fewer than needed:
+ *                           HGT_ERR_WORKSPACE).  A negative numel or size, NULL n_chunks_host: HGT_ERR_INVALID_ARG; more than
+ *                           INT32_MAX chunks: HGT_ERR_UNSUPPORTED.
+ *   hgt_optim_tables_bytes  step_bytes = tensors + groups in one buffer, the groups at groups_offset; chunk_bytes; partials_bytes
+ *                           (one double per chunk).
+ *   hgt_grad_sqnorm         partials[c] = the fp64 sum of g^2 over chunk c -- per thread over its quads in element order, a shuffle
+ *                           tree, then wavefront after wavefront; 0 where the row has no gradient or its group has clip == 0.
+ *                           One workgroup per chunk, no atomics.
+ *   hgt_grad_norm_join      *total_norm = (float)sqrt(sum of partials[0 .. n_chunks)), one workgroup, a fixed order (thread t adds
+ *                           partials t, t + 256, ..., then the tree of hgt_grad_sqnorm); n_chunks == 0 writes 0.
+ *   hgt_adamw_step          with total_norm != NULL: coef = min(1, max_norm / (*total_norm + 1e-6f)) in fp32 as clip_grad_norm_ forms
+ *                           it (a NaN or infinite norm gives what torch's expression gives: no special case); NULL: no clipping.
+ *                           Per element of a row with a gradient, in fp32:
+ *                             g *= coef (groups with clip);  g = -g (maximize);  p *= 1 - lr wd;  m = b1 m + (1 - b1) g;
+ *                             v = b2 v + (1 - b2) g g;  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+ *                           bc1 = 1 - b1^step, bc2 = 1 - b2^step, 1 - lr wd, lr / bc1 and sqrt(bc2) are formed in fp64 once per
+ *                           workgroup and rounded to fp32 once.  p, exp_avg and exp_avg_sq are written; g is NOT (the clipped
+ *                           gradient is never stored).  One workgroup per chunk.
+ *                           All three: no allocation, no synchronisation.  n_chunks == 0: HGT_OK without a launch (the join still
+ *                           writes its 0).  A negative size, a NULL table or fewer than one tensor or group with chunks, NULL
+ *                           partials / total_norm where written, max_norm negative or NaN with total_norm: HGT_ERR_INVALID_ARG;
+ *                           n_chunks > INT32_MAX: HGT_ERR_UNSUPPORTED; no launch.  A chunk whose row, group or first element lies
+ *                           outside the tables is skipped (its partial is 0); the pointers of a row are trusted.  The 16-byte path is taken only where
+ *                           `aligned` is set AND the chunk's first element is a multiple of 4 (always so in the table of
+ *                           hgt_optim_chunk_table); any other chunk of a caller-built table takes the scalar path.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_OPTIM_CHUNK 4096
+typedef struct hgt_optim_tensor {
+    void* p;
+    const void* g;
+    void* exp_avg;
+    void* exp_avg_sq;
+    int64_t numel;
+    int32_t group;
+    int32_t step;
+    int32_t aligned;
+    int32_t reserved[3];
+} hgt_optim_tensor;
+typedef struct hgt_optim_group {
+    double lr, beta1, beta2, eps, weight_decay;
+    int32_t maximize;
+    int32_t clip;
+    int64_t reserved[2];
+} hgt_optim_group;
+typedef struct hgt_optim_chunk {
+    int64_t first;
+    int32_t row;
+    int32_t reserved;
+} hgt_optim_chunk;
+int hgt_optim_constants(int32_t* chunk_host);
+int hgt_optim_chunk_table(const int64_t* numel_host, int32_t n_tensors, hgt_optim_chunk* chunks_host, int64_t capacity,
+                          int64_t* n_chunks_host);
+int hgt_optim_tables_bytes(int32_t n_tensors, int32_t n_groups, int64_t n_chunks, uint64_t* step_bytes_host,
+                           uint64_t* groups_offset_host, uint64_t* chunk_bytes_host, uint64_t* partials_bytes_host);
+int hgt_grad_sqnorm(const hgt_optim_tensor* tensors, int32_t n_tensors, const hgt_optim_group* groups, int32_t n_groups,
+                    const hgt_optim_chunk* chunks, int64_t n_chunks, double* partials, void* stream);
+int hgt_grad_norm_join(const double* partials, int64_t n_chunks, float* total_norm, void* stream);
+int hgt_adamw_step(const hgt_optim_tensor* tensors, int32_t n_tensors, const hgt_optim_group* groups, int32_t n_groups,
+                   const hgt_optim_chunk* chunks, int64_t n_chunks, const float* total_norm, float max_norm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,7 @@ class HgtSamplerMask(C.Structure):
 
 RANK_LIST_CAP = 1024     # HGT_RANK_LIST_CAP: positives a pass of hgt_rank_metrics holds
 CLASS_LOSS_WAVE_COLS = 256   # HGT_CLASS_LOSS_WAVE_COLS: the longest row of hgt_class_loss that takes a wavefront
+OPTIM_CHUNK = 4096          # HGT_OPTIM_CHUNK: the most elements of one tensor a workgroup of the optimizer kernels takes
 PREDICT_MAX_SPLITS = 8     # HGT_PREDICT_MAX_SPLITS: the most splits hgt_class_predict counts in one call
 ABI_VERSION = 8          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
 
@@ -265,6 +266,15 @@ SIGNATURES = {
     # stream) and (logits, ld, n_cols, ids, piece_ptr_host, n_pieces, slot_of, n_nodes, votes, ld_votes, count, n_slots, stream)
     "hgt_class_predict": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "hgt_vote_add": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp]),
+    # the optimizer step (csrc/hgt_optim.hip): (numel_host, n_tensors, chunks_host, capacity, n_chunks_host); (n_tensors, n_groups,
+    # n_chunks, step_bytes, groups_offset, chunk_bytes, partials_bytes); (tensors, n_tensors, groups, n_groups, chunks, n_chunks, partials,
+    # stream); (partials, n_chunks, total_norm, stream); (tensors .. n_chunks, total_norm, max_norm, stream)
+    "hgt_optim_constants": (C.c_int, [C.POINTER(_i32)]),
+    "hgt_optim_chunk_table": (C.c_int, [_vp, _i32, _vp, _i64, C.POINTER(_i64)]),
+    "hgt_optim_tables_bytes": (C.c_int, [_i32, _i32, _i64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "hgt_grad_sqnorm": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "hgt_grad_norm_join": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "hgt_adamw_step": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i64, _vp, C.c_float, _vp]),
 }
 
 _lib = None

@@ -11,7 +11,10 @@ the sizes above in both modes, alternating (5 warm-ups, median of 20, events on 
 hgt_mul_inplace at n = 2^28, and torch.cuda.max_memory_allocated() of a four-layer step in each mode; FILE is written as JSON.
 --stack B[,B...] [--out FILE]: instead, the sampled-size training step (c3 layer, c5 2-layer GNN; forward + backward, dropout on) on
 B stacked batches (pyhgt_amd.sampled.stack_device_graphs) against the same B batches stepped one after the other, in one process,
-alternating, medians of 5 windows: ms per piece."""
+alternating, medians of 5 windows: ms per piece.
+--optimizer {none,torch,device} (default none: the numbers above do not move): the sampled-batch steps end in an optimizer step over
+the module's parameters -- torch: clip_grad_norm_(0.5) + torch.optim.AdamW; device: pyhgt_amd.AdamW(max_norm=0.5) -- so that three runs
+give the share of a step the optimizer is (tools/bench_optimizer.py times the optimizer step alone)."""
 import json
 import os
 import sys
@@ -57,6 +60,19 @@ def minimal_backward_bytes(N, E, d, H):
 
 
 DETERMINISTIC = "--deterministic" in sys.argv or os.environ.get("HGT_TRAIN_DETERMINISTIC", "0") not in ("", "0")
+OPTIMIZER = sys.argv[sys.argv.index("--optimizer") + 1] if "--optimizer" in sys.argv else "none"
+assert OPTIMIZER in ("none", "torch", "device"), "--optimizer {none,torch,device}"
+
+
+def optimizer_step(params):
+    """the call that ends a step under --optimizer (None: the gradients are dropped, as before)"""
+    if OPTIMIZER == "none":
+        return None
+    if OPTIMIZER == "torch":
+        opt = torch.optim.AdamW(params, lr=1e-3)
+        return lambda: (torch.nn.utils.clip_grad_norm_(params, 0.5), opt.step())
+    import pyhgt_amd
+    return pyhgt_amd.AdamW(params, lr=1e-3, max_norm=0.5).step
 
 
 def sampled_batches(dev):
@@ -66,13 +82,16 @@ def sampled_batches(dev):
     from pyhgt_amd.sampled import synthetic_sampled_batch, to_torch_layout
     res = {}
 
-    def step_us(fn, params, iters=30):
+    def step_us(fn, params, module, iters=30):
+        opt_step = optimizer_step(list(module.parameters()))
         for it in range(5 + iters):
             if it == 5:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
             out = fn()
             out.backward(torch.ones_like(out))
+            if opt_step is not None:
+                opt_step()
             for p_ in params:
                 p_.grad = None
         torch.cuda.synchronize()
@@ -84,7 +103,7 @@ def sampled_batches(dev):
     plan = GraphPlan(nt, ei, et, tm, 4, len(ed))
     xg = x.clone().requires_grad_(True)
     res["c3_layer"] = {"N": int(nt.numel()), "E": int(et.numel()), "d": 256,
-                       "fwd_bwd_us": step_us(lambda: layer(xg, nt, ei, et, tm, plan=plan), list(layer.parameters()) + [xg])}
+                       "fwd_bwd_us": step_us(lambda: layer(xg, nt, ei, et, tm, plan=plan), list(layer.parameters()) + [xg], module=layer)}
     for key, c in (("c5_gnn2", dict(schema="oag", n_seed=256, width=128, depth=6, feat_dim=1169, mean_degree=1.2, seed=5, in_dim=1169, n_hid=400,
                                     T=5, H=8, L=2, norm=False)),
                    ("mag4_gnn4", dict(schema="mag", n_seed=128, width=128, depth=6, feat_dim=129, mean_degree=4.0, seed=3, in_dim=129, n_hid=512,
@@ -94,7 +113,8 @@ def sampled_batches(dev):
         x, nt, tm, ei, et, _, ed = [t.to(dev) if torch.is_tensor(t) else t for t in to_torch_layout(*batch)]
         gnn = GNN(c["in_dim"], c["n_hid"], c["T"], len(ed), c["H"], c["L"], 0.2, "hgt", c["norm"], c["norm"], True, deterministic=DETERMINISTIC).to(dev).train()
         res[key] = {"N": int(nt.numel()), "E": int(et.numel()), "n_hid": c["n_hid"], "layers": c["L"],
-                    "fwd_bwd_us": step_us(lambda: gnn(x, nt, tm, ei, et), list(gnn.parameters()))}
+                    "fwd_bwd_us": step_us(lambda: gnn(x, nt, tm, ei, et), list(gnn.parameters()), module=gnn)}
+    res["optimizer"] = OPTIMIZER
     return res
 
 

@@ -9,6 +9,7 @@ cp $G/prof_$TAG/${TAG}_kernel_stats.csv $G/prof_$TAG/${TAG}_pmc_per_kernel.csv $
 tail -1 $G/${TAG}_bench.json | python -c "import json,sys; print(json.dumps(json.loads(sys.stdin.read()), indent=1))" > $P/${TAG}_bench_line.json
 cp $G/${TAG}_latency_*.txt $P/
 cp $G/${TAG}_train_line.json $G/${TAG}_train_kernel_stats.txt $P/ 2>/dev/null || true
+cp $G/${TAG}_optimizer_step.json $P/ 2>/dev/null || true      # tools/bench_optimizer.py --out $G/${TAG}_optimizer_step.json
 python - $TAG $G <<'PY'
 import json, sys, glob, os
 tag, out_dir = sys.argv[1], sys.argv[2]
