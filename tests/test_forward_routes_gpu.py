@@ -11,7 +11,11 @@ The route cannot be read back from the library.  Where the expected form and its
 two calls, fused against unfused, item-parallel against sub-tile) the case also runs with the flags that force the expected form
 and requires the default output to equal it bit for bit.  That proves nothing about lines between forms that are bit-identical or
 have no forcing flag (targets per wavefront of the merge+update and sub-tile kernels, edges per work item): there the predicate
-comes from the sources alone and the check is the fp64 comparison."""
+comes from the sources alone and the check is the fp64 comparison.
+
+The logits kernel has a line of its own: hgt_edge_logits_kside from 64-edge work items on, where it covers the layer (`logits` is one
+of "kside" | "mfma" | "valu").  It rounds differently from the target-side kernels, so the cases that keep the attention weights
+run with it forced on and off as well and the default weights must carry the bits of the kernel the route names."""
 import os
 import re
 import time
@@ -55,6 +59,10 @@ RESTATED = dict(
     SUB_FULL_NODES=65536,           # hgt_edge_agg_mfma.hip launch_agg_mfma: sub = NQ < 65536 ? (small ? HGT_SMALL_SUB : 4) : HGT_SUB
     SMALL_SUB_NODES=6144, SMALL_SUB_MAX_R=16, MID_SUB=4,
     VALU_SUB_FULL_NODES=65536, VALU_MID_SUB=4,      # hgt_edge_agg_valu.hip LaunchAggregate: sub = NQ < 65536 ? 4 : HGT_SUB
+    KSIDE_MIN_ITEM=64,              # hgt_api.hip route(): hgt_edge_logits_kside by default from 64-edge work items on
+    KSIDE_TABLE_LOG2=32,            # hgt_api.hip route(): ... with every Q / K row below 1 << 32 bytes from its base
+    KSIDE_DK=32,                    # hgt_kside_map.h HGT_KSIDE_DK: the padded head width that kernel covers
+    KSIDE_HEADS_A=2, KSIDE_HEADS_B=4, KSIDE_HEADS_C=8,      # hgt_edge_logits_kside.hip kside_layout: one head group of such heads
 )
 
 _SOURCE_PATTERNS = [
@@ -70,6 +78,15 @@ _SOURCE_PATTERNS = [
     ("hgt_api.hip", r"fuse_update = !dense && split && \(dout <= (\d+) \|\| \(dout <= (\d+) && dp <= (\d+)\)\)",
      ["UPDATE_FUSED_DOUT", "UPDATE_WIDE_DOUT", "UPDATE_WIDE_DP"]),
     ("hgt_api.hip", r"stage != 4 && \(dkp >= (\d+) \|\| \(fl & HGT_FLAG_MFMA_LOGITS\)\)", ["MFMA_LOGITS_MIN_DKP"]),
+    # (whole statements: _forward_route restates the covered set and the flag rule, so a term added or dropped is an error here)
+    ("hgt_api.hip", r"const bool kside_covered = have_kside && split && !a->use_rte && stage != 4 &&\s*"
+                    r"\(uint64_t\)N \* \(uint64_t\)H \* \(uint64_t\)dkp \* 4u < \(1ull << (\d+)\);", ["KSIDE_TABLE_LOG2"]),
+    ("hgt_api.hip", r"const bool kside = kside_covered && !\(fl & HGT_FLAG_NO_KSIDE_LOGITS\) &&\s*"
+                    r"\(\(fl & HGT_FLAG_KSIDE_LOGITS\) \|\| \(hgt_item_edges\(E\) >= (\d+) && "
+                    r"!\(fl & \(HGT_FLAG_MFMA_LOGITS \| HGT_FLAG_VALU_LOGITS\)\)\)\);", ["KSIDE_MIN_ITEM"]),
+    ("hgt_kside_map.h", r"constexpr int HGT_KSIDE_DK = (\d+);", ["KSIDE_DK"]),
+    ("hgt_edge_logits_kside.hip", r"static bool kside_layout\(int32_t H, int32_t dk_pad\) \{ return dk_pad == HGT_KSIDE_DK && "
+                                  r"\(H == (\d+) \|\| H == (\d+) \|\| H == (\d+)\); \}", ["KSIDE_HEADS_A", "KSIDE_HEADS_B", "KSIDE_HEADS_C"]),
     ("hgt_edge_agg_items.hip", r"R >= (\d+) \|\| d % 64 != 0 \|\| d / 64 > (\d+)\) return HGT_ERR_UNSUPPORTED", [None, "ITEM_MAX_VF"]),
     ("hgt_edge_agg_items.hip", r"const int tpw = NQ <= ([\d *+]+) \? 1 : 2;", ["TPW1_MAX_TARGETS"]),
     ("hgt_edge_agg_items.hip", r"if constexpr \(G::DKP >= (\d+) && G::NCT % 4 == 0 && \(G::NCT / 4\) \* G::NKS <= 8\) \{\s*"
@@ -107,7 +124,7 @@ def _source_constants():
     """The constants of the route as the sources state them today.  A line that no longer matches its pattern is an error: the
     restated route below has to be revisited together with it."""
     if not _SOURCE_CACHE:
-        text = {}
+        text, consts = {}, {}
         for fname, pat, names in _SOURCE_PATTERNS:
             if fname not in text:
                 with open(os.path.join(CSRC, fname)) as f:
@@ -117,7 +134,8 @@ def _source_constants():
             vals = found[0] if isinstance(found[0], tuple) else (found[0],)
             for name, v in zip(names, vals):
                 if name is not None:
-                    _SOURCE_CACHE[name] = _int_expr(v)
+                    consts[name] = _int_expr(v)
+        _SOURCE_CACHE.update(consts)          # (only a complete set: every test that needs it repeats the error of a line that moved)
     return dict(_SOURCE_CACHE)
 
 
@@ -181,9 +199,9 @@ def _shared_transform(vec, lph, item_edges, min_dkp, max_item, flags):
 LOGITS_MFMA_LAYOUTS = {(4, 8), (4, 16), (4, 32), (4, 64), (2, 32), (2, 64), (1, 64)}      # hgt_launch_logits_mfma: LGM_CASE
 
 
-def _forward_route(N, NQ, E, d, H, R, precision, dense=False, flags=0, item_scratch=None, K=None):
+def _forward_route(N, NQ, E, d, H, R, precision, dense=False, flags=0, item_scratch=None, K=None, use_rte=False):
     """What Conv::route() and the kernels' own dispatch decide for a whole-layer call (stage 0, in_dim == out_dim == d, d % 4 == 0,
-    hubs possible).  item_scratch: the workspace holds the item-parallel scratch if the library grants it -- None: what
+    hubs possible).  use_rte: the layer has a temporal encoding (only the logits kernel depends on it).  item_scratch: the workspace holds the item-parallel scratch if the library grants it -- None: what
     HGTConv.forward asks for with its own workspace (split precision and no HGT_FLAG_NO_ITEM_AGGREGATE); False: a caller-owned
     workspace of workspace_bytes(staged=True).  Returns the forms that ANSWER (a form that returns HGT_ERR_UNSUPPORTED hands over
     to the next one; `tried` lists them in order)."""
@@ -203,8 +221,15 @@ def _forward_route(N, NQ, E, d, H, R, precision, dense=False, flags=0, item_scra
     # logits
     mfma_logits = have_frags and not (flags & F.HGT_FLAG_VALU_LOGITS) and (dkp >= K["MFMA_LOGITS_MIN_DKP"] or bool(flags & F.HGT_FLAG_MFMA_LOGITS))
     mfma_logits = mfma_logits and (vec_s, lph_s) in LOGITS_MFMA_LAYOUTS         # (else hgt_launch_logits_mfma hands over)
-    r["logits"] = "mfma" if mfma_logits else "valu"
-    r["logits_shared"] = mfma_logits and _shared_transform(vec_s, lph_s, ie, K["LOGITS_SHARED_MIN_DKP"], K["LOGITS_SHARED_MAX_ITEM"], flags)
+    # ... on the source side, per edge (hgt_edge_logits_kside), where that kernel is covered and, by default, the items are long enough
+    kside_covered = (split and dkp == K["KSIDE_DK"] and heads in (K["KSIDE_HEADS_A"], K["KSIDE_HEADS_B"], K["KSIDE_HEADS_C"]) and
+                     not use_rte and N * heads * dkp * 4 < (1 << K["KSIDE_TABLE_LOG2"]))
+    kside = (kside_covered and not (flags & F.HGT_FLAG_NO_KSIDE_LOGITS) and
+             (bool(flags & F.HGT_FLAG_KSIDE_LOGITS) or
+              (ie >= K["KSIDE_MIN_ITEM"] and not (flags & (F.HGT_FLAG_MFMA_LOGITS | F.HGT_FLAG_VALU_LOGITS)))))
+    r["kside_covered"] = kside_covered
+    r["logits"] = "kside" if kside else "mfma" if mfma_logits else "valu"
+    r["logits_shared"] = mfma_logits and not kside and _shared_transform(vec_s, lph_s, ie, K["LOGITS_SHARED_MIN_DKP"], K["LOGITS_SHARED_MAX_ITEM"], flags)
     # the scratch of the item-parallel form: sized from N (conv_workspace), part of the workspace only if the caller sized it in
     scratch = _item_scratch_bytes(E, heads, dkp)
     r["item_scratch_bytes"] = scratch
@@ -324,12 +349,43 @@ HAND_ROWS = [
     ((3000, 3000, 30000, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_MFMA_LOGITS, None), dict(logits="mfma", logits_shared=False)),
     # one head of 512 columns: no matrix-core edge kernel covers it (mfma_split_for == 0)
     ((3000, 3000, 30000, 512, 1, 4, "bf16x3", False, 0, None), dict(logits="valu", tried=["subtile"], agg_kernel="valu", sub=4, update="linear_fused")),
+    # the K-side logits kernel (an eleventh entry: use_rte).  hgt_item_edges(262 144) = 64 is its default line at 32-column heads
+    ((12000, 12000, 262143, 256, 8, 8, "bf16x3", False, 0, None), dict(logits="valu", kside_covered=True, item_edges=32, dkp=32)),
+    ((12000, 12000, 262144, 256, 8, 8, "bf16x3", False, 0, None), dict(logits="kside", kside_covered=True, item_edges=64, logits_shared=False)),
+    ((12000, 12000, 262144, 256, 8, 8, "f16x3", False, 0, None), dict(logits="kside", item_edges=64)),
+    ((12000, 12000, 262143, 256, 8, 8, "bf16x3", False, 0, None, True), dict(logits="valu", kside_covered=False, item_edges=32)),
+    ((12000, 12000, 262144, 256, 8, 8, "bf16x3", False, 0, None, True), dict(logits="valu", kside_covered=False, item_edges=64)),
+    ((12000, 12000, 262143, 256, 8, 8, "fp32", False, 0, None), dict(logits="valu", kside_covered=False)),
+    ((12000, 12000, 262144, 256, 8, 8, "fp32", False, 0, None), dict(logits="valu", kside_covered=False, item_edges=64)),
+    ((12000, 12000, 262144, 512, 16, 8, "bf16x3", False, 0, None), dict(logits="valu", kside_covered=False, dkp=32, dp=512)),      # 16 heads
+    ((12000, 12000, 262144, 128, 8, 8, "bf16x3", False, 0, None), dict(logits="valu", kside_covered=False, dkp=16)),
+    ((12000, 12000, 262144, 512, 8, 9, "bf16x3", False, 0, None), dict(logits="mfma", kside_covered=False, dkp=64)),
+    ((12000, 12000, 262144, 96, 3, 8, "bf16x3", False, 0, None), dict(logits="kside", kside_covered=True, dkp=32, dp=128)),          # 3 heads run as 4
+    ((12000, 12000, 262144, 64, 2, 8, "f16x3", False, 0, None), dict(logits="kside", dkp=32, dp=64)),
+    ((12000, 12000, 262144, 128, 4, 8, "f16x3", False, 0, None), dict(logits="kside", dkp=32, dp=128)),
+    # rows of 1024 bytes: node 4 194 304 would start 4 GiB from the base (route rows only: nothing this large is allocated)
+    ((4194303, 4194303, 41943030, 256, 8, 8, "bf16x3", False, 0, None), dict(logits="kside", kside_covered=True, item_edges=512)),
+    ((4194304, 4194304, 41943040, 256, 8, 8, "bf16x3", False, 0, None), dict(logits="valu", kside_covered=False, item_edges=512)),
+    ((3000, 3000, 30000, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_KSIDE_LOGITS, None), dict(logits="kside", item_edges=16)),
+    ((3000, 3000, 30000, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_KSIDE_LOGITS | FL.HGT_FLAG_VALU_LOGITS, None), dict(logits="kside")),
+    ((3000, 3000, 30000, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_KSIDE_LOGITS | FL.HGT_FLAG_MFMA_LOGITS, None), dict(logits="kside", logits_shared=False)),
+    ((3000, 3000, 30000, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_KSIDE_LOGITS, None, True), dict(logits="valu")),
+    ((3000, 3000, 30000, 256, 8, 8, "fp32", False, FL.HGT_FLAG_KSIDE_LOGITS, None), dict(logits="valu")),
+    ((12000, 12000, 262144, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_MFMA_LOGITS, None), dict(logits="mfma", item_edges=64)),
+    ((12000, 12000, 262144, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_VALU_LOGITS, None), dict(logits="valu")),
+    ((12000, 12000, 262144, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_NO_KSIDE_LOGITS, None), dict(logits="valu", kside_covered=True)),
+    ((12000, 12000, 262144, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_NO_KSIDE_LOGITS | FL.HGT_FLAG_KSIDE_LOGITS, None), dict(logits="valu")),
+    ((12000, 12000, 262144, 256, 8, 8, "bf16x3", False, FL.HGT_FLAG_NO_KSIDE_LOGITS | FL.HGT_FLAG_MFMA_LOGITS, None), dict(logits="mfma")),
 ]
 
 
-@pytest.mark.parametrize("args,expect", HAND_ROWS, ids=["%d-%d-%d-d%d-h%d-r%d-%s-%s-f%d-%s" % a for a, _ in HAND_ROWS])
+def _hand_row_id(a):
+    return "%d-%d-%d-d%d-h%d-r%d-%s-%s-f%d-%s" % a[:10] + ("-rte" if len(a) > 10 and a[10] else "")
+
+
+@pytest.mark.parametrize("args,expect", HAND_ROWS, ids=[_hand_row_id(a) for a, _ in HAND_ROWS])
 def test_forward_route_against_hand_derived_rows(args, expect):
-    r = _forward_route(*args)
+    r = _forward_route(*args[:10], use_rte=len(args) > 10 and args[10])
     for k, v in expect.items():
         assert r[k] == v, (k, r)
 
@@ -362,8 +418,8 @@ def _build_cases():
     cs.append(_case("fused-16384-d64", 16384, 64, 4, dict(agg="fused", agg_kernel="mfma", tried=["fused"]), line=16384, T=3, R=4))
     cs.append(_case("fused-16384-d512", 16384, 512, 8, dict(agg="items_update", tpw=2, tried=["items_update"], logits="mfma"), line=16384, R=9))
     # the 65 536 line
-    cs.append(_case("n65535-d256", 65535, 256, 8, dict(agg="fused", item_scratch_granted=True), line=65536))
-    cs.append(_case("n65536-d256", 65536, 256, 8, dict(agg="fused", item_scratch_granted=False), line=65536))
+    cs.append(_case("n65535-d256", 65535, 256, 8, dict(agg="fused", item_scratch_granted=True, logits="kside"), line=65536))
+    cs.append(_case("n65536-d256", 65536, 256, 8, dict(agg="fused", item_scratch_granted=False, logits="valu"), line=65536))      # (temporal)
     cs.append(_case("n65535-d768", 65535, 768, 8, dict(tried=["subtile"], agg_kernel="mfma", sub=4, update="linear_node", dp=1024),
                     line=65536, T=3, R=5))
     cs.append(_case("n65536-d768", 65536, 768, 8, dict(tried=["subtile"], agg_kernel="mfma", sub=16, update="linear_node", dp=1024),
@@ -382,9 +438,10 @@ def _build_cases():
     for d in (256, 512):
         L = _layout(d, 8)
         e = _scratch_gate_edges(L["heads"], L["dkp"], K)
-        cs.append(_case("gate-under-d%d" % d, 12000, d, 8, dict(agg="items_update", tpw=2, item_scratch_granted=True), E=e, R=9 if d == 512 else 8))
+        cs.append(_case("gate-under-d%d" % d, 12000, d, 8, dict(agg="items_update", tpw=2, item_scratch_granted=True, logits="valu" if d == 256 else "mfma"), E=e, R=9 if d == 512 else 8))      # (temporal)
         cs.append(_case("gate-over-d%d" % d, 12000, d, 8, dict(tried=["subtile"], agg_kernel="mfma", sub=4, update="linear_fused",
-                                                              item_scratch_granted=False), E=e + 1, R=9 if d == 512 else 8))
+                                                              item_scratch_granted=False, logits="kside" if d == 256 else "mfma"),
+                        E=e + 1, R=9 if d == 512 else 8))
     cs.append(_case("r63-n3000", 3000, 256, 8, dict(agg="items_update", tpw=1), T=3, R=63))
     cs.append(_case("r64-n3000", 3000, 256, 8, dict(tried=["subtile"], agg_kernel="mfma", sub=4, update="linear_fused"), T=3, R=64))
     cs.append(_case("halo-n60000-q10000", 60000, 256, 8, dict(agg="items_update", tpw=2, qkv_launches=2, item_scratch_granted=True), NQ=10000))
@@ -398,9 +455,10 @@ def _build_cases():
     cs.append(_case("halo-n40000-q16384", 40000, 256, 8, dict(agg="fused", qkv_launches=2), NQ=16384, line=16384))
     # DenseHGTConv
     for d in (256, 400):
-        cs.append(_case("dense-n20000-d%d" % d, 20000, d, 8, dict(tried=["items"], update="dense"), dense=True, T=5 if d == 400 else 4, R=9))
-        cs.append(_case("dense-n66000-d%d" % d, 66000, d, 8, dict(tried=["subtile"], agg_kernel="mfma", sub=16, update="dense"), dense=True,
-                        T=5 if d == 400 else 4, R=9))
+        cs.append(_case("dense-n20000-d%d" % d, 20000, d, 8, dict(tried=["items"], update="dense", logits="valu" if d == 256 else "mfma"),
+                        dense=True, T=5 if d == 400 else 4, R=9))      # (temporal)
+        cs.append(_case("dense-n66000-d%d" % d, 66000, d, 8, dict(tried=["subtile"], agg_kernel="mfma", sub=16, update="dense",
+                                                                 logits="kside" if d == 256 else "mfma"), dense=True, T=5 if d == 400 else 4, R=9))
     # exact fp32: the vector-ALU sub-tile kernel has the same 65 536 line
     cs.append(_case("fp32-n65535-d64", 65535, 64, 4, dict(tried=["subtile"], agg_kernel="valu", sub=4, update="linear_node"), line=65536,
                     T=3, R=4, precisions=("fp32",)))
@@ -410,6 +468,21 @@ def _build_cases():
         if c["E"] is None:
             c["E"] = 10 * c["NQ"]               # about ten in-edges per target
         c["use_norm"], c["use_rte"], c["keep_att"], c["strided"] = i % 3 != 1, i % 2 == 0, i % 3 == 0 or c["line"] in (16384, 65536), i % 2 == 1
+    # The lines of the K-side logits kernel (hgt_edge_logits_kside), appended behind the loop so that the index-derived switches of the
+    # cases above stay what they were: 64-edge items (E = 262 144) at every head count it covers, and what it does not cover.  Every
+    # one keeps the attention weights: the GPU test reads the logits kernel off their bits.
+    n_old = len(cs)
+    ks = dict(E=262144, T=3, R=4)
+    cs.append(_case("kside-e262143-d256", 12000, 256, 8, dict(logits="valu", kside_covered=True, item_edges=32), E=262143, T=3, R=4))
+    cs.append(_case("kside-e262144-d256", 12000, 256, 8, dict(logits="kside", item_edges=64), **ks))
+    cs.append(_case("kside-e262144-d256-rte", 12000, 256, 8, dict(logits="valu", kside_covered=False, item_edges=64), **ks))
+    cs.append(_case("kside-e262144-d64-h2", 12000, 64, 2, dict(logits="kside", item_edges=64, dkp=32), **ks))
+    cs.append(_case("kside-e262144-d128-h4", 12000, 128, 4, dict(logits="kside", item_edges=64, dkp=32), **ks))
+    cs.append(_case("kside-e262144-d96-h3", 12000, 96, 3, dict(logits="kside", item_edges=64, dkp=32), **ks))
+    cs.append(_case("kside-e262144-d128-h8", 12000, 128, 8, dict(logits="valu", kside_covered=False, item_edges=64, dkp=16), **ks))
+    cs.append(_case("kside-e262144-d256-fp32", 12000, 256, 8, dict(logits="valu", kside_covered=False, item_edges=64), precisions=("fp32",), **ks))
+    for i, c in enumerate(cs[n_old:]):
+        c["use_norm"], c["use_rte"], c["keep_att"], c["strided"], c["logits_bits"] = i % 3 != 1, c["id"].endswith("-rte"), True, i % 2 == 1, True
     return cs
 
 
@@ -418,7 +491,8 @@ CASE_PARAMS = [pytest.param(c, p, id="%s-%s" % (c["id"], p)) for c in CASES for 
 
 
 def _case_route(c, precision, flags=0):
-    return _forward_route(c["N"], c["NQ"], c["E"], c["d"], c["H"], c["R"], precision, c["dense"], flags, False if c["own_ws"] else None)
+    return _forward_route(c["N"], c["NQ"], c["E"], c["d"], c["H"], c["R"], precision, c["dense"], flags, False if c["own_ws"] else None,
+                          use_rte=c["use_rte"])
 
 
 @pytest.mark.parametrize("c,precision", CASE_PARAMS)
@@ -506,7 +580,10 @@ def test_forward_route_case_against_fp64(c, precision):
     """One case of the list ("size line -> kernel on each side"): default flags, output of ~2000
     check rows against the fp64 closed form within PREC_TOL, attention weights of all their in-edges within 1e-5 (keep_att cases),
     rows of unknown type exactly 0, a second forward bit-identical outside the hub rows, and the default output bit-identical to
-    the run that forces the expected form (all rows with HGT_FLAG_DETERMINISTIC_HUBS on both, non-hub rows without)."""
+    the run that forces the expected form (all rows with HGT_FLAG_DETERMINISTIC_HUBS on both, non-hub rows without).  Cases with
+    32-column heads that keep the attention weights, and the K-side cases, also run with the K-side logits kernel forced on and
+    off: the default weights equal, bit for bit, the run of the kernel the route names, the two forced runs differ where the
+    kernel covers the layer and are identical where it does not."""
     if HGTConv.EXTRA_KERNEL_FLAGS:
         pytest.skip("a forced-kernel pass of the suite puts one kernel on every layer: the default route under test does not run")
     t0 = time.time()
@@ -573,6 +650,19 @@ def test_forward_route_case_against_fp64(c, precision):
         err_det = (det[tg].double() - ref).abs().max().item()
         print("  forced %s (flags %d): %d non-hub rows differ from the default run; with deterministic hubs %d rows differ, max|err| %.2e"
               % (route["agg"], ff, n_diff, n_diff_det, err_det))
+    # the logits kernel, read off the bits of the attention weights: hgt_edge_logits_kside rounds differently from the target-side
+    # kernels, so on a layer it covers the two forced runs differ and the default run equals the one the route names; on a layer it
+    # does not cover both flags are ignored.  (The forcing flags of the aggregation above name no logits kernel.)
+    n_att_diff, att_runs = -1, None
+    if c["keep_att"] and (route["dkp"] == K["KSIDE_DK"] or c.get("logits_bits")):
+        det_fl = _lib.HGT_FLAG_DETERMINISTIC_HUBS
+        att_runs = []
+        for fl in (det_fl, det_fl | _lib.HGT_FLAG_KSIDE_LOGITS, det_fl | _lib.HGT_FLAG_NO_KSIDE_LOGITS):
+            _forward(layer, g, fl, ws_det)
+            att_runs.append(layer.att.view(torch.int32))
+        n_att_diff = int((att_runs[1] != att_runs[2]).sum())
+        print("  logits %s (covered by the K-side kernel: %s): %d of %d attention weights differ between the runs forced to it and off it"
+              % (route["logits"], route["kside_covered"], n_att_diff, att_runs[1].numel()))
     print("  %.3f s" % (time.time() - t0))
     GraphPlan.clear_cache()
     assert err < PREC_TOL[precision]
@@ -584,3 +674,13 @@ def test_forward_route_case_against_fp64(c, precision):
         assert n_diff == 0, "the default route is not the expected form %s: %d rows differ from the forced run" % (route["agg"], n_diff)
         assert n_diff_det == 0
         assert err_det < PREC_TOL[precision]
+    if att_runs is not None:
+        assert route["logits"] in ("kside", "valu")
+        want = att_runs[1] if route["logits"] == "kside" else att_runs[2]
+        assert torch.equal(att_runs[0], want), "the default route's logits kernel is not %s" % route["logits"]
+        not_hub = ~hub_rows[g["ei"][1]]         # (without deterministic hubs: every edge into a non-hub row)
+        assert torch.equal(att.view(torch.int32)[not_hub], want[not_hub]), "the default run's logits kernel is not %s" % route["logits"]
+        if route["kside_covered"]:
+            assert n_att_diff > 0, "the forced runs are bit-identical: the comparison says nothing about the logits kernel"
+        else:
+            assert n_att_diff == 0 and torch.equal(att_runs[0], att_runs[1])

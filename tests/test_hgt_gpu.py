@@ -1780,7 +1780,8 @@ def test_plan_cache_and_weight_cache_follow_in_place_edits():
 
 def test_prepared_images_survive_a_change_of_kernel_flags():
     """Round-3 advisor finding: the fragment images of the prepared buffer were only written when the FIRST forward's flags selected
-    the kernels that read them; a later flag change on the live layer then read uninitialised memory.  Every order must work."""
+    the kernels that read them; a later flag change on the live layer then read uninitialised memory.  Every order must work -- with
+    temporal encoding (the fragment images) and without it (the image of the K-side logits kernel, which no temporal layer reads)."""
     T, R, H, d, N, E = 3, 4, 8, 256, 3000, 30000
     sd = O.make_state_dict(d, d, T, R, H, True, True, seed=9)
     x, nt, ei, et, tm = synthetic_typed_graph(N, E, d, T, R, seed=10)
@@ -1798,6 +1799,22 @@ def test_prepared_images_survive_a_change_of_kernel_flags():
                 with torch.no_grad():
                     out = layer(*args)
                 assert (out.cpu().double() - ref).abs().max().item() < TOL, (precision, order, fl)
+    # ... and the image of hgt_edge_logits_kside, which only a layer without temporal encoding reads: written by a first forward that
+    # does not take that kernel, read by a later one that does, and the other way round
+    sd = O.make_state_dict(d, d, T, R, H, True, False, seed=11)
+    ref = O.forward_closed_form(sd, T, R, H, x, nt, ei, et, None, use_RTE=False)
+    args = _to_dev(x, nt, ei, et, tm)[:4]
+    orders = [(F.HGT_FLAG_NO_KSIDE_LOGITS, F.HGT_FLAG_KSIDE_LOGITS), (F.HGT_FLAG_VALU_LOGITS, F.HGT_FLAG_KSIDE_LOGITS, 0),
+              (F.HGT_FLAG_KSIDE_LOGITS, F.HGT_FLAG_MFMA_LOGITS, F.HGT_FLAG_NO_KSIDE_LOGITS)]
+    for precision in ("bf16x3", "f16x3"):
+        for order in orders:
+            layer = _layer_from(sd, d, T, R, H, True, False, keep_att=False, precision=precision)
+            GraphPlan.clear_cache()
+            for fl in order:
+                layer.kernel_flags = fl
+                with torch.no_grad():
+                    out = layer(*args)
+                assert (out.cpu().double() - ref).abs().max().item() < TOL, ("no temporal encoding", precision, order, fl)
 
 
 @pytest.mark.parametrize("precision,flags", [("bf16x3", 0), ("f16x3", 0), ("bf16x3", _lib.HGT_FLAG_NO_FUSED_UPDATE), ("fp32", 0)])

@@ -1,7 +1,19 @@
 """hgt_edge_logits_kside: attention logits with the relation transform applied to the K row of every edge on the matrix cores
 (csrc/hgt_edge_logits_kside.hip).  Whole layers with the kernel forced (kernel_flags = 65536) against the fp64 closed form on
 every batch shape it has -- ragged, full, double-buffered, padded d_k, padded heads, a single edge, no edge --, its scale rule at
-extreme magnitudes, bit-reproducibility, and the shapes it does not cover."""
+extreme magnitudes, bit-reproducibility, and the shapes it does not cover.
+
+The kernel's own edges go through the entry point (hgt_edge_logits_kside) at H = 2, 4 and 8, on the input sets of
+test_kside_scale_rule.py (which shows, without a GPU, that the quantisation of the scale rule alone stays below half the bound on
+each of them: 0.002 .. 0.010 of it).  Bound everywhere: |error| <= 2^-17 sum |q| |A'| |k| per (edge, head), plus 2^-149 where the
+fp64 logit is below fp32's normal range.  Measured worst error / bound on an MI355X:
+  uniform magnitudes, x * 2^0 / 2^20 / 2^-20 (H = 8, 32-edge items)                       0.006 / 0.005 / 0.006
+  uneven rows (exponents per row and block, zero / half / dominant / subnormal rows),
+    64-edge items, H = 2 / 4 / 8, logits in fp32's normal range                           0.012 / 0.020 / 0.021
+    ... logits that round to fp32 subnormals (half a step of 2^-149 against the 2^-149)   0.498 / 0.492 / 0.498
+  512-edge items, 16 batches per item (H = 8, E = 2 097 152)                              0.0059
+  rows 2.25 GB from the base of Q and K (N = 2 200 000), and the same graph on 8192 rows  0.0050, bit-identical
+One inf in K and one NaN in Q make exactly the 1766 logits of their (edges, head) non-finite; the others keep their bits."""
 import ctypes as C
 
 import pytest
@@ -10,6 +22,7 @@ import torch
 from oracle import hgt_oracle as O
 from pyhgt_amd import HGTConv, GraphPlan, _lib
 from pyhgt_amd.synth import synthetic_typed_graph
+import test_kside_scale_rule as S
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -102,28 +115,24 @@ def test_edgeless_graph(precision):
 
 
 # ------------------------------------------------------------------ the entry point itself
-def _direct_setup(N, E, d, H, T, R, x_scale, seed):
+def _direct_setup(N, E, d, H, T, R, x_scale, seed, inputs=None):
     """Q, K (fp64 typed linears of x * x_scale, rounded to fp32: LayerNorm plays no part), the packed relation matrices and the plan
-    of a graph with unclaimed edges, on the device; d_k = 32 and H a power of two (no padding anywhere)."""
+    of a graph with unclaimed edges, on the device; d_k = 32 and H in {2, 4, 8} (no padding anywhere).  inputs: an input set of
+    test_kside_scale_rule.py instead -- its Q and K as they are (edited rows and all; tensors on either device), its edits of
+    att_t applied to what hgt_relation_pack wrote, in front of hgt_relation_kside_pack; N may exceed the set's rows if Q / K do."""
     lib = _lib.load()
     dk = d // H
-    assert dk == 32
-    sd = O.make_state_dict(d, d, T, R, H, False, False, seed=seed)
-    x, nt, ei, et, tm = synthetic_typed_graph(N, E, d, T, R, seed=seed + 1)
-    et = et.clone()
-    et[::41] = R
-    xs = x.double() * x_scale
-    Q = torch.zeros(N, d, dtype=torch.float64)
-    K = torch.zeros(N, d, dtype=torch.float64)
-    for t in range(T):
-        m = nt == t
-        Q[m] = xs[m] @ sd["q_linears.%d.weight" % t].double().T + sd["q_linears.%d.bias" % t].double()
-        K[m] = xs[m] @ sd["k_linears.%d.weight" % t].double().T + sd["k_linears.%d.bias" % t].double()
-    Qd, Kd = Q.float().to(DEV).contiguous(), K.float().to(DEV).contiguous()
+    assert dk == 32 and H in (2, 4, 8)
+    inp = inputs if inputs is not None else S.plain_inputs(N, E, H, T, R, seed, x_scale)
+    assert (inp["E"], inp["H"], inp["T"], inp["R"]) == (E, H, T, R)
+    sd, nt, ei, et = inp["sd"], inp["nt"], inp["ei"], inp["et"]
+    Qd, Kd = inp["Q"].to(DEV).contiguous(), inp["K"].to(DEV).contiguous()
+    assert Qd.shape == (N, d) and Kd.shape == (N, d) and Qd.dtype == torch.float32 and nt.numel() == N and int(ei.max()) < N
     ra, rm, rp = (sd[k].float().to(DEV).contiguous() for k in ("relation_att", "relation_msg", "relation_pri"))
     att_t = torch.empty(R * H * dk * dk, dtype=torch.float32, device=DEV)
     msg_p = torch.empty_like(att_t)
     assert lib.hgt_relation_pack(ra.data_ptr(), rm.data_ptr(), rp.data_ptr(), R, H, H, dk, dk, att_t.data_ptr(), msg_p.data_ptr(), _st()) == 0
+    att_t = S.edit_att(inp, att_t.view(R, H, dk, dk)).view(-1)
     nb = C.c_uint64()
     assert lib.hgt_relation_kside_bytes(R, H, dk, C.byref(nb)) == 0 and nb.value > 0
     img = torch.empty(int(nb.value), dtype=torch.uint8, device=DEV)
@@ -145,20 +154,32 @@ def _direct_logits(s):
     return out.cpu()
 
 
-def _logits_fp64(s):
-    """fp64 logits of the kernel's own fp32 inputs, and sum |q| |A'| |k| per (edge, head): the scale of their rounding errors"""
-    E, H, R, dk = s["E"], s["H"], s["R"], s["dk"]
-    Q, K = s["Q"].cpu().double().view(-1, H, dk), s["K"].cpu().double().view(-1, H, dk)
-    A = s["att_t"].cpu().double().view(R, H, dk, dk)          # [r][h][output j][k c]
-    src, dst, et = s["ei"][0], s["ei"][1], s["et"]
-    ref = torch.zeros(E, H, dtype=torch.float64)
-    mag = torch.zeros(E, H, dtype=torch.float64)
-    for r in range(R):
-        sel = (et == r).nonzero().flatten()
-        k, q = K[src[sel]].transpose(0, 1), Q[dst[sel]].transpose(0, 1)          # [h][e][dk]
-        ref[sel] = (torch.bmm(k, A[r].transpose(1, 2)) * q).sum(-1).T
-        mag[sel] = (torch.bmm(k.abs(), A[r].abs().transpose(1, 2)) * q.abs()).sum(-1).T
-    return ref, mag
+def _logits_fp64(s, on_device=False):
+    """fp64 logits of the kernel's own fp32 inputs, and sum |q| |A'| |k| per (edge, head): the scale of their rounding errors.
+    on_device: the same float64 sums computed there (graphs of 262 144 edges and more)."""
+    Q, K = (s["Q"], s["K"]) if on_device else (s["Q"].cpu(), s["K"].cpu())
+    ref, mag = S.logits_fp64(Q, K, s["att_t"], s["ei"], s["et"], s["R"], s["H"])
+    return ref.cpu(), mag.cpu()
+
+
+def _item_edges(lib, E):
+    ce = C.c_int32()
+    assert lib.hgt_plan_item_edges(E, C.byref(ce)) == 0
+    return ce.value
+
+
+def _against_bound(got, ref, mag, what):
+    """|error| <= 2^-17 sum |q| |A'| |k| per (edge, head), plus one fp32 subnormal step where the fp64 value is below fp32's normal
+    range (the final ldexp rounds there); prints and returns the worst error / bound."""
+    err = (got.double() - ref).abs()
+    bound = 2.0 ** -17 * mag + (ref.abs() < 2.0 ** -126).double() * 2.0 ** -149
+    ratio = err / bound.clamp(min=1e-300)
+    worst = ratio.max().item()
+    normal = ref.abs() >= 2.0 ** -126
+    print("%s: worst err / bound %.4f at (edge, head) %s; %.4f over the %d logits in fp32's normal range" % (
+        what, worst, divmod(int(ratio.argmax()), got.shape[1]), ratio[normal].max().item(), int(normal.sum())))
+    assert bool((err <= bound).all()), worst
+    return worst
 
 
 @pytest.mark.parametrize("log2_scale", [0, 20, -20])
@@ -215,3 +236,104 @@ def test_entry_point_refuses_what_it_does_not_cover():
     assert lib.hgt_edge_logits_kside(*args(4, 64, None)) == UNSUPPORTED                    # d_k = 64
     assert lib.hgt_edge_logits_kside(*args(8, 32, None)) == 0
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------ the kernel's own edges (input sets: test_kside_scale_rule.py)
+@pytest.mark.parametrize("H", [2, 4, 8])
+def test_scale_rule_on_uneven_rows(H):
+    """Every (row, head) of Q and K and every (relation, head) block of att_t at an exponent of its own (2^-40 .. 2^40, blocks
+    2^-30 .. 2^30), zero rows and a zero block, rows whose halves or one element differ by 2^20 (the cross-half maximum), a
+    subnormal K row, a Q row at 2^120: 64-edge items, so every head count runs several batches per item with ragged tails (H = 4, 8:
+    the four-head pipeline).  A scale taken from the wrong operand, half or columns, or a wrong clamp, leaves the bound here; at
+    uniform magnitudes it would not."""
+    inp = S.uneven_inputs(H)
+    s = _direct_setup(inp["N"], inp["E"], 32 * H, H, inp["T"], inp["R"], 1.0, 0, inputs=inp)
+    assert _item_edges(s["lib"], s["E"]) == 64
+    n_special = S.special_edge_counts(inp)
+    assert min(n_special.values()) >= 32, n_special
+    assert torch.equal(s["att_t"].cpu().view(-1) == 0, inp["att_t"].view(-1) == 0)
+    got = _direct_logits(s)
+    assert torch.isfinite(got).all(), "inf / NaN in the logits"
+    ref, mag = _logits_fp64(s, on_device=True)
+    assert float(ref.abs().max()) < 2.0 ** 126 and float(ref.abs().max()) > 2.0 ** 60
+    _against_bound(got, ref, mag, "kside logits, uneven rows, H = %d (%s)" % (H, n_special))
+    zero = S.zero_logit_mask(inp)
+    assert int(zero.sum()) > s["E"] // 41 and bool((got[zero] == 0).all()), "logits of unclaimed edges, zero rows and the zero block must be exactly 0"
+    assert bool((got[s["et"] == s["R"]] == 0).all())
+    # the special rows one by one: their worst error / bound is reported with them
+    src, dst = s["ei"][0], s["ei"][1]
+    for name, (what, idx, h) in inp["special"].items():
+        m = ((src == idx) if what == "K" else (dst == idx) if what == "Q" else (s["et"] == idx)) & (s["et"] < s["R"])
+        e, b = (got[m, h].double() - ref[m, h]).abs(), 2.0 ** -17 * mag[m, h] + (ref[m, h].abs() < 2.0 ** -126).double() * 2.0 ** -149
+        print("   %-18s %5d edges, head %d: worst err / bound %.4f, largest |logit| %.3e" % (
+            name, int(m.sum()), h, (e / b.clamp(min=1e-300)).max().item(), ref[m, h].abs().max().item()))
+    pair = (src == 18) & (dst == 19) & (s["et"] < s["R"])
+    assert bool((ref[pair, inp["special"]["k_subnormal"][2]] != 0).any()) and bool((got[pair, inp["special"]["k_subnormal"][2]] != 0).any())
+
+
+def test_many_batches_per_item():
+    """512-edge items: 16 batches per item and wavefront -- the pipeline's steady state (pieces three steps ahead, edge indices one
+    batch further) at H = 8, as the benchmark runs it, through the entry point."""
+    inp = S.many_batches_inputs()
+    s = _direct_setup(inp["N"], inp["E"], 256, 8, inp["T"], inp["R"], 1.0, 0, inputs=inp)
+    assert _item_edges(s["lib"], s["E"]) == 512
+    got = _direct_logits(s)
+    assert torch.isfinite(got).all()
+    ref, mag = _logits_fp64(s, on_device=True)
+    _against_bound(got, ref, mag, "kside logits, 512-edge items")
+    assert float(ref.abs().max()) > 0 and bool((got[s["et"] == s["R"]] == 0).all())
+
+
+def test_non_finite_inputs_stay_where_they_are():
+    """One inf in K and one NaN in Q: exactly the logits of (edges out of that source, that head) and (edges into that target, that
+    head) are non-finite, every other logit has the bits of the run without the two values -- an edge is a column of the matrix
+    product, and a clamped or re-read row of another lane must not leak."""
+    H = 4
+    inp = S.plain_inputs(300, 270000, H, 2, 3, seed=44)
+    s = _direct_setup(inp["N"], inp["E"], 32 * H, H, inp["T"], inp["R"], 1.0, 0, inputs=inp)
+    clean = _direct_logits(s)
+    assert torch.isfinite(clean).all()
+    j, hk, i, hq = 37, 1, 211, 2
+    s["K"].view(-1, H, 32)[j, hk, 9] = float("inf")
+    s["Q"].view(-1, H, 32)[i, hq, 27] = float("nan")
+    got = _direct_logits(s)
+    claimed = s["et"] < s["R"]
+    want = torch.zeros(s["E"], H, dtype=torch.bool)
+    want[:, hk] |= (s["ei"][0] == j) & claimed
+    want[:, hq] |= (s["ei"][1] == i) & claimed
+    assert int(want[:, hk].sum()) >= 32 and int(want[:, hq].sum()) >= 32
+    bad = ~torch.isfinite(got)
+    print("non-finite inputs: %d logits expected non-finite, %d are; %d of them unexpected, %d missing"
+          % (int(want.sum()), int(bad.sum()), int((bad & ~want).sum()), int((want & ~bad).sum())))
+    assert torch.equal(bad, want)
+    assert torch.equal(got.view(torch.int32)[~want], clean.view(torch.int32)[~want])
+
+
+def test_rows_between_2_and_4_gib_from_the_base():
+    """2 200 000 rows of 1024 bytes: the last 4096 sit 2.25 GB from the bases of Q and K, where the 32-bit lane offsets and the
+    record count of the buffer descriptors have their top bit set.  60 000 edges among the first and the last 4096 rows (both
+    directions across the 2 GiB mark), bit-identical to the same graph renumbered onto 8192 rows, and within the bound."""
+    if torch.cuda.get_device_properties(0).total_memory < 16 << 30:
+        pytest.skip("two tables of 2.25 GB and their plan need a GPU with 16 GiB or more")
+    small = S.far_rows_inputs()
+    n_s, half, N, H = small["N"], small["N"] // 2, 2_200_000, 8
+    assert (N - half) * 1024 > 1 << 31 and N * 1024 < 1 << 32
+    s_small = _direct_setup(n_s, small["E"], 256, H, small["T"], small["R"], 1.0, 0, inputs=small)
+    got_small = _direct_logits(s_small)
+    ref, mag = _logits_fp64(s_small)
+    _against_bound(got_small, ref, mag, "kside logits, 8192 rows")
+    far = lambda v: torch.where(v < half, v, v + (N - n_s))
+    big = dict(small, N=N, ei=far(small["ei"]))
+    big["nt"] = torch.cat([small["nt"][:half], small["nt"][half:half + 1].expand(N - n_s), small["nt"][half:]])
+    for k in ("Q", "K"):
+        t = torch.zeros(N, 256, dtype=torch.float32, device=DEV)
+        t[:half], t[N - half:] = small[k][:half].to(DEV), small[k][half:].to(DEV)
+        big[k] = t
+    src, dst = big["ei"][0], big["ei"][1]
+    assert int(((src < half) & (dst >= N - half)).sum()) > 10000 and int(((src >= N - half) & (dst < half)).sum()) > 10000
+    s_big = _direct_setup(N, small["E"], 256, H, small["T"], small["R"], 1.0, 0, inputs=big)
+    got = _direct_logits(s_big)
+    assert torch.isfinite(got).all() and float(got.abs().max()) > 0
+    _against_bound(got, ref, mag, "kside logits, rows 2.25 GB from the base")
+    n_diff = int((got.view(torch.int32) != got_small.view(torch.int32)).sum())
+    assert n_diff == 0, "%d logits differ from the renumbered graph" % n_diff
