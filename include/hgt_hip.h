@@ -1214,6 +1214,65 @@ int hgt_grad_norm_join(const double* partials, int64_t n_chunks, float* total_no
 int hgt_adamw_step(const hgt_optim_tensor* tensors, int32_t n_tensors, const hgt_optim_group* groups, int32_t n_groups,
                    const hgt_optim_chunk* chunks, int64_t n_chunks, const float* total_norm, float max_norm, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Building the resident graph from raw edge lists (csrc/hgt_graph_build.hip): what ogbn-mag/preprocess_ogbn_mag.py:29-42 does with
+ * nested dicts, one Python step per edge -- `elist[t_id][s_id] = year` -- and the row means of its lines 69-99.  Added under ABI 8
+ * (new symbols only).  pyhgt_amd.graph_build.np_edge_lists_to_csr / np_neighbour_mean are the definitions.
+ *
+ *   hgt_graph_csr_bytes   *ws_bytes_host = the device scratch hgt_graph_csr_build needs for E entries (E < 0, NULL: HGT_ERR_INVALID_ARG;
+ *                         E >= 2^31 - 1: HGT_ERR_TOO_LARGE).  Host arithmetic on E alone, no device call: about 52 bytes per entry,
+ *                         16 of them reserved for rocPRIM's sorts (a rocPRIM that wants more: HGT_ERR_UNSUPPORTED from the build,
+ *                         before its first launch).
+ *   hgt_graph_csr_build   one direction of one relation.  Entry e (0 <= e < E) says "row rows[e * row_stride] has the neighbour
+ *                         nbrs[e * nbr_stride]"; strides in elements, ids of id_bytes = 4 (int32) or 8 (int64) bytes, read in place.
+ *                         The dict rule: inside a row the neighbours stand in the order of their FIRST entry; a repeated (row,
+ *                         neighbour) pair keeps that position and takes the time of its LAST entry.  The time of entry e is
+ *                         edge_time[e], else node_time[row id] (node_time_by == HGT_GRAPH_TIME_BY_ROW) or node_time[neighbour id]
+ *                         (HGT_GRAPH_TIME_BY_NBR), else HGT_SAMPLER_TIME_NONE's value (both NULL); giving both is
+ *                         HGT_ERR_INVALID_ARG.
+ *                         Out: indptr int32[n_rows + 1], nbr_out / time_out int32[E] of which the first indptr[n_rows] are written,
+ *                         status int32[2] = {entries kept, error flag}.  Flag bit 0: an id outside [0, n_rows) / [0, n_nbrs) -- such
+ *                         an entry is built as id 0, so every index of the output stays in range, and the caller reads the flag with
+ *                         the count and discards the result.
+ *                         How: a stable radix sort (rocPRIM) by (row, neighbour) brings the copies of a pair together in entry
+ *                         order; the head of a run marks its entry as kept, the tail hands it its time; a second stable sort of the
+ *                         entries by row, a scan over the kept marks and one compaction give the three arrays.  Integers only, no
+ *                         atomics but the OR into the flag.  Nothing synchronises; E == 0 writes a zero indptr and status.
+ *                         NULL output / scratch, NULL ids with E > 0, a negative size or stride, id_bytes not 4 or 8, n_rows or n_nbrs
+ *                         < 1 with E > 0: HGT_ERR_INVALID_ARG; E, n_rows or n_nbrs >= 2^31 - 1: HGT_ERR_TOO_LARGE; ws_bytes below
+ *                         hgt_graph_csr_bytes: HGT_ERR_WORKSPACE; no launch in any of these.
+ *   hgt_neighbour_mean_bytes  *ws_bytes_host = the scratch of hgt_neighbour_mean for n_entries = the summed lengths of the CSRs'
+ *                         neighbour arrays and rows of d columns.
+ *   hgt_neighbour_mean    out[r, 0:d] = (sum of x[nbr]) / count over the neighbours of row r in n_csr CSRs (host table, at most
+ *                         HGT_SAMPLER_MAX_TRIPLES) that share the row type and the neighbour type: fp32, the CSRs in table order, a
+ *                         CSR's neighbours in its order -- one sequence of `count` terms per row, a pair that two CSRs hold counts
+ *                         twice (coo_matrix sums duplicates, preprocess_ogbn_mag.py:83).  count == 0: a row of zeros (normalize's
+ *                         1 / 0 -> 0).  A sequence of up to HGT_GRAPH_MEAN_CHUNK terms is added term by term by one wavefront;
+ *                         a longer one is cut into chunks of HGT_GRAPH_MEAN_CHUNK terms, one wavefront each, whose sums are joined
+ *                         in chunk order: the bits of a row depend on its own sequence alone, not on the other rows or the launch.
+ *                         No float atomics.  x: [n_nbrs, d] float32 with row stride ldx >= d (a column slice is fine), out: [n_rows,
+ *                         d] with ldo >= d; any d >= 1.  Ids in the CSRs are trusted (hgt_graph_csr_build made them).
+ *                         NULL table / x / out / scratch where read, n_csr < 1, d < 1, ld below d, a negative size:
+ *                         HGT_ERR_INVALID_ARG; n_csr > HGT_SAMPLER_MAX_TRIPLES: HGT_ERR_UNSUPPORTED; n_rows or n_entries >= 2^31 - 1:
+ *                         HGT_ERR_TOO_LARGE; scratch too small: HGT_ERR_WORKSPACE; no launch.  n_rows == 0: HGT_OK, no launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_GRAPH_MEAN_CHUNK 256
+#define HGT_GRAPH_TIME_BY_ROW 0
+#define HGT_GRAPH_TIME_BY_NBR 1
+#define HGT_GRAPH_BAD_ID 1
+typedef struct hgt_graph_csr {
+    const int32_t* indptr;
+    const int32_t* nbr;
+} hgt_graph_csr;
+int hgt_graph_csr_bytes(int64_t E, uint64_t* ws_bytes_host);
+int hgt_graph_csr_build(const void* rows, int64_t row_stride, const void* nbrs, int64_t nbr_stride, int32_t id_bytes,
+                        const int32_t* edge_time, const int32_t* node_time, int32_t node_time_by, int64_t E, int64_t n_rows,
+                        int64_t n_nbrs, int32_t* indptr, int32_t* nbr_out, int32_t* time_out, int32_t* status, void* ws,
+                        uint64_t ws_bytes, void* stream);
+int hgt_neighbour_mean_bytes(int64_t n_entries, int32_t d, uint64_t* ws_bytes_host);
+int hgt_neighbour_mean(const hgt_graph_csr* csrs_host, int32_t n_csr, const float* x, int64_t ldx, int64_t n_rows, int64_t n_entries,
+                       int32_t d, float* out, int64_t ldo, void* ws, uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,7 +99,14 @@ class HgtSamplerMask(C.Structure):
     _fields_ = [("tgt_below", C.c_int32), ("src_below", C.c_int32)]
 
 
-RANK_LIST_CAP = 1024     # HGT_RANK_LIST_CAP: positives a pass of hgt_rank_metrics holds
+class HgtGraphCsr(C.Structure):
+    _fields_ = [("indptr", C.c_void_p), ("nbr", C.c_void_p)]
+
+
+GRAPH_MEAN_CHUNK = 256      # HGT_GRAPH_MEAN_CHUNK: the most terms of a row one wavefront of hgt_neighbour_mean adds
+HGT_GRAPH_TIME_BY_ROW = 0
+HGT_GRAPH_TIME_BY_NBR = 1
+RANK_LIST_CAP = 1024    # HGT_RANK_LIST_CAP: positives a pass of hgt_rank_metrics holds
 CLASS_LOSS_WAVE_COLS = 256   # HGT_CLASS_LOSS_WAVE_COLS: the longest row of hgt_class_loss that takes a wavefront
 OPTIM_CHUNK = 4096          # HGT_OPTIM_CHUNK: the most elements of one tensor a workgroup of the optimizer kernels takes
 PREDICT_MAX_SPLITS = 8     # HGT_PREDICT_MAX_SPLITS: the most splits hgt_class_predict counts in one call
@@ -275,6 +282,13 @@ SIGNATURES = {
     "hgt_grad_sqnorm": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp]),
     "hgt_grad_norm_join": (C.c_int, [_vp, _i64, _vp, _vp]),
     "hgt_adamw_step": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i64, _vp, C.c_float, _vp]),
+    # the resident graph from raw edge lists (csrc/hgt_graph_build.hip): (E, ws_bytes); (rows, row_stride, nbrs, nbr_stride, id_bytes,
+    # edge_time, node_time, node_time_by, E, n_rows, n_nbrs, indptr, nbr_out, time_out, status, ws, ws_bytes, stream); (n_entries, d,
+    # ws_bytes); (csrs_host, n_csr, x, ldx, n_rows, n_entries, d, out, ldo, ws, ws_bytes, stream)
+    "hgt_graph_csr_bytes": (C.c_int, [_i64, C.POINTER(_u64)]),
+    "hgt_graph_csr_build": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "hgt_neighbour_mean_bytes": (C.c_int, [_i64, _i32, C.POINTER(_u64)]),
+    "hgt_neighbour_mean": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _u64, _vp]),
 }
 
 _lib = None

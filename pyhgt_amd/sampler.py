@@ -82,16 +82,42 @@ class DeviceHeteroGraph:
                 list is the triple's index in the random-word keys
     csr         per triple (indptr int32[n_tgt + 1], src int32[], time int32[]), TIME_NONE = the reference's None
     features    per type a float32 [n_type, in_dim] matrix (or None for a type without nodes)
+    degree      {type: int32 [n_type]}: neighbours summed over the triples into the type
+    Three ways in: from_csr (finished CSRs), from_reference_graph (the reference's nested dicts) and from_edge_lists (raw edge lists;
+    with a device the CSRs are built there and `csr` is downloaded on first use -- pyhgt_amd/graph_build.py).
     It answers get_types() / get_meta_graph() like the reference's Graph, so it can stand in for `graph` in to_torch-like calls."""
 
     def __init__(self, types, meta, n_nodes, csr, features=None, device=None):
+        meta = [tuple(m) for m in meta]
+        if len(meta) != len(csr):
+            raise ValueError("pyhgt_amd: one CSR per meta triple")
+        picked = self._set_schema(types, meta, n_nodes)
+        tid = {t: i for i, t in enumerate(self.types)}
+        self._csr = []
+        for i in picked:
+            indptr, src, time = csr[i]
+            tt, st, _ = meta[i]
+            indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+            src = np.ascontiguousarray(src, dtype=np.int32)
+            time = np.full(src.shape, TIME_NONE, np.int32) if time is None else np.ascontiguousarray(time, dtype=np.int32)
+            if indptr.shape != (self.n_nodes[tid[tt]] + 1,) or indptr[0] != 0 or np.any(np.diff(indptr) < 0) or indptr[-1] != src.size:
+                raise ValueError("pyhgt_amd: indptr of %r is not a CSR over the target type's nodes" % (meta[i],))
+            if time.shape != src.shape or (src.size and (src.min() < 0 or src.max() >= self.n_nodes[tid[st]])):
+                raise ValueError("pyhgt_amd: neighbour ids / times of %r out of range" % (meta[i],))
+            self._csr.append((indptr, src, time))
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            self.csr_dev = [tuple(up(a) for a in c) for c in self._csr]
+        self.set_features(features)
+
+    def _set_schema(self, types, meta, n_nodes):
+        """types / meta / edge_dict / triples / tri_types and the empty call state; -> the positions in `meta` of the triples, in the
+        order of `triples` (by relation id, then target type; `self` left out, data.py:116)"""
         self.types = list(types)
         T = len(self.types)
         if not 1 <= T <= _lib.HGT_SAMPLER_MAX_TYPES:
             raise ValueError("pyhgt_amd: 1..%d node types, got %d" % (_lib.HGT_SAMPLER_MAX_TYPES, T))
-        meta = [tuple(m) for m in meta]
-        if len(meta) != len(csr):
-            raise ValueError("pyhgt_amd: one CSR per meta triple")
         keep = [i for i, m in enumerate(meta) if m[2] != "self"]                    # data.py:116
         self.meta = [meta[i] for i in keep]
         if len(self.meta) > _lib.HGT_SAMPLER_MAX_TRIPLES:
@@ -103,20 +129,7 @@ class DeviceHeteroGraph:
         order = sorted(range(len(keep)), key=lambda i: (self.edge_dict[self.meta[i][2]], tid[self.meta[i][0]]))
         self.triples = [self.meta[i] for i in order]
         self.tri_types = [(tid[tt], tid[st], self.edge_dict[rel]) for tt, st, rel in self.triples]
-        self.csr = []
-        for i in order:
-            indptr, src, time = csr[keep[i]]
-            tt, st, _ = self.meta[i]
-            indptr = np.ascontiguousarray(indptr, dtype=np.int32)
-            src = np.ascontiguousarray(src, dtype=np.int32)
-            time = np.full(src.shape, TIME_NONE, np.int32) if time is None else np.ascontiguousarray(time, dtype=np.int32)
-            if indptr.shape != (self.n_nodes[tid[tt]] + 1,) or indptr[0] != 0 or np.any(np.diff(indptr) < 0) or indptr[-1] != src.size:
-                raise ValueError("pyhgt_amd: indptr of %r is not a CSR over the target type's nodes" % (self.meta[i],))
-            if time.shape != src.shape or (src.size and (src.min() < 0 or src.max() >= self.n_nodes[tid[st]])):
-                raise ValueError("pyhgt_amd: neighbour ids / times of %r out of range" % (self.meta[i],))
-            self.csr.append((indptr, src, time))
-        self.features_host = None if features is None else [None if features.get(t) is None else features[t] for t in self.types]
-        self.device = None if device is None else torch.device(device)
+        self._degree = None
         self._host_state = None
         self._dev_state = {}
         self._dev_nodes = None
@@ -124,9 +137,14 @@ class DeviceHeteroGraph:
         self._batch_state = {}                               # the same three for batched calls (sample_subgraphs_device): [B, n] arrays
         self._batch_nodes = None                             # of their own, sized for the largest B seen, and a flag of their own
         self._batch_dirty = False
+        return [keep[i] for i in order]
+
+    def set_features(self, features):
+        """features = {type: [n_type, in_dim]} (or None): replaces the feature matrices, e.g. once `neighbour_mean` has computed those
+        of the types that came without any"""
+        tid = {t: i for i, t in enumerate(self.types)}
+        self.features_host = None if features is None else [None if features.get(t) is None else features[t] for t in self.types]
         if self.device is not None:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-            self.csr_dev = [tuple(up(a) for a in c) for c in self.csr]
             self.features = None
             if features is not None:
                 self.features = []
@@ -135,6 +153,42 @@ class DeviceHeteroGraph:
                     if f is not None and (f.dim() != 2 or f.size(0) != self.n_nodes[tid[t]]):
                         raise ValueError("pyhgt_amd: features[%r] must be [n_nodes, in_dim]" % t)
                     self.features.append(f)
+
+    @classmethod
+    def _from_device_csr(cls, types, meta, n_nodes, csr_dev, features, device):
+        """The private way in for a graph whose CSRs were BUILT on the device (from_edge_lists): per meta triple contiguous int32 device
+        tensors (indptr, src, time) whose invariants the building kernels guarantee -- nothing is validated or copied to the host here;
+        `.csr` downloads them on first use."""
+        self = cls.__new__(cls)
+        picked = self._set_schema(types, [tuple(m) for m in meta], n_nodes)
+        self.device = torch.device(device)
+        self._csr = None
+        self.csr_dev = [tuple(csr_dev[i]) for i in picked]
+        self.set_features(features)
+        return self
+
+    @property
+    def csr(self):
+        """per triple (indptr, src, time) as host numpy arrays; of a graph built on the device: downloaded once, on first use"""
+        if self._csr is None:
+            self._csr = [tuple(a.cpu().numpy() for a in c) for c in self.csr_dev]
+        return self._csr
+
+    @property
+    def degree(self):
+        """{type: int32 [n]}: a node's neighbours summed over all triples whose target is its type (preprocess_ogbn_mag.py:63) -- device
+        tensors on a device graph, numpy arrays on a host graph; log10 of it is the script's last feature column"""
+        if self._degree is None:
+            if self.device is not None:
+                deg = [torch.zeros(n, dtype=torch.int32, device=self.device) for n in self.n_nodes]
+                for (tt, _, _), (ip, _, _) in zip(self.tri_types, self.csr_dev):
+                    deg[tt] += ip[1:] - ip[:-1]
+            else:
+                deg = [np.zeros(n, np.int32) for n in self.n_nodes]
+                for (tt, _, _), (ip, _, _) in zip(self.tri_types, self.csr):
+                    deg[tt] += np.diff(ip)
+            self._degree = dict(zip(self.types, deg))
+        return self._degree
 
     @classmethod
     def from_csr(cls, types, meta, n_nodes, csr, features=None, device=None):
@@ -169,11 +223,26 @@ class DeviceHeteroGraph:
                     csr.append((indptr, src, time))
         return cls(types, meta, n_nodes, csr, features, device)
 
+    @classmethod
+    def from_edge_lists(cls, types, n_nodes, edges, edge_time=None, node_time=None, features=None, device=None, reverse="rev_"):
+        """From raw edge lists, the form heterogeneous datasets ship in: edges = {(source type, relation, target type): edge_index [2, E]}
+        (row 0 the sources), in the key order of OGB's edge_index_dict -- what ogbn-mag/preprocess_ogbn_mag.py:29-42 turns into nested
+        dicts and `from_reference_graph` into CSRs, with the same result array for array.  With `device` the CSRs are built there
+        (csrc/hgt_graph_build.hip) from edge arrays that never visit the host; device=None runs the numpy definition
+        `np_edge_lists_to_csr`.  pyhgt_amd/graph_build.py has the arguments and the rule."""
+        from .graph_build import build_from_edge_lists
+        return build_from_edge_lists(cls, types, n_nodes, edges, edge_time, node_time, features, device, reverse)
+
     def get_types(self):
         return list(self.types)
 
     def get_meta_graph(self):
         return list(self.meta)
+
+
+def _host_array(f):
+    """a feature matrix as float32 numpy (the features of a graph built on the device may be device tensors)"""
+    return f.detach().cpu().numpy().astype(np.float32, copy=False) if isinstance(f, torch.Tensor) else np.asarray(f, dtype=np.float32)
 
 
 def _seed_arrays(dgraph, inp):
@@ -432,7 +501,7 @@ def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, s
                 score[t][ids], stamp[t][ids], serial[t][ids] = 0, 0, -1
     width = max([f.shape[1] for f in (dgraph.features_host or []) if f is not None] + [0])
     feat = [np.zeros((0, width), np.float32) if dgraph.features_host is None or dgraph.features_host[t] is None or sampled[t].size == 0
-            else np.asarray(dgraph.features_host[t], dtype=np.float32)[sampled[t]] for t in range(T)]
+            else _host_array(dgraph.features_host[t])[sampled[t]] for t in range(T)]
     feat = np.concatenate(feat, axis=0) if width else np.zeros((int(type_off[-1]), 0), np.float32)
     tt = lambda a: torch.from_numpy(np.ascontiguousarray(a))
     out = _wire_tuple(_HostGraph, dgraph, tt(feat), [sampled[t].size for t in range(T)], tt(src), tt(dst), tt(etime), tt(rel_ptr), tt(type_off))

@@ -7,6 +7,8 @@ edge_type i64[E], edge_time i64[E] in [0,240) (data.py:250).  The recipe follows
 SURVEY.md section 8(d): uniform sources/targets (Poisson in-degree), relation
 ids independent of node types (every (src_type, rel, dst_type) combination occurs).
 """
+from collections import OrderedDict
+
 import numpy as np
 import torch
 
@@ -135,3 +137,29 @@ def synthetic_hetero_csr(types, meta, n_nodes, mean_degree=4.0, seed=0, years=(2
         indptr = np.concatenate([[0], np.cumsum(np.bincount(tgt, minlength=int(n_nodes[tt])))])
         out.append((indptr.astype(np.int32), src[order].astype(np.int32), tm[order].astype(np.int32)))
     return out
+
+
+MAG_RAW_NODES = {"paper": 736389, "author": 1134649, "field_of_study": 59965, "institution": 8740}          # ogbn-mag
+MAG_RAW_EDGES = OrderedDict([(("author", "affiliated_with", "institution"), 1043998), (("author", "writes", "paper"), 7145660),
+                             (("paper", "cites", "paper"), 5416271), (("paper", "has_topic", "field_of_study"), 7505078)])
+
+
+def synthetic_mag_raw(scale=1.0, feat_dim=128, seed=0):
+    """ogbn-mag-shaped RAW arrays, the form OGB / PyG ship a heterogeneous dataset in: -> (types, n_nodes, edge_index_dict,
+    paper features float32 [n_paper, feat_dim], paper years int32 [n_paper]) with node and edge counts `scale` times ogbn-mag's.
+    edge_index_dict[(source type, relation, target type)] is an int64 [2, E] tensor in OGB's key order; the ends are drawn with a
+    skew (squared uniforms), so that fields and institutions have the long rows of the real data, and pairs repeat now and then."""
+    g = torch.Generator().manual_seed(seed)
+    n_nodes = OrderedDict((t, max(4, int(n * scale))) for t, n in MAG_RAW_NODES.items())
+    skewed = {"field_of_study", "institution"}
+    edges = OrderedDict()
+    for key, e in MAG_RAW_EDGES.items():
+        E = max(1, int(e * scale))
+        ends = []
+        for t in (key[0], key[2]):
+            u = torch.rand(E, generator=g, dtype=torch.float64)
+            ends.append(((u * u if t in skewed else u) * n_nodes[t]).long().clamp_(max=n_nodes[t] - 1))
+        edges[key] = torch.stack(ends)
+    x = torch.randn(n_nodes["paper"], feat_dim, generator=g)
+    years = torch.randint(2010, 2020, (n_nodes["paper"],), generator=g, dtype=torch.int32)
+    return list(n_nodes), n_nodes, edges, x, years

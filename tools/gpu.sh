@@ -21,6 +21,8 @@
 #   small     the latency-regime part of the judged line only (bench.py --small-only): wall-clock us per layer / forward + parity
 #   sampler   the device sampler: its GPU tests, then tools/bench_sampler.py (device call against the numpy sibling and to_device_graph on
 #             MAG- / OAG-shaped resident graphs) -> $OUT/<tag>_device_sampler.json, and the example loop that trains on sampled batches
+#   graph     the graph build: its GPU tests, tools/bench_graph_build.py (one process per setting) -> $OUT/<tag>_graph_build.json, and
+#             examples/build_ogbn_mag_device.py;  graphprof: rocprofv3 kernel statistics of the build and of the neighbour means
 # Everything lands in $OUT (HGT_OUT_DIR, default bench_out/); summaries to be judged are copied to profiles/ by hand (or by `final`).
 # bench.py runs whose parity, secondaries or CPU baseline are read here pass --full (a plain bench.py run is the headline only).
 # Kernel experiments: tools/lab/build_lab.sh (lab libraries), lab_run.sh (phase times), pmc_quick.sh (counters), isa.sh (ISA + resources).
@@ -168,6 +170,33 @@ sampler)
     grep -E "^select | passed| failed|^FAILED|^ERROR" $OUT/${TAG}_sampler_tests.log | tail -20
     timeout 900 python tools/bench_sampler.py --out $OUT/${TAG}_device_sampler.json 2> $OUT/${TAG}_device_sampler.err; echo "bench rc=$?"
     timeout 300 python examples/train_device_sampler.py --steps 20 2>&1 | tail -4
+    ;;
+graph)
+    # every step under a time limit of its own; the chain ends at the first step that fails
+    timeout -k 10 300 python -m pytest tests/test_graph_build_gpu.py -m gpu -q -x > $OUT/${TAG}_graph_tests.log 2>&1 || { tail -20 $OUT/${TAG}_graph_tests.log; exit 1; }
+    tail -1 $OUT/${TAG}_graph_tests.log
+    rm -f $OUT/${TAG}_graph_build.json
+    for s in a b mean c d; do
+        timeout -k 10 400 python tools/bench_graph_build.py --only $s --out $OUT/${TAG}_graph_build.json 2> $OUT/${TAG}_graph_build_$s.err || { echo "setting $s failed"; tail -5 $OUT/${TAG}_graph_build_$s.err; exit 1; }
+    done
+    timeout -k 10 200 python examples/build_ogbn_mag_device.py 2>&1 | tail -2
+    ;;
+graphprof)
+    # kernel times of the build and of the means: a run of its own under rocprofv3, no counters in it
+    export TMPDIR=/tmp; ROOT=$(pwd); cd /tmp
+    for s in a mean; do
+        rm -rf /tmp/pg_$s
+        timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pg_$s -o s -- python $ROOT/tools/bench_graph_build.py --only $s --repeats 3 > /tmp/pg_$s.log 2>&1 || { tail -5 /tmp/pg_$s.log; exit 1; }
+        python - $s <<'PY' | tee $ROOT/$OUT/${TAG}_graph_build_kernels_$s.txt
+import csv, glob, sys
+f = glob.glob("/tmp/pg_%s/**/*kernel_stats.csv" % sys.argv[1], recursive=True)
+rows = sorted(csv.DictReader(open(f[0])), key=lambda r: -float(r["TotalDurationNs"]))
+print("tools/bench_graph_build.py --only %s --repeats 3 (a warm-up and one more call included)" % sys.argv[1])
+for r in rows[:14]:
+    print("%-100s %6s %10.1f us %10.2f ms" % (r["Name"][:100], r["Calls"], float(r["AverageNs"]) / 1e3, float(r["TotalDurationNs"]) / 1e6))
+PY
+    done
+    cd $ROOT
     ;;
 emuprof)
     export TMPDIR=/tmp; ROOT=$(pwd); cd /tmp
