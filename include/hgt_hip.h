@@ -286,7 +286,7 @@ int hgt_edge_logits_mfma(const void* plan, int64_t n_nodes, int64_t n_edges, int
  *   (relation, head) block as fp16 hi / lo of att_t * 2^s with one power-of-two scale per block, and the blocks' exponents behind them.
  *   The K rows are scaled per (row, head) and the Q rows per (row, head) by exact powers of two inside the kernel, so the result is
  *   finite whenever the fp32 logit is, whatever the magnitudes; the same image and arithmetic serve both split precisions
- *   (frag_f16 is accepted and ignored; att_t is not read).
+ *   (att_t is not read; of frag_f16 only bit 3 is: the per-lane gather of HGT_FLAG_KSIDE_LANE_GATHER, same logits bit for bit).
  * Covered: dk_pad == 32, n_heads (layout heads) 2, 4 or 8 (rows of at most 256 padded columns), rte_k == NULL, and
  *   n_nodes * n_heads * dk_pad * 4 < 2^32 (every Q / K row below 4 GiB from its base).  HGT_ERR_UNSUPPORTED otherwise: the caller
  *   takes hgt_edge_logits / hgt_edge_logits_mfma.  Edges of the unclaimed bucket get logit 0.  No atomics: bit-reproducible. */
@@ -300,6 +300,11 @@ int hgt_edge_logits_kside(const void* plan, int64_t n_nodes, int64_t n_edges, in
  *   b_col[k-step 2][lane 64][8] = the column of the head a lane supplies as element j of the B operand;
  *   c_out[lane 64][16] = the output a lane receives in accumulator register reg.  Any of the three may be NULL. */
 int hgt_kside_image_map(int32_t n_blocks, int32_t* image_map, int32_t* b_col, int32_t* c_out);
+/* Host only (no GPU): how the kernel's lanes gather a batch of 32 edges x one 128-byte head line through LDS (4 pieces of 1 KB).
+ *   dma_map[piece 4][lane 64][2] = {edge of the batch, 16-byte chunk of the head line} a lane fetches; it lands at 1024 piece + 16 lane;
+ *   read_map[read 4][lane 64][3] = {LDS byte offset, edge, chunk}: where the lane's i-th 16-byte read goes and what it must find.
+ * Either may be NULL. */
+int hgt_kside_gather_map(int32_t* dma_map, int32_t* read_map);
 /* ABI 6: the work items [item_begin, item_end) only = the items of a range of destination tiles (hgt_plan_tile_items_offset): the
  * logits of ONE target block of the multi-GPU path.  att_frag may be NULL (vector-ALU kernel). */
 int hgt_edge_logits_range(const void* plan, int64_t n_nodes, int64_t n_edges, int32_t n_types, int32_t n_relations,
@@ -701,6 +706,11 @@ typedef struct hgt_conv_args {
                                       * plain staged and target-block (stage 5) calls with a split precision whose work items have at least 64 edges, and neither of the
                                       * two flags above) */
 #define HGT_FLAG_NO_KSIDE_LOGITS 131072 /* never hgt_edge_logits_kside */
+#define HGT_FLAG_KSIDE_LANE_GATHER 262144 /* wherever hgt_edge_logits_kside runs (the stage-5 item ranges included): every lane loads its own 16-byte
+                                      * pieces of K[src] and Q[dst] instead of the gather of whole head lines through LDS.  Same logits bit
+                                      * for bit; tests / A/B timings.  Bit 3 of `frag_f16` of hgt_edge_logits_kside.  ABI note: added while
+                                      * HGT_ABI_VERSION stayed 8 (earlier libraries ignore the bit, as they ignore every unknown one); the
+                                      * bit and the lane form are to be retired once the LDS form has held for a while -- do not reuse it */
 #define HGT_FLAG_ITEM_AGGREGATE 16   /* hgt_edge_aggregate_items wherever it applies.  It applies -- and is the default -- when ALL of these hold: a split
                                       * precision; fewer than 65536 NODES (n_nodes: the workspace only then holds its scratch) and fewer than 65536
                                       * targets (n_q_rows); a scratch of at most 1 GiB (hgt_edge_aggregate_items_bytes <= 1 << 30: ~986 k edges at

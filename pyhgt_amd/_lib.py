@@ -29,6 +29,7 @@ HGT_FLAG_NO_COOP_EDGE = 16384
 HGT_FLAG_COOP_EDGE_ALWAYS = 32768
 HGT_FLAG_KSIDE_LOGITS = 65536
 HGT_FLAG_NO_KSIDE_LOGITS = 131072
+HGT_FLAG_KSIDE_LANE_GATHER = 262144
 HGT_LINEAR_FORCE_XS = 0x100
 HGT_LINEAR_NO_XS = 0x200
 HGT_LINEAR_NO_TILE = 0x400
@@ -149,6 +150,7 @@ SIGNATURES = {
     "hgt_relation_kside_pack": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "hgt_edge_logits_kside": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "hgt_kside_image_map": (C.c_int, [_i32, _vp, _vp, _vp]),
+    "hgt_kside_gather_map": (C.c_int, [_vp, _vp]),
     "hgt_edge_logits_range": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),
     "hgt_edge_aggregate_update_range": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                                   _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i32, _i32]),

@@ -18,7 +18,8 @@
 
 // hgt_edge_logits_kside.hip: that kernel on the work items [item_lo, item_hi) (a target block of the multi-GPU path), or all of them (0, -1)
 int hgt_edge_logits_kside_items(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H, int32_t dk_pad, const float* Q,
-                                const float* K, const float* rte_k, const void* att_kside, float* logits, int item_lo, int item_hi, void* stream);
+                                const float* K, const float* rte_k, const void* att_kside, float* logits, int item_lo, int item_hi, int lane_gather,
+                                void* stream);
 
 namespace {
 
@@ -385,15 +386,16 @@ struct Conv {
     }
 
     int edge_logits() const {
+        const int kside_lane = (a->flags & HGT_FLAG_KSIDE_LANE_GATHER) ? 8 : 0;      // bit 3 of `frag_f16` of hgt_edge_logits_kside
         if (r.logits == LOGITS_KSIDE) {      // (route() checked the coverage; an answer of "unsupported" still takes the other kernels)
-            const int rc = hgt_edge_logits_kside(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_t, att_k_buf, fmode, logits, stream);
+            const int rc = hgt_edge_logits_kside(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_t, att_k_buf, fmode | kside_lane, logits, stream);
             if (rc != HGT_ERR_UNSUPPORTED) return rc;
             if (r.mfma_logits) return hgt_edge_logits_mfma(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_t, att_f_buf, fmode, logits, stream);
         }
         switch (r.logits) {
             case LOGITS_RANGE:
                 if (r.kside_range) {
-                    const int rc = hgt_edge_logits_kside_items(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_k_buf, logits, a->item_begin, a->item_end, stream);
+                    const int rc = hgt_edge_logits_kside_items(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_k_buf, logits, a->item_begin, a->item_end, kside_lane, stream);
                     if (rc != HGT_ERR_UNSUPPORTED) return rc;
                 }
                 return hgt_edge_logits_range(a->plan, N, E, T, R, H, dkp, Q, K, rte_k, att_t, r.mfma_logits ? att_f_buf : nullptr, fmode, logits,

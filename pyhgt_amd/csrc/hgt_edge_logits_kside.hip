@@ -18,12 +18,23 @@
 // overflows or is flushed whatever the magnitudes, the fp32 accumulators stay below 2^36, and the logit is finite whenever its fp32
 // value is.
 //
-// Work: a wavefront takes min(H, 4) heads of one work item for all its batches (at H = 8 two wavefronts share an item), keeps the
-// image of its heads in registers (16 per head) and min(H, 4) row buffers: the K and Q pieces of the step (batch, head) three
-// steps ahead are requested before the current step is consumed -- 24 KB of rows in flight per wavefront, two wavefronts per
-// SIMD, no scratch.  Every load is unconditional and of fixed size (indices clamped to the item), see hgt_edge_logits.hip.
-// Measured at the benchmark size (profiles/kside_logits_*): the kernel is bound by the texture-address units, not by HBM or the
-// ALUs -- an edge on the lane makes every row load 64 separate 16-byte pieces -- see DESIGN.md section 4.
+// Work: a wavefront takes min(H, 4) heads of one work item for all its batches (at H = 8 two wavefronts share an item) and keeps the
+// image of its heads in registers (16 per head).  The steps are the (batch, head) pairs in order.
+//
+// Gather (default): the K and Q pieces of a step arrive by LDS-DMA in whole 128-byte head lines -- one instruction fetches 8 edges x
+// one line, lanes 8 r .. 8 r + 7 the eight 16-byte chunks of edge 8 piece + r, four instructions for K and four for Q -- into a ring
+// of two 8 KB slots that is private to the wavefront (no workgroup barrier), and the lane reads its 64 + 64 bytes back with eight
+// conflict-free ds_read_b128 (maps: hgt_kside_map.h).  A slot is refilled with the step two ahead as soon as its reads have returned
+// (lgkmcnt), in front of the step's arithmetic; a step's reads follow a counted vmcnt that leaves the younger step in flight:
+// two steps = 16 KB of rows in flight per wavefront, two wavefronts per SIMD (128 KB of LDS per CU), no row buffers in registers.
+// The edge ids of the batch after next are the loop's only register loads; they are issued, like the DMAs, where hipcc does not
+// count them (it would drain every DMA at their use) and retired by the same counted wait.  Every request is unconditional and of
+// fixed size (indices clamped to the item), see hgt_edge_logits.hip.
+//
+// Lane gather (HGT_FLAG_KSIDE_LANE_GATHER, kept for A/B runs and as the bit-identity reference of the form above; to be retired):
+// every lane loads its own 16-byte pieces into min(H, 4) row buffers, the pieces of the step three ahead requested before the
+// current one is consumed -- 24 KB in flight, but 64 separate 64-byte sectors per load instruction, which binds the kernel to the
+// texture-address units (profiles/kside_logits_*).  Same arithmetic, same logits bit for bit.
 #include "hgt_edge_common.h"
 #include "hgt_split_common.h"
 #include "hgt_kside_map.h"
@@ -109,11 +120,12 @@ __global__ __launch_bounds__(256) void k_relation_kside_pack(const float* __rest
     if (t == 0) reinterpret_cast<int*>(img + (int64_t)n_rh * HGT_KSIDE_BLOCK_ELEMS)[rh] = e - 141;
 }
 
+typedef unsigned hgt_u32x4 __attribute__((ext_vector_type(4)));
+
 struct KsideRows {   // a lane's 64 bytes of K[src] and of Q[dst] for one head
     float4 k[4], q[4];
 };
 
-typedef unsigned hgt_u32x4 __attribute__((ext_vector_type(4)));
 typedef __amdgpu_buffer_rsrc_t kside_rsrc;
 
 // Q and K are read through buffer descriptors: the lane offsets are 32-bit by construction (coverage: every row below 4 GiB), a
@@ -133,6 +145,56 @@ __device__ __forceinline__ void kside_issue(kside_rsrc K, kside_rsrc Q, unsigned
     for (int i = 0; i < 4; ++i) b.k[i] = kside_load16(K, koff + h * 128 + 16 * i);
 #pragma unroll
     for (int i = 0; i < 4; ++i) b.q[i] = kside_load16(Q, qoff + h * 128 + 16 * i);
+}
+
+// ---- gather through LDS (hgt_kside_map.h: gather maps) ----
+constexpr unsigned KSIDE_PIECE = 1024;                    // bytes one LDS-DMA instruction writes: 8 edges x a 128-byte head line
+constexpr unsigned KSIDE_SIDE = 4 * KSIDE_PIECE;          // the K (or Q) head lines of a batch of 32 edges
+constexpr unsigned KSIDE_SLOT = 2 * KSIDE_SIDE;           // a step: K pieces, then Q pieces
+constexpr unsigned KSIDE_RING = 2;                        // slots per wavefront
+constexpr unsigned KSIDE_WAVE_LDS = KSIDE_RING * KSIDE_SLOT;
+
+// the same descriptor as kside_table, as four scalar words for the LDS-DMA statements
+__device__ __forceinline__ hgt_u32x4 kside_table_words(const float* p, unsigned bytes) {
+    const uint64_t a = (uint64_t)(uintptr_t)p;
+    const hgt_u32x4 r = {(unsigned)a, (unsigned)(a >> 32) & 0xffffu, bytes, 0x00020000u};
+    return r;
+}
+// The four pieces of one side of a step: 64 lanes x 16 B each from table[voff[p] + soff] to LDS [lds_dst + 1024 p + 16 lane].  M0 (the
+// LDS destination; compiler-reserved) is written and restored inside the statement; soff goes into the scalar offset, which -- unlike
+// the instruction's immediate -- moves the source only.  The opening s_nop, with the three instructions in front of the first load,
+// covers the wait states of a scalar operand that a vector instruction (readfirstlane) wrote.  Not counted by hipcc: kside_wait_vm.
+__device__ __forceinline__ void kside_dma4(hgt_u32x4 table, const unsigned (&voff)[4], unsigned soff, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile(
+        "s_nop 1\n\ts_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %5, %7 offen lds\n\t"
+        "s_add_u32 m0, %6, 0x400\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %5, %7 offen lds\n\t"
+        "s_add_u32 m0, %6, 0x800\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %5, %7 offen lds\n\t"
+        "s_add_u32 m0, %6, 0xc00\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %5, %7 offen lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(table), "s"(lds_dst), "s"(soff)
+        : "memory", "scc");
+}
+static_assert(KSIDE_PIECE == 0x400, "the piece stride written into kside_dma4");
+constexpr int KSIDE_STEP_DMAS = 8;      // LDS-DMA instructions of a step: the count every wait below leaves in flight
+// all but the youngest step's DMAs have landed (vector memory operations retire in order)
+__device__ __forceinline__ void kside_wait_vm() { asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
+// ... and with them the edge ids requested by kside_ids_request in front of that youngest step
+__device__ __forceinline__ void kside_wait_vm_ids(int& s, int& d) { asm volatile("s_waitcnt vmcnt(8)" : "+v"(s), "+v"(d) : : "memory"); }
+__device__ __forceinline__ void kside_ids_request(const int32_t* ps, const int32_t* pd, int& s, int& d) {
+    asm volatile("global_load_dword %0, %2, off\n\tglobal_load_dword %1, %3, off" : "=&v"(s), "=&v"(d) : "v"(ps), "v"(pd) : "memory");
+}
+__device__ __forceinline__ void kside_wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// per-lane byte offsets of a batch's eight pieces (K 0-3, Q 4-7) from the edge ids the lane holds for edge lane & 31
+__device__ __forceinline__ void kside_piece_offsets(int s, int d, const int (&bp)[4], const unsigned (&cp)[4], unsigned rowb, unsigned (&off)[8]) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        off[p] = (unsigned)__builtin_amdgcn_ds_bpermute(bp[p], s) * rowb + cp[p];
+        off[4 + p] = (unsigned)__builtin_amdgcn_ds_bpermute(bp[p], d) * rowb + cp[p];
+    }
 }
 
 // one head of one batch: split the K piece, six MFMAs, dot with the Q piece, undo the three scales
@@ -178,9 +240,8 @@ __device__ __forceinline__ float kside_head(const KsideRows& b, const hgt_f16x8 
 
 // HW heads per wavefront: a wavefront takes HW = min(H, 4) heads of its item for all the item's batches, so at H = 8 two wavefronts
 // share an item (each reads its 512-byte half of every row, stores its four logits of every edge) and a workgroup takes 4 H / 8 ... 4
-// items.  The image of HW heads is 16 HW registers, which leaves room for HW row buffers: the pieces of step s + HW - 1 are requested
-// before step s is consumed (steps = (batch, head) pairs in order), HW - 1 steps = 8 (HW - 1) KB of rows in flight per wavefront.
-template <int H>
+// items.  The image of HW heads is 16 HW registers.  LANE: the per-lane gather into HW row buffers (see the head of the file).
+template <int H, bool LANE>
 __global__ __launch_bounds__(256, 2) void k_edge_logits_kside(
     const HgtItem* __restrict__ items, const HgtPlanHeader* __restrict__ hdr, const int32_t* __restrict__ esrc,
     const int32_t* __restrict__ edst, const float* __restrict__ Qp, const float* __restrict__ Kp, unsigned table_bytes,
@@ -203,7 +264,6 @@ __global__ __launch_bounds__(256, 2) void k_edge_logits_kside(
         return;
     }
     const int el = lane & 31, half = lane >> 5;
-    const kside_rsrc K = kside_table(Kp, table_bytes), Q = kside_table(Qp, table_bytes);
 
     // the relation's image: A operands of this wavefront's heads, and the exponents that undo their scales
     hgt_f16x8 ah[HW][2], al[HW][2];
@@ -222,53 +282,135 @@ __global__ __launch_bounds__(256, 2) void k_edge_logits_kside(
 #pragma unroll
     for (int h = 0; h < HW; ++h) ea[h] = eap[h];
 
-    // Software pipeline over the steps (batch of 32 edges, head): buffer h holds head h; step (b, h) first requests the pieces of the
-    // step HW - 1 ahead -- (b, HW - 1) at h = 0, (b + 1, h - 1) otherwise -- into the buffer the previous step released.  The edge
-    // indices run one batch further ahead.  Indices are clamped to the item, so the requests behind its end re-read its last edge.
-    const unsigned lo = (unsigned)half * 64u + (unsigned)h0 * 128u;
-    int li = min(beg + el, end - 1);
-    unsigned koff = (unsigned)esrc[li] * ROWB + lo, qoff = (unsigned)edst[li] * ROWB + lo;
-    li = min(beg + 32 + el, end - 1);
-    unsigned koff_n = (unsigned)esrc[li] * ROWB + lo, qoff_n = (unsigned)edst[li] * ROWB + lo;
-    KsideRows buf[HW];
+    if constexpr (LANE) {
+        // Software pipeline over the steps (batch of 32 edges, head): buffer h holds head h; step (b, h) first requests the pieces of the
+        // step HW - 1 ahead -- (b, HW - 1) at h = 0, (b + 1, h - 1) otherwise -- into the buffer the previous step released.  The edge
+        // indices run one batch further ahead.  Indices are clamped to the item, so the requests behind its end re-read its last edge.
+        const kside_rsrc K = kside_table(Kp, table_bytes), Q = kside_table(Qp, table_bytes);
+        const unsigned lo = (unsigned)half * 64u + (unsigned)h0 * 128u;
+        int li = min(beg + el, end - 1);
+        unsigned koff = (unsigned)esrc[li] * ROWB + lo, qoff = (unsigned)edst[li] * ROWB + lo;
+        li = min(beg + 32 + el, end - 1);
+        unsigned koff_n = (unsigned)esrc[li] * ROWB + lo, qoff_n = (unsigned)edst[li] * ROWB + lo;
+        KsideRows buf[HW];
 #pragma unroll
-    for (int h = 0; h < HW - 1; ++h) kside_issue<H>(K, Q, koff, qoff, h, buf[h]);
-    li = min(beg + 64 + el, end - 1);
-    int s2 = esrc[li], d2 = edst[li];
-    for (int base = beg; base < end; base += 32) {
-        float lg[HW];
+        for (int h = 0; h < HW - 1; ++h) kside_issue<H>(K, Q, koff, qoff, h, buf[h]);
+        li = min(beg + 64 + el, end - 1);
+        int s2 = esrc[li], d2 = edst[li];
+        for (int base = beg; base < end; base += 32) {
+            float lg[HW];
 #pragma unroll
-        for (int h = 0; h < HW; ++h) {
-            // (the barriers pin every request in front of the arithmetic it overlaps: left free, the scheduler moves the loads to
-            //  where their registers are needed and one step's pieces are in flight instead of HW - 1)
-            if (h == 0) kside_issue<H>(K, Q, koff, qoff, HW - 1, buf[HW - 1]);
-            else kside_issue<H>(K, Q, koff_n, qoff_n, h - 1, buf[h - 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            lg[h] = kside_head(buf[h], ah[h], al[h], ea[h]);
-            __builtin_amdgcn_sched_barrier(0);
+            for (int h = 0; h < HW; ++h) {
+                // (the barriers pin every request in front of the arithmetic it overlaps: left free, the scheduler moves the loads to
+                //  where their registers are needed and one step's pieces are in flight instead of HW - 1)
+                if (h == 0) kside_issue<H>(K, Q, koff, qoff, HW - 1, buf[HW - 1]);
+                else kside_issue<H>(K, Q, koff_n, qoff_n, h - 1, buf[h - 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                lg[h] = kside_head(buf[h], ah[h], al[h], ea[h]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (half == 0 && base + el < end) {
+                float* o = logits + (int64_t)(base + el) * H + h0;
+                if constexpr (HW == 2) *reinterpret_cast<float2*>(o) = make_float2(lg[0], lg[1]);
+                else *reinterpret_cast<float4*>(o) = make_float4(lg[0], lg[1], lg[2], lg[3]);
+            }
+            koff = koff_n;
+            qoff = qoff_n;
+            koff_n = (unsigned)s2 * ROWB + lo;
+            qoff_n = (unsigned)d2 * ROWB + lo;
+            li = min(base + 96 + el, end - 1);
+            s2 = esrc[li];
+            d2 = edst[li];
         }
-        if (half == 0 && base + el < end) {
-            float* o = logits + (int64_t)(base + el) * H + h0;
-            if constexpr (HW == 2) *reinterpret_cast<float2*>(o) = make_float2(lg[0], lg[1]);
-            else *reinterpret_cast<float4*>(o) = make_float4(lg[0], lg[1], lg[2], lg[3]);
+    } else {
+        // Ring of two slots per wavefront: step t = (batch, head h) lives in slot h & 1 (HW is even).  Step t: wait until only the
+        // DMAs of step t + 1 are in flight, read the slot, wait for the reads, refill the slot with step t + 2 -- head h + 2 of this
+        // batch or head h + 2 - HW of the next --, then the arithmetic of step t.  off_c / off_n are the piece offsets of this and of
+        // the next batch; the edge ids of the batch after next are requested in front of step 0's refill and are therefore retired by
+        // step 1's wait (older than the only step it leaves in flight).  The logit store between two batches only makes a wait stricter.
+        static_assert(HW % 2 == 0 && KSIDE_RING == 2 && KSIDE_STEP_DMAS == 8, "slot of a step = its head & 1; eight DMAs per step");
+        __shared__ __attribute__((aligned(1024))) unsigned char ring[4 * KSIDE_WAVE_LDS];
+        const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)ring) +
+                                  (unsigned)wib * KSIDE_WAVE_LDS;
+        const unsigned char* rd = ring + (unsigned)wib * KSIDE_WAVE_LDS;
+        const hgt_u32x4 K = kside_table_words(Kp, table_bytes), Q = kside_table_words(Qp, table_bytes);
+        unsigned cp[4], ra[4];      // source byte of the lane's chunk in its edge's row (DMA side), LDS byte of read i (read side)
+        int bp[4];                  // the lane that holds the edge id of the lane's DMA row, as a ds_bpermute address
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            cp[p] = (unsigned)h0 * 128u + 16u * (unsigned)hgt_kside_dma_chunk(p, lane);
+            bp[p] = 4 * hgt_kside_dma_edge(p, lane);
+            ra[p] = (unsigned)hgt_kside_read_offset(lane, p);
         }
-        koff = koff_n;
-        qoff = qoff_n;
-        koff_n = (unsigned)s2 * ROWB + lo;
-        qoff_n = (unsigned)d2 * ROWB + lo;
-        li = min(base + 96 + el, end - 1);
-        s2 = esrc[li];
-        d2 = edst[li];
+        unsigned off_c[8], off_n[8];
+        int li = min(beg + el, end - 1);
+        kside_piece_offsets(esrc[li], edst[li], bp, cp, ROWB, off_c);
+        li = min(beg + 32 + el, end - 1);
+        kside_piece_offsets(esrc[li], edst[li], bp, cp, ROWB, off_n);
+        // (every load hipcc counts is consumed in front of the first DMA: its own waits stay out of the loop)
+#pragma unroll
+        for (int h = 0; h < HW; ++h)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(ah[h][s]), "+v"(al[h][s]));
+#pragma unroll
+        for (int h = 0; h < HW; ++h) asm volatile("" : "+v"(ea[h]));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(off_c[i]), "+v"(off_n[i]));
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            kside_dma4(K, reinterpret_cast<const unsigned(&)[4]>(off_c[0]), h * 128u, lds_wave + h * KSIDE_SLOT);
+            kside_dma4(Q, reinterpret_cast<const unsigned(&)[4]>(off_c[4]), h * 128u, lds_wave + h * KSIDE_SLOT + KSIDE_SIDE);
+        }
+        int s2 = 0, d2 = 0;
+        for (int base = beg; base < end; base += 32) {
+            float lg[HW];
+#pragma unroll
+            for (int h = 0; h < HW; ++h) {
+                const unsigned slot = (h & 1) * KSIDE_SLOT;
+                if (h == 1) kside_wait_vm_ids(s2, d2);
+                else kside_wait_vm();
+                KsideRows b;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    b.k[i] = *reinterpret_cast<const float4*>(rd + slot + ra[i]);
+                    b.q[i] = *reinterpret_cast<const float4*>(rd + slot + KSIDE_SIDE + ra[i]);
+                }
+                kside_wait_lds();
+                if (h == 0) {
+                    li = min(base + 64 + el, end - 1);
+                    kside_ids_request(esrc + li, edst + li, s2, d2);
+                }
+                const bool same = h + 2 < HW;      // the step two ahead: in this batch, or in the next
+                const unsigned hn = (same ? h + 2 : h + 2 - HW) * 128u;
+                kside_dma4(K, reinterpret_cast<const unsigned(&)[4]>(same ? off_c[0] : off_n[0]), hn, lds_wave + slot);
+                kside_dma4(Q, reinterpret_cast<const unsigned(&)[4]>(same ? off_c[4] : off_n[4]), hn, lds_wave + slot + KSIDE_SIDE);
+                __builtin_amdgcn_sched_barrier(0);
+                lg[h] = kside_head(b, ah[h], al[h], ea[h]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (half == 0 && base + el < end) {
+                float* o = logits + (int64_t)(base + el) * H + h0;
+                if constexpr (HW == 2) *reinterpret_cast<float2*>(o) = make_float2(lg[0], lg[1]);
+                else *reinterpret_cast<float4*>(o) = make_float4(lg[0], lg[1], lg[2], lg[3]);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) off_c[i] = off_n[i];
+            kside_piece_offsets(s2, d2, bp, cp, ROWB, off_n);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the two steps requested behind the item's end: no DMA outlives the wavefront
     }
 }
 
 template <int H>
 static void launch_kside(const HgtPlanView& pv, const float* Q, const float* K, unsigned table_bytes, const unsigned short* img, float* logits, int R,
-                         int item_lo, int item_hi, hipStream_t stream) {
+                         int item_lo, int item_hi, bool lane_gather, hipStream_t stream) {
     constexpr int IPW = H == 8 ? 2 : 4;                                             // items per workgroup
     const int64_t n_launch = item_hi >= 0 ? (int64_t)(item_hi - item_lo) : pv.L.max_items;
     const unsigned blocks = hgt_item_grid((n_launch + IPW - 1) / IPW);
-    k_edge_logits_kside<H><<<blocks, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, Q, K, table_bytes, img, logits, R, item_lo, item_hi, (int)pv.L.max_items);
+    if (lane_gather)
+        k_edge_logits_kside<H, true><<<blocks, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, Q, K, table_bytes, img, logits, R, item_lo, item_hi, (int)pv.L.max_items);
+    else
+        k_edge_logits_kside<H, false><<<blocks, 256, 0, stream>>>(pv.items, pv.hdr, pv.esrc, pv.edst, Q, K, table_bytes, img, logits, R, item_lo, item_hi, (int)pv.L.max_items);
 }
 
 // one head group of 32-column heads
@@ -293,7 +435,8 @@ extern "C" int hgt_relation_kside_pack(const float* att_t, int32_t R, int32_t H,
 // the work items [item_lo, item_hi) of the plan (a target block of the multi-GPU path), or all of them (0, -1)
 __attribute__((visibility("hidden"))) int hgt_edge_logits_kside_items(const void* plan, int64_t N, int64_t E, int32_t T, int32_t R, int32_t H,
                                                                       int32_t dk_pad, const float* Q, const float* K, const float* rte_k,
-                                                                      const void* att_kside, float* logits, int item_lo, int item_hi, void* stream) {
+                                                                      const void* att_kside, float* logits, int item_lo, int item_hi, int lane_gather,
+                                                                      void* stream) {
     if (!plan || !Q || !K || !att_kside || (E > 0 && !logits) || N < 0 || E < 0 || R <= 0 || H <= 0 || 64 % H != 0 || dk_pad <= 0)
         return HGT_ERR_INVALID_ARG;
     if (dk_pad % (64 / H) != 0) return HGT_ERR_INVALID_ARG;
@@ -303,9 +446,9 @@ __attribute__((visibility("hidden"))) int hgt_edge_logits_kside_items(const void
     const HgtPlanView pv = hgt_plan_view(plan, N, E, T, R);
     const unsigned short* img = (const unsigned short*)att_kside;
     const unsigned table_bytes = (unsigned)((uint64_t)N * H * dk_pad * 4u);      // (Q may have fewer rows: the plan's targets lie inside it)
-    if (H == 2) launch_kside<2>(pv, Q, K, table_bytes, img, logits, R, item_lo, item_hi, (hipStream_t)stream);
-    else if (H == 4) launch_kside<4>(pv, Q, K, table_bytes, img, logits, R, item_lo, item_hi, (hipStream_t)stream);
-    else launch_kside<8>(pv, Q, K, table_bytes, img, logits, R, item_lo, item_hi, (hipStream_t)stream);
+    if (H == 2) launch_kside<2>(pv, Q, K, table_bytes, img, logits, R, item_lo, item_hi, lane_gather != 0, (hipStream_t)stream);
+    else if (H == 4) launch_kside<4>(pv, Q, K, table_bytes, img, logits, R, item_lo, item_hi, lane_gather != 0, (hipStream_t)stream);
+    else launch_kside<8>(pv, Q, K, table_bytes, img, logits, R, item_lo, item_hi, lane_gather != 0, (hipStream_t)stream);
     HGT_CHECK_LAUNCH();
     return HGT_OK;
 }
@@ -314,8 +457,7 @@ extern "C" int hgt_edge_logits_kside(const void* plan, int64_t N, int64_t E, int
                                      const float* Q, const float* K, const float* rte_k, const float* att_t, const void* att_kside,
                                      int32_t frag_f16, float* logits, void* stream) {
     (void)att_t;
-    (void)frag_f16;
-    return hgt_edge_logits_kside_items(plan, N, E, T, R, H, dk_pad, Q, K, rte_k, att_kside, logits, 0, -1, stream);
+    return hgt_edge_logits_kside_items(plan, N, E, T, R, H, dk_pad, Q, K, rte_k, att_kside, logits, 0, -1, frag_f16 & 8, stream);
 }
 
 // The index maps of hgt_kside_map.h enumerated on the host (no GPU): image_map[p] = {block, term, output, k} for every f16 element
@@ -339,5 +481,23 @@ extern "C" int hgt_kside_image_map(int32_t n_blocks, int32_t* image_map, int32_t
         if (c_out)
             for (int reg = 0; reg < 16; ++reg) c_out[lane * 16 + reg] = hgt_kside_c_out(lane >> 5, reg);
     }
+    return HGT_OK;
+}
+
+// The gather maps of hgt_kside_map.h enumerated on the host (no GPU): dma_map[piece 4][lane 64] = {edge of the batch, chunk of the
+// head line} a DMA lane fetches (its 16 bytes land at 1024 piece + 16 lane of the batch's 4 KB); read_map[i 4][lane 64] = {LDS byte
+// offset, edge, chunk}: where read i of a lane goes and what it must find there.  Either may be NULL.
+extern "C" int hgt_kside_gather_map(int32_t* dma_map, int32_t* read_map) {
+    for (int lane = 0; lane < 64; ++lane)
+        for (int p = 0; p < 4; ++p) {
+            if (dma_map) {
+                int32_t* o = dma_map + 2 * (p * 64 + lane);
+                o[0] = hgt_kside_dma_edge(p, lane), o[1] = hgt_kside_dma_chunk(p, lane);
+            }
+            if (read_map) {
+                int32_t* o = read_map + 3 * (p * 64 + lane);
+                o[0] = hgt_kside_read_offset(lane, p), o[1] = lane & 31, o[2] = hgt_kside_read_chunk(lane, p);
+            }
+        }
     return HGT_OK;
 }
