@@ -3,10 +3,12 @@
 graph is put on the device once (DeviceHeteroGraph), and every step samples a fresh sub-graph around random seed papers with
 sample_subgraph_device (instead of sample_subgraph + to_torch on the host) -> GNN -> Classifier -> nll_loss -> backward -> step.
 
-    python examples/train_device_sampler.py [--schema mag|oag] [--steps 30] [--stack B] [--papers 20000]
+    python examples/train_device_sampler.py [--schema mag|oag] [--steps 30] [--stack B] [--papers 20000] [--trim]
 
 --stack B: B sampled batches per optimizer step, drawn by one sample_subgraphs_device call (one pass of launches, one host read) and
 stacked on the device (stack_device_graphs); the pieces are sampled without a plan.  --stack 1 is the single call.
+--trim: the seed-trimmed forward, gnn(..., seeds=the seed rows): every layer computes only the rows that still reach a seed, and the
+result is the seed rows alone ("Seed-trimmed forward").
 The datasets are not available offline, so the task is synthetic: a paper's label is a fixed random projection of its features."""
 import argparse
 import os
@@ -40,7 +42,7 @@ def resident_graph(schema, n_paper, feat_dim, device, seed=0, mean_degree=3.0):
 
 
 def run(schema="mag", steps=30, n_paper=20000, n_hid=128, n_heads=8, n_layers=2, n_classes=16, batch_size=128, depth=4, width=64, lr=2e-3,
-        seed=0, device="cuda:0", verbose=True, stack=1, device_optimizer=False):
+        seed=0, device="cuda:0", verbose=True, stack=1, device_optimizer=False, trim=False):
     torch.manual_seed(seed)
     feat_dim = 129 if schema == "mag" else 256
     dgraph, n_nodes = resident_graph(schema, n_paper, feat_dim, device, seed)
@@ -78,8 +80,12 @@ def run(schema="mag", steps=30, n_paper=20000, n_hid=128, n_heads=8, n_layers=2,
         y = torch.cat([labels[p.indxs["paper"][:batch_size]] for p in pieces])
         t_sample += time.perf_counter() - ts
         gnn.train(), head.train()
-        rep = gnn(g[0], g[1], g[2], g[3], g[4])
-        loss = torch.nn.functional.nll_loss(head(rep[seeds]), y)
+        if trim:                                                            # the seed rows alone, from the rows that reach them
+            rows = pieces[0].seed_rows("paper") if stack == 1 else seeds
+            loss = torch.nn.functional.nll_loss(head(gnn(g[0], g[1], g[2], g[3], g[4], seeds=rows)), y)
+        else:
+            rep = gnn(g[0], g[1], g[2], g[3], g[4])
+            loss = torch.nn.functional.nll_loss(head(rep[seeds]), y)
         opt.zero_grad()
         loss.backward()
         if not device_optimizer:
@@ -103,5 +109,6 @@ if __name__ == "__main__":
     ap.add_argument("--stack", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device-optimizer", action="store_true", help="pyhgt_amd.AdamW(max_norm=0.5) in place of clip_grad_norm_ + torch.optim.AdamW")
+    ap.add_argument("--trim", action="store_true", help="the seed-trimmed forward: gnn(..., seeds=the seed rows)")
     a = ap.parse_args()
-    run(a.schema, a.steps, a.papers, seed=a.seed, stack=a.stack, device_optimizer=a.device_optimizer)
+    run(a.schema, a.steps, a.papers, seed=a.seed, stack=a.stack, device_optimizer=a.device_optimizer, trim=a.trim)

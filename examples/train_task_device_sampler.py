@@ -4,11 +4,12 @@ training years, samples their sub-graph with the label edges at the seeds masked
 reads the labels from the label relation of the full graph (LabelSpace.index) -- all of it on the device -- and trains GNN ->
 Classifier -> nll_loss; every few steps a batch from the validation years is scored.
 
-    python examples/train_task_device_sampler.py [--steps 30] [--papers 20000] [--no-mask]
+    python examples/train_task_device_sampler.py [--steps 30] [--papers 20000] [--no-mask] [--trim]
 
 The datasets are not available offline, so the graph is synthetic with the OAG schema: a paper's journal (PV_Journal) is a fixed
 random projection of its features and the edge carries the paper's year.  --no-mask leaves the label edges in the batch: the model then
-reads the answer off an in-edge of the node it classifies, which is what the mask is for."""
+reads the answer off an in-edge of the node it classifies, which is what the mask is for.  --trim: the seed-trimmed forward,
+gnn(..., seeds=batch.seed_rows("paper")): every layer computes only the rows that still reach a seed paper."""
 import argparse
 import os
 import sys
@@ -45,7 +46,7 @@ def task_graph(n_paper, feat_dim, device, seed=0, mean_degree=3.0):
 
 
 def run(steps=30, n_paper=20000, n_hid=128, n_heads=8, n_layers=2, batch_size=128, depth=4, width=64, lr=2e-3, seed=0, device="cuda:0",
-        verbose=True, masked=True, feat_dim=256, valid_every=10):
+        verbose=True, masked=True, feat_dim=256, valid_every=10, trim=False):
     torch.manual_seed(seed)
     dgraph, n_nodes = task_graph(n_paper, feat_dim, device, seed)
     space = LabelSpace(dgraph, LABEL, np.arange(n_nodes["venue"]))             # cand_list: every venue is a class
@@ -65,11 +66,16 @@ def run(steps=30, n_paper=20000, n_hid=128, n_heads=8, n_layers=2, batch_size=12
         g = sample_subgraph_device(dgraph, window[split][1], depth, width, inp, seed=call_seed, mask=mask)
         return g, g.seed_rows("paper"), space.index(g.indxs["paper"][:batch_size], *window[split])
 
+    def seed_rep(g, x_ids):
+        if trim:                                                                # the seed rows alone, from the rows that reach them
+            return gnn(g[0], g[1], g[2], g[3], g[4], seeds=x_ids)
+        return gnn(g[0], g[1], g[2], g[3], g[4])[x_ids]
+
     losses, accuracy, t0 = [], [], time.perf_counter()
     for step in range(steps):
         g, x_ids, y = batch("train", seed * 100003 + 2 * step)
         gnn.train(), head.train()
-        loss = torch.nn.functional.nll_loss(head(gnn(g[0], g[1], g[2], g[3], g[4])[x_ids]), y)
+        loss = torch.nn.functional.nll_loss(head(seed_rep(g, x_ids)), y)
         opt.zero_grad()
         loss.backward()
         torch.nn.utils.clip_grad_norm_(gnn.parameters(), 0.5)
@@ -79,7 +85,7 @@ def run(steps=30, n_paper=20000, n_hid=128, n_heads=8, n_layers=2, batch_size=12
             g, x_ids, y = batch("valid", seed * 100003 + 2 * step + 1)
             gnn.eval(), head.eval()
             with torch.no_grad():
-                accuracy.append((head(gnn(g[0], g[1], g[2], g[3], g[4])[x_ids]).argmax(dim=1) == y).float().mean().item())
+                accuracy.append((head(seed_rep(g, x_ids)).argmax(dim=1) == y).float().mean().item())
             if verbose:
                 print("step %3d  loss %.4f  validation accuracy %.3f  (%d nodes, %d edges, %d label edges in the batch)"
                       % (step, losses[-1], accuracy[-1], g[1].numel(), g[4].numel(), int((g[4] == dgraph.edge_dict[LABEL[2]]).sum())))
@@ -96,5 +102,6 @@ if __name__ == "__main__":
     ap.add_argument("--papers", type=int, default=20000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-mask", action="store_true")
+    ap.add_argument("--trim", action="store_true", help="the seed-trimmed forward: gnn(..., seeds=the seed rows)")
     a = ap.parse_args()
-    run(a.steps, a.papers, seed=a.seed, masked=not a.no_mask)
+    run(a.steps, a.papers, seed=a.seed, masked=not a.no_mask, trim=a.trim)

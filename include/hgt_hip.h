@@ -1283,6 +1283,43 @@ int hgt_neighbour_mean_bytes(int64_t n_entries, int32_t d, uint64_t* ws_bytes_ho
 int hgt_neighbour_mean(const hgt_graph_csr* csrs_host, int32_t n_csr, const float* x, int64_t ldx, int64_t n_rows, int64_t n_entries,
                        int32_t d, float* out, int64_t ldo, void* ws, uint64_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Seed-trimmed graphs (csrc/hgt_trim.hip): the rows and edges each layer of an n_layers stack needs for the seed rows, in hop-major
+ * order.  Added under ABI 8 (new symbols only).  pyhgt_amd.trim.np_trim_to_seeds / np_trim_graph are the definitions: hop[v] = the
+ * shortest directed distance from v to a seed along source -> target edges over EVERY edge (0 at a seed; -1 beyond n_layers); rows
+ * kept iff hop <= L, ordered by (hop, old row); edges kept iff hop[target] <= L - 1, ordered by (hop[target], old position).
+ *
+ *   hgt_trim_tmp_bytes    *tmp_bytes_host = the device scratch of the two calls below (host arithmetic: 4 bytes per node and about
+ *                         (L + 2) / 512 bytes per node and per edge).
+ *   hgt_trim_hops         edge_index int64 read in place (source of edge e at [e * stride_col], target at [stride_row + e *
+ *                         stride_col], as hgt_plan_build takes it), seeds int64[n_seeds] in any order, with repeats.  Leaves the hops
+ *                         and the bad-index flag in tmp: 2 + n_layers launches (one per hop round: the launch boundary is the only
+ *                         global synchronisation; atomicMin on hop, where every writer of a round writes the same value).
+ *   hgt_trim_fill         same graph, seeds, n_layers and tmp, after hgt_trim_hops on the same stream.  Out: hop int32[N] (-1 = out),
+ *                         order int64[N] (the first n_rows[0] written), new_id int64[N] (-1 = dropped), edge_order int64[E] (the first
+ *                         n_edges[1] written), node_type_out int64[N] = node_type[order], edge_index_out int64[2][E] contiguous =
+ *                         new_id[edge_index[:, edge_order]], edge_type_out / edge_time_out int64[E] (edge_time NULL: none, and
+ *                         edge_time_out is not touched), out_rows int64[n_seeds] = new_id[seeds], counts int32[2 L + 2] on the device
+ *                         = {n_rows[0..L], n_edges[1..L], flag} and the same 8 L + 8 bytes in counts_host_pinned (one hipMemcpyAsync
+ *                         on `stream`: the caller waits for the stream before it reads them).  n_rows[k] = #{hop <= L - k},
+ *                         n_edges[l] = #{kept edges with hop[target] <= L - l}.  Flag bit 0 (HGT_TRIM_BAD_ID): a seed or an edge end
+ *                         outside [0, N); such a seed / edge is left out, every index written stays in range, and the caller discards
+ *                         the result.  6 launches: positions come from per-tile counts, one single-workgroup scan and wavefront
+ *                         ballots, never from an atomic -- every array is a function of the inputs alone.
+ *   All three: n_layers outside [1, HGT_TRIM_MAX_LAYERS], a negative size, N, E or n_seeds >= 2^31, a NULL pointer where the sizes say it
+ *   is read or written: HGT_ERR_INVALID_ARG; tmp_bytes too small: HGT_ERR_WORKSPACE; no launch.  N, E or n_seeds == 0 are valid.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_TRIM_MAX_LAYERS 8
+#define HGT_TRIM_BAD_ID 1
+int hgt_trim_tmp_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_layers, uint64_t* tmp_bytes_host);
+int hgt_trim_hops(const int64_t* edge_index, int64_t stride_row, int64_t stride_col, int64_t n_nodes, int64_t n_edges,
+                  const int64_t* seeds, int64_t n_seeds, int32_t n_layers, void* tmp, uint64_t tmp_bytes, void* stream);
+int hgt_trim_fill(const int64_t* edge_index, int64_t stride_row, int64_t stride_col, const int64_t* edge_type, const int64_t* edge_time,
+                  const int64_t* node_type, int64_t n_nodes, int64_t n_edges, const int64_t* seeds, int64_t n_seeds, int32_t n_layers,
+                  void* tmp, uint64_t tmp_bytes, int32_t* hop_out, int64_t* order, int64_t* new_id, int64_t* edge_order,
+                  int64_t* node_type_out, int64_t* edge_index_out, int64_t* edge_type_out, int64_t* edge_time_out, int64_t* out_rows,
+                  int32_t* counts, void* counts_host_pinned, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@ HGT_SAMPLER_MAX_NUMBER = 1024
 HGT_SAMPLER_HUB_DEG = 512
 HGT_SAMPLER_TIME_NONE = -2 ** 31
 HGT_SAMPLER_MAX_BATCH = 64
+HGT_TRIM_MAX_LAYERS = 8
 
 
 class HgtLayout(C.Structure):
@@ -291,6 +292,13 @@ SIGNATURES = {
     "hgt_graph_csr_build": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "hgt_neighbour_mean_bytes": (C.c_int, [_i64, _i32, C.POINTER(_u64)]),
     "hgt_neighbour_mean": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _u64, _vp]),
+    # seed-trimmed graphs (csrc/hgt_trim.hip): (N, E, L, tmp_bytes); (edge_index, stride_row, stride_col, N, E, seeds, n_seeds, L, tmp,
+    # tmp_bytes, stream); (edge_index, stride_row, stride_col, edge_type, edge_time, node_type, N, E, seeds, n_seeds, L, tmp, tmp_bytes,
+    # hop, order, new_id, edge_order, node_type_out, edge_index_out, edge_type_out, edge_time_out, out_rows, counts, counts_host, stream)
+    "hgt_trim_tmp_bytes": (C.c_int, [_i64, _i64, _i32, C.POINTER(_u64)]),
+    "hgt_trim_hops": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _u64, _vp]),
+    "hgt_trim_fill": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -108,28 +108,51 @@ class GNN(nn.Module):
             self._tiles_key = key
         return self._tiles
 
-    def forward(self, node_feature, node_type, edge_time, edge_index, edge_type):
-        """Same argument order as the reference (model.py:69): note edge_time comes third."""
+    def forward(self, node_feature, node_type, edge_time, edge_index, edge_type, seeds=None, trim=None):
+        """Same argument order as the reference (model.py:69): note edge_time comes third.
+
+        seeds (int64 device tensor of rows, any order, repeats allowed) or trim (a `TrimmedGraph` of `trim_to_seeds` for this graph and
+        this many layers): the seed-trimmed forward.  Every layer computes only the rows that can still reach a seed in the layers
+        left, and the result is the [len(seeds), n_hid] tensor of the seed rows -- what `forward(...)[seeds]` gives, up to the rounding
+        of another kernel route and row grouping.  Dropout masks are drawn over the trimmed rows: another draw than the untrimmed
+        step's.  With keep_att, layer l's `.att` is over the edges `trim.edge_order[:trim.n_edges[l]]`."""
         lib = _lib.load()
         if not node_feature.is_cuda:
             raise RuntimeError("pyhgt_amd.GNN runs only on a ROCm GPU tensor; there is no CPU fallback")
+        if seeds is not None or trim is not None:
+            return self._forward_trimmed(node_feature, node_type, edge_time, edge_index, edge_type, seeds, trim)
         conv0 = self.gcs[0].base_conv
         plan = GraphPlan.cached(node_type, edge_index, edge_type, edge_time if conv0.use_RTE else None,
                                 conv0.num_types, conv0.num_relations)
-        rows = plan.row_lists()
-        if torch.is_grad_enabled() and (node_feature.requires_grad or any(p.requires_grad for p in self.parameters())):
-            # training / differentiable path (SURVEY.md section 8f-2): the adapter through TypedLinearFunction (typed weight
-            # gradient kernels), tanh + dropout as in model.py:70-76, then the layers' own autograd path
-            from .autograd import TypedLinearFunction, takes_det_route
-            w = torch.stack([lin.weight for lin in self.adapt_ws]).float()
-            b = torch.stack([lin.bias for lin in self.adapt_ws]).float()
-            h = TypedLinearFunction.apply((rows.rows_all, rows.off_all, plan), self.num_types, conv0.precision,
-                                          node_feature.float(), w, b, takes_det_route(self))
-            h = self.drop(torch.tanh(h))        # rows of a type no adapter claims stay 0 (model.py:70)
+        if self._takes_grad(node_feature):
+            h = self._adapt_grad(node_feature, plan)
             for gc in self.gcs:
                 h = gc.base_conv(h, node_type, edge_index, edge_type, edge_time, plan=plan)
             return h
-        x = node_feature.detach().float().contiguous()
+        h = self._adapt(node_feature.detach().float().contiguous(), plan)
+        for gc in self.gcs:
+            h = gc.base_conv(h, node_type, edge_index, edge_type, edge_time, plan=plan)
+        return h
+
+    def _takes_grad(self, node_feature):
+        return torch.is_grad_enabled() and (node_feature.requires_grad or any(p.requires_grad for p in self.parameters()))
+
+    def _adapt_grad(self, node_feature, plan):
+        """The adapter on the rows of `plan`, differentiable: TypedLinearFunction (typed weight gradient
+        kernels), then tanh + dropout as in model.py:70-76."""
+        from .autograd import TypedLinearFunction, takes_det_route
+        rows = plan.row_lists()
+        w = torch.stack([lin.weight for lin in self.adapt_ws]).float()
+        b = torch.stack([lin.bias for lin in self.adapt_ws]).float()
+        h = TypedLinearFunction.apply((rows.rows_all, rows.off_all, plan), self.num_types, self.gcs[0].base_conv.precision,
+                                      node_feature.float(), w, b, takes_det_route(self))
+        return self.drop(torch.tanh(h))        # rows of a type no adapter claims stay 0 (model.py:70)
+
+    def _adapt(self, x, plan):
+        """The adapter on the rows of `plan` without autograd: x float32 [plan.N, in_dim], contiguous -> tanh(adapt_ws[type](x))."""
+        lib = _lib.load()
+        conv0 = self.gcs[0].base_conv
+        rows = plan.row_lists()
         N = x.size(0)
         w, b = self._pack_adapter()
         T, n_hid, in_dim = self.num_types, self.n_hid, self.in_dim
@@ -162,9 +185,52 @@ class GNN(nn.Module):
             _lib.check(lib.hgt_zero_rows(rows.rows_all, rows.off_all + 4 * T, n_hid, _ptr(h), st), "hgt_zero_rows")
         if need_tanh:
             _lib.check(lib.hgt_tanh_inplace(_ptr(h), N * n_hid, st), "hgt_tanh_inplace")
-        for gc in self.gcs:
-            h = gc.base_conv(h, node_type, edge_index, edge_type, edge_time, plan=plan)
         return h
+
+    def _forward_trimmed(self, node_feature, node_type, edge_time, edge_index, edge_type, seeds, trim):
+        """forward(..., seeds= / trim=): gather the rows the stack needs, the adapter on them, layer l on the rows and edges of its
+        prefix (the rectangular layer: n_q_rows = trim.n_rows[l]), the seed rows of the last layer's output."""
+        from .trim import TrimmedGraph, trim_to_seeds
+        L = len(self.gcs)
+        conv0 = self.gcs[0].base_conv
+        if seeds is not None and trim is not None:
+            raise ValueError("pyhgt_amd.GNN: pass seeds= or trim=, not both")
+        if trim is None:
+            trim = trim_to_seeds((node_type, edge_time, edge_index, edge_type), seeds, L, conv0.num_types, conv0.num_relations)
+        elif not isinstance(trim, TrimmedGraph):
+            raise TypeError("pyhgt_amd.GNN: trim must be a TrimmedGraph (pyhgt_amd.trim_to_seeds)")
+        if trim.n_layers != L:
+            raise ValueError("pyhgt_amd.GNN: the trim was built for %d layers, this stack has %d" % (trim.n_layers, L))
+        if trim.n_nodes != node_feature.size(0):
+            raise ValueError("pyhgt_amd.GNN: the trim was built for a graph of %d nodes, node_feature has %d rows"
+                             % (trim.n_nodes, node_feature.size(0)))
+        if trim.num_types is None:
+            trim.num_types, trim.num_relations = conv0.num_types, conv0.num_relations
+        if conv0.use_RTE and trim.edge_time is None:
+            raise ValueError("use_RTE=True needs edge_time (conv.py:91-92)")
+        grad = self._takes_grad(node_feature)
+        n0, S = trim.n_rows[0], trim.n_seeds
+        if n0 == 0:                                  # no seed: no row, no layer
+            return torch.zeros(S, self.n_hid, dtype=torch.float32, device=node_feature.device)
+        lib = _lib.load()
+        if grad:
+            h = self._adapt_grad(node_feature[trim.order], trim.plan(1, conv0.use_RTE))
+        else:
+            x = node_feature.detach().float()
+            x = x if x.stride(1) == 1 else x.contiguous()
+            xs = torch.empty(n0, self.in_dim, dtype=torch.float32, device=x.device)
+            _lib.check(lib.hgt_gather_rows(_ptr(x), x.stride(0), _ptr(trim.order32), n0, self.in_dim, _ptr(xs), _stream()),
+                       "hgt_gather_rows(trim)")
+            h = self._adapt(xs, trim.plan(1, conv0.use_RTE))
+        for l, gc in enumerate(self.gcs, start=1):
+            nt, ei, et, tm = trim.layer_graph(l)
+            h = gc.base_conv(h, nt, ei, et, tm, plan=trim.plan(l, gc.base_conv.use_RTE), n_q_rows=trim.n_rows[l])
+        if grad:
+            return h[trim.out_rows]
+        out = torch.empty(S, self.n_hid, dtype=torch.float32, device=h.device)
+        _lib.check(lib.hgt_gather_rows(_ptr(h), h.stride(0), _ptr(trim.out_rows32), S, self.n_hid, _ptr(out), _stream()),
+                   "hgt_gather_rows(seeds)")
+        return out
 
 
 def _det(module):

@@ -8,7 +8,14 @@ target-sorted runs, edge_time in [111, 129], min in-degree 1), handed over once 
 --stack B[,B...] [--out FILE]: instead, stacked batches (pyhgt_amd.sampled.stack_device_graphs): for every B, B pieces of the c3
 shape (one layer) and of the c5 shape (2-layer GNN) run as ONE block-diagonal graph against the same B pieces run one after the
 other, in one process, alternating, medians of 5 windows: us per piece and layer for both, and the time of stack_device_graphs
-itself (hgt_stack_sorted + feature gather + plan).  The JSON goes to stdout and, with --out, to FILE."""
+itself (hgt_stack_sorted + feature gather + plan).  The JSON goes to stdout and, with --out, to FILE.
+
+--trim [--batches 1,16] [--papers 50000] [--only WORKLOAD] [--out FILE]: instead, the seed-trimmed eval forward (GNN.forward(seeds=))
+against the untrimmed one read at the seed rows, on the three sampler workloads of tools/bench_sampler.py drawn by the device sampler,
+with the README's 4-layer MAG and 2-layer OAG models: alternating windows of ~0.3 s in one process after a warm-up of both, median and
+min-max of 5; the trimmed time includes the trim and its plan builds, which are also timed alone.  FILE keeps one JSON object; this
+run fills its "eval_forward" (tools/bench_train.py --trim fills the training step and the memory).  --kernels-only: only repeated
+trims, for a `rocprofv3 --kernel-trace --stats` run of their launches."""
 import json
 import os
 import statistics
@@ -93,8 +100,129 @@ def stack_bench(dev, Bs, out_path=None, precs=("bf16x3", "f16x3")):
     return res
 
 
+# ------------------------------------------------------------------------------------------------ --trim: the seed-trimmed forward
+TRIM_MODELS = {      # the README's models, by the schema of the workload they run on
+    "mag": dict(in_dim=129, n_hid=512, H=8, L=4, norm=True),       # the published 4-layer ogbn-mag model
+    "oag": dict(in_dim=1169, n_hid=400, H=8, L=2, norm=False),     # the 2-layer OAG model
+}
+
+
+def trim_cases(dev, papers, Bs, only=None):
+    """The three sampler workloads of tools/bench_sampler.py (128 seed papers, depth 6), drawn by the device sampler on the synthetic
+    resident graphs of examples/train_device_sampler.py: yields (workload, B, graph, seed rows, model spec) for B = 1 (one batch with
+    its plan, as sample_subgraph_device hands it over) and B > 1 (one sample_subgraphs_device call, stacked)."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    from bench_sampler import WORKLOADS
+    from pyhgt_amd import sample_subgraph_device, sample_subgraphs_device
+    from pyhgt_amd.sampled import stack_device_graphs
+    from train_device_sampler import resident_graph
+    for name, (schema, depth, width, max_time) in WORKLOADS.items():
+        if only and name not in only:
+            continue
+        m = TRIM_MODELS[schema]
+        dgraph, n_nodes = resident_graph(schema, papers, m["in_dim"], dev, seed=1, mean_degree=3.0)
+        rng = np.random.default_rng(7)
+        for B in Bs:
+            inps = [{"paper": np.stack([rng.choice(n_nodes["paper"], 128, replace=False), np.full(128, 2015)], axis=1)} for _ in range(B)]
+            keys = [1000 + b for b in range(B)]
+            if B == 1:
+                g = sample_subgraph_device(dgraph, max_time, depth, width, inps[0], seed=keys[0])
+                rows = g.seed_rows("paper")
+            else:
+                g = stack_device_graphs(sample_subgraphs_device(dgraph, max_time, depth, width, inps, keys, plan=False))
+                rows = torch.cat([g.rows(b, "paper", torch.arange(128)) for b in range(B)])
+            yield name, B, g, rows, m
+            del g
+        del dgraph
+        GraphPlan.clear_cache()
+        torch.cuda.empty_cache()
+
+
+def trim_shares(t, N, E):
+    """rows x layers and edges x layers the trimmed stack still computes, against the untrimmed stack"""
+    L = t.n_layers
+    return {"nodes": N, "edges": E, "rows_per_stage": list(t.n_rows), "edges_per_layer": list(t.n_edges[1:]),
+            "row_share": round(sum(t.n_rows[1:]) / max(1, L * N), 4), "edge_share": round(sum(t.n_edges[1:]) / max(1, L * E), 4)}
+
+
+def alternating_spread(fns, window_s=0.3, windows=5, warm=5):
+    """Per function {median_us, min_us, max_us, iters}: a warm-up of all, then `windows` timed windows of each, interleaved; a window
+    repeats the call until it lasts about window_s."""
+    for fn in fns:
+        for _ in range(warm):
+            fn()
+    iters = [max(3, int(window_s * 1e6 / max(timeit(fn, iters=3, warm=0), 1.0))) for fn in fns]
+    samples = [[] for _ in fns]
+    for _ in range(windows):
+        for i, fn in enumerate(fns):
+            samples[i].append(timeit(fn, iters=iters[i], warm=0))
+    return [{"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1), "iters": n}
+            for v, n in zip(samples, iters)]
+
+
+def trim_verdict(untrimmed, trimmed):
+    """"pays" only where the trimmed median lies below the untrimmed one by more than the two min-max spreads together"""
+    spread = (untrimmed["max_us"] - untrimmed["min_us"]) + (trimmed["max_us"] - trimmed["min_us"])
+    return {"ratio_trimmed_over_untrimmed": round(trimmed["median_us"] / untrimmed["median_us"], 3),
+            "pays": bool(trimmed["median_us"] < untrimmed["median_us"] - spread)}
+
+
+def merge_out(out_path, key, value):
+    """FILE holds one JSON object; this run's part goes under `key`, the other tool's part stays"""
+    res = {}
+    if out_path and os.path.exists(out_path):
+        with open(out_path) as f:
+            res = json.load(f)
+    res[key] = value
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+def trim_bench(dev, Bs, papers, out_path=None, only=None, kernels_only=False):
+    """--trim: the eval forward read at the seed rows, untrimmed (plan cached) against trimmed (gnn(..., seeds=rows): the trim, its L
+    plan builds and the forward), with the trim alone and the trim with its plans beside them."""
+    from pyhgt_amd import trim_to_seeds
+    res = {"papers": papers, "seeds": 128, "depth": 6, "unit": "us per call: median, min and max of 5 alternating windows of ~0.3 s", "cases": []}
+    for name, B, g, rows, m in trim_cases(dev, papers, Bs, only):
+        T, R, L = len(g[5]), len(g[6]), m["L"]
+        if kernels_only:                                    # under rocprofv3 --kernel-trace --stats: the trim's own launches
+            for _ in range(20):
+                trim_to_seeds(g, rows, L)
+            continue
+        gnn = GNN(m["in_dim"], m["n_hid"], T, R, m["H"], L, prev_norm=m["norm"], last_norm=m["norm"], use_RTE=True).eval().to(dev)
+
+        def plans():
+            t = trim_to_seeds(g, rows, L)
+            for l in range(1, L + 1):
+                t.plan(l, True)
+        with torch.no_grad():
+            u, t, alone, with_plans = alternating_spread([lambda: gnn(g[0], g[1], g[2], g[3], g[4])[rows],
+                                                          lambda: gnn(g[0], g[1], g[2], g[3], g[4], seeds=rows),
+                                                          lambda: trim_to_seeds(g, rows, L), plans])
+            err = (gnn(g[0], g[1], g[2], g[3], g[4])[rows] - gnn(g[0], g[1], g[2], g[3], g[4], seeds=rows)).abs().max().item()
+        case = {"workload": name, "B": B, "layers": L, "n_hid": m["n_hid"], **trim_shares(trim_to_seeds(g, rows, L), g[1].numel(), g[4].numel()),
+                "untrimmed": u, "trimmed": t, "trim_alone": alone, "trim_and_plans": with_plans, "max_abs_diff": err, **trim_verdict(u, t)}
+        res["cases"].append(case)
+        print("%s x %2d  %d layers: untrimmed %.0f us [%.0f, %.0f], trimmed %.0f us [%.0f, %.0f] (trim %.0f, with plans %.0f), row share "
+              "%.2f, edge share %.2f, pays: %s" % (name, B, L, u["median_us"], u["min_us"], u["max_us"], t["median_us"], t["min_us"],
+                                                   t["max_us"], alone["median_us"], with_plans["median_us"], case["row_share"],
+                                                   case["edge_share"], case["pays"]), flush=True)
+        del gnn
+    if not kernels_only:
+        merge_out(out_path, "eval_forward", res)
+    return res
+
+
 def main():
     dev = "cuda:0"
+    if "--trim" in sys.argv:
+        arg = lambda k, d: sys.argv[sys.argv.index(k) + 1] if k in sys.argv else d
+        trim_bench(dev, [int(v) for v in arg("--batches", "1,16").split(",")], int(arg("--papers", "50000")), arg("--out", None),
+                   arg("--only", None), "--kernels-only" in sys.argv)
+        return
     if "--stack" in sys.argv:
         Bs = [int(v) for v in sys.argv[sys.argv.index("--stack") + 1].split(",")]
         stack_bench(dev, Bs, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)

@@ -14,7 +14,12 @@ B stacked batches (pyhgt_amd.sampled.stack_device_graphs) against the same B bat
 alternating, medians of 5 windows: ms per piece.
 --optimizer {none,torch,device} (default none: the numbers above do not move): the sampled-batch steps end in an optimizer step over
 the module's parameters -- torch: clip_grad_norm_(0.5) + torch.optim.AdamW; device: pyhgt_amd.AdamW(max_norm=0.5) -- so that three runs
-give the share of a step the optimizer is (tools/bench_optimizer.py times the optimizer step alone)."""
+give the share of a step the optimizer is (tools/bench_optimizer.py times the optimizer step alone).
+--trim [--batches 1,16] [--papers 50000] [--only WORKLOAD] [--out FILE]: instead, the training step of the seed-trimmed forward
+(GNN.forward(seeds=), the trim and its plan builds inside the step) against the untrimmed step read at the seed rows, on the sampler
+workloads and models of tools/bench_small.py --trim, alternating windows of ~0.3 s, median and min-max of 5; and
+torch.cuda.max_memory_allocated() / the memory kept after the forward of a 4-layer step in both forms.  FILE keeps one JSON object;
+this run fills its "training_step"."""
 import json
 import os
 import sys
@@ -337,8 +342,59 @@ def recompute_compare(dev, out_path=None, warmup=5, iters=20):
     return res
 
 
+def trim_step(dev, Bs, papers, out_path=None, only=None):
+    """--trim: the training step (forward + backward of the seed rows, dropout on, gradients dropped) untrimmed against trimmed
+    (GNN.forward(seeds=): the trim and its plan builds inside the timed step), on the workloads and models of tools/bench_small.py
+    --trim, and peak / kept memory of a step of the 4-layer model in both forms."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from bench_small import alternating_spread, merge_out, trim_cases, trim_shares, trim_verdict
+    from pyhgt_amd import GNN, trim_to_seeds
+    res = {"papers": papers, "seeds": 128, "depth": 6, "deterministic": DETERMINISTIC, "cases": [],
+           "unit": "us per step: median, min and max of 5 alternating windows of ~0.3 s; memory in MB above what was allocated before the step"}
+    for name, B, g, rows, m in trim_cases(dev, papers, Bs, only):
+        T, R, L = len(g[5]), len(g[6]), m["L"]
+        gnn = GNN(m["in_dim"], m["n_hid"], T, R, m["H"], L, 0.2, "hgt", m["norm"], m["norm"], True, deterministic=DETERMINISTIC).to(dev).train()
+        params = list(gnn.parameters())
+
+        def step(trimmed):
+            out = gnn(g[0], g[1], g[2], g[3], g[4], seeds=rows) if trimmed else gnn(g[0], g[1], g[2], g[3], g[4])[rows]
+            out.backward(torch.ones_like(out))
+            for p_ in params:
+                p_.grad = None
+        u, t = alternating_spread([lambda: step(False), lambda: step(True)])
+        case = {"workload": name, "B": B, "layers": L, "n_hid": m["n_hid"], **trim_shares(trim_to_seeds(g, rows, L), g[1].numel(), g[4].numel()),
+                "untrimmed": u, "trimmed": t, **trim_verdict(u, t)}
+        if L == 4:
+            for key, trimmed in (("untrimmed", False), ("trimmed", True)):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                out = gnn(g[0], g[1], g[2], g[3], g[4], seeds=rows) if trimmed else gnn(g[0], g[1], g[2], g[3], g[4])[rows]
+                torch.cuda.synchronize()
+                kept = torch.cuda.memory_allocated() - base
+                out.backward(torch.ones_like(out))
+                torch.cuda.synchronize()
+                case[key]["kept_after_forward_mb"] = round(kept / 1e6, 2)
+                case[key]["peak_mb"] = round((torch.cuda.max_memory_allocated() - base) / 1e6, 2)
+                del out
+                for p_ in params:
+                    p_.grad = None
+        res["cases"].append(case)
+        print("%s x %2d  %d layers: training step untrimmed %.0f us [%.0f, %.0f], trimmed %.0f us [%.0f, %.0f], pays: %s%s"
+              % (name, B, L, u["median_us"], u["min_us"], u["max_us"], t["median_us"], t["min_us"], t["max_us"], case["pays"],
+                 "" if L != 4 else ", peak %.1f -> %.1f MB, kept %.1f -> %.1f MB" % (u["peak_mb"], t["peak_mb"], u["kept_after_forward_mb"],
+                                                                                 t["kept_after_forward_mb"])), flush=True)
+        del gnn, params
+    merge_out(out_path, "training_step", res)
+    return res
+
+
 def main():
     dev = "cuda:0"
+    if "--trim" in sys.argv:
+        arg = lambda k, d: sys.argv[sys.argv.index(k) + 1] if k in sys.argv else d
+        trim_step(dev, [int(v) for v in arg("--batches", "1,16").split(",")], int(arg("--papers", "50000")), arg("--out", None), arg("--only", None))
+        return
     if "--recompute" in sys.argv:
         recompute_compare(dev, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
         return
