@@ -1320,6 +1320,67 @@ int hgt_trim_fill(const int64_t* edge_index, int64_t stride_row, int64_t stride_
                   int64_t* node_type_out, int64_t* edge_index_out, int64_t* edge_type_out, int64_t* edge_time_out, int64_t* out_rows,
                   int32_t* counts, void* counts_host_pinned, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Whole-graph view of a resident graph (csrc/hgt_graph_view.hip): the CSRs of every meta triple -> the wire format of to_torch
+ * (pyHGT/data.py:212-256) over all nodes and all, or the kept, edges.  Added under ABI 8 (new symbols only).
+ * pyhgt_amd.view.np_whole_graph is the definition.
+ *
+ *   the table             hgt_view_triple[n_triples + 1] in DEVICE memory, built by the caller: the triples ordered by (relation id,
+ *                         target type), then one entry for the self run.  Per triple: the CSR (indptr int32[n_rows + 1], src, time with
+ *                         HGT_SAMPLER_TIME_NONE = none; time may be NULL = all none), the leave-out flags over the target / source
+ *                         type's nodes (uint8, non-zero = the entries at that node are dropped; NULL = none), the node times of the two
+ *                         types (int32; both NULL or both set), `first` = the entries of the triples in front, n_rows = the target type's
+ *                         nodes, the two types' first global rows and the relation id in [0, n_relations).  The last entry has first =
+ *                         the CSR entries of all triples, n_rows = N and rel_id = the id of `self`; its pointers are not read.
+ *                         n_entries = all CSR entries + N with self loops, = all CSR entries without.  The CSRs are trusted (rows
+ *                         ascending, ids in range), as the sampler trusts them.
+ *   the order             entry e of triple m is position p = e - first of its CSR: source src_off + src[p] -> target tgt_off + row(p);
+ *                         the self run is i -> i for i in [0, N).  The kept entries keep this order.  A wavefront owns
+ *                         HGT_VIEW_TILE consecutive entries (a workgroup four such tiles); it finds a row by one binary search of indptr
+ *                         per triple it enters and walks from there.
+ *   the filter            (filtered != 0) an entry with stored time t is kept iff t <= max_time (has_max_time != 0; a TIME_NONE entry
+ *                         takes tgt_time[row] under the same test, and is kept where there is none) and neither flag is set; self entries
+ *                         are always kept.  filtered == 0: nothing is tested, positions = entry indices, ONE launch.  filtered: count
+ *                         per tile, one single-workgroup scan, fill -- positions from the scan and wavefront ballots, never from an
+ *                         atomic.
+ *   hgt_view_tmp_bytes    *tmp_bytes_host = the device scratch of a filtered build (4 bytes per tile; host arithmetic).
+ *   hgt_view_build        Out: src32 / dst32 int32[n_entries] and, with has_time, time32 = tgt_time[row] - src_time[src] + 120 (120
+ *                         on a self entry; NOT clamped to [0, 240), only saturated to int32).  Every output array has room for
+ *                         n_entries elements; a filtered build writes only the first rel_ptr[n_relations] elements of each.  With
+ *                         edge_index != NULL the reference's int64 tensors come out of the same pass: sources at edge_index[pos],
+ *                         targets at edge_index[edge_index_stride + pos], edge_type, edge_time (has_time).  rel_ptr int32[n_relations
+ *                         + 2]: rel_ptr[r] = the first kept position of relation id r, rel_ptr[n_relations] = the kept entries, then
+ *                         the flag word; head_host_pinned (may be NULL) receives the same 4 (n_relations + 2) bytes by one
+ *                         hipMemcpyAsync on `stream`.  Flag bit 0 (HGT_VIEW_BAD_TIME): a kept entry's time difference is outside
+ *                         [0, 240); the value stands in time32 / edge_time as it is, so hgt_plan_from_sorted and hgt_plan_build flag
+ *                         the same edges in the plan header (the reference's IndexError).
+ *   Both: NULL table / rel_ptr, a NULL output that n_entries > 0 (and has_time) says is written, edge_index without edge_type (or
+ *   without edge_time under has_time) or with a stride below n_entries, NULL tmp for a filtered build, a negative size, n_entries
+ *   >= 2^31 - 1, n_triples > HGT_SAMPLER_MAX_TRIPLES, n_relations outside [1, HGT_SAMPLER_MAX_TRIPLES + 1]: HGT_ERR_INVALID_ARG;
+ *   tmp_bytes too small: HGT_ERR_WORKSPACE; no launch.  n_entries == 0, empty triples and types without nodes are valid.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_VIEW_TILE 512
+#define HGT_VIEW_BAD_TIME 1
+typedef struct hgt_view_triple {
+    const int32_t* indptr;
+    const int32_t* src;
+    const int32_t* time;
+    const uint8_t* tgt_flags;
+    const uint8_t* src_flags;
+    const int32_t* tgt_time;
+    const int32_t* src_time;
+    int64_t first;
+    int32_t n_rows;
+    int32_t tgt_off;
+    int32_t src_off;
+    int32_t rel_id;
+} hgt_view_triple;
+int hgt_view_tmp_bytes(int64_t n_entries, uint64_t* tmp_bytes_host);
+int hgt_view_build(const hgt_view_triple* table_dev, int32_t n_triples, int32_t n_relations, int64_t n_entries, int32_t filtered,
+                   int32_t has_max_time, int32_t max_time, int32_t has_time, int32_t* src32, int32_t* dst32, int32_t* time32,
+                   int64_t* edge_index, int64_t edge_index_stride, int64_t* edge_type, int64_t* edge_time, int32_t* rel_ptr, void* tmp,
+                   uint64_t tmp_bytes, void* head_host_pinned, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,8 @@ HGT_SAMPLER_HUB_DEG = 512
 HGT_SAMPLER_TIME_NONE = -2 ** 31
 HGT_SAMPLER_MAX_BATCH = 64
 HGT_TRIM_MAX_LAYERS = 8
+HGT_VIEW_TILE = 512          # entries of the whole-graph view's entry space one wavefront takes (a workgroup takes four such tiles)
+HGT_VIEW_BAD_TIME = 1
 
 
 class HgtLayout(C.Structure):
@@ -103,6 +105,12 @@ class HgtSamplerMask(C.Structure):
 
 class HgtGraphCsr(C.Structure):
     _fields_ = [("indptr", C.c_void_p), ("nbr", C.c_void_p)]
+
+
+class HgtViewTriple(C.Structure):
+    _fields_ = [("indptr", C.c_void_p), ("src", C.c_void_p), ("time", C.c_void_p), ("tgt_flags", C.c_void_p), ("src_flags", C.c_void_p),
+                ("tgt_time", C.c_void_p), ("src_time", C.c_void_p), ("first", C.c_int64), ("n_rows", C.c_int32), ("tgt_off", C.c_int32),
+                ("src_off", C.c_int32), ("rel_id", C.c_int32)]
 
 
 GRAPH_MEAN_CHUNK = 256      # HGT_GRAPH_MEAN_CHUNK: the most terms of a row one wavefront of hgt_neighbour_mean adds
@@ -299,6 +307,11 @@ SIGNATURES = {
     "hgt_trim_hops": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _u64, _vp]),
     "hgt_trim_fill": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _vp]),
+    # whole-graph view (csrc/hgt_graph_view.hip): (n_entries, tmp_bytes); (table_dev, n_triples, n_relations, n_entries, filtered,
+    # has_max_time, max_time, has_time, src32, dst32, time32, edge_index, edge_index_stride, edge_type, edge_time, rel_ptr, tmp,
+    # tmp_bytes, head_host_pinned, stream)
+    "hgt_view_tmp_bytes": (C.c_int, [_i64, C.POINTER(_u64)]),
+    "hgt_view_build": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
 }
 
 _lib = None

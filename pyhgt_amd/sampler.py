@@ -233,6 +233,20 @@ class DeviceHeteroGraph:
         from .graph_build import build_from_edge_lists
         return build_from_edge_lists(cls, types, n_nodes, edges, edge_time, node_time, features, device, reverse)
 
+    def whole_graph(self, node_time=None, max_time=None, leave_out=None, self_loops=True, plan=True):
+        """The graph as the model's input, with no sampling: the 7-tuple of `to_torch` (node_feature, node_type, edge_time, edge_index,
+        edge_type, node_dict, edge_dict) over ALL nodes and all edges -- or those that max_time ("the graph as of year Y") and
+        leave_out (label edges) keep.  pyhgt_amd/view.py has the rule (`np_whole_graph`) and the arguments.  On a device graph: a
+        `_DeviceGraph` built on the device from the CSRs (csrc/hgt_graph_view.hip; nothing is copied to the host, an unfiltered view
+        reads nothing back, a filtered one reads rel_ptr and a flag word once), with `.sorted`, `.plan` (plan=True: built by
+        `GraphPlan.from_sorted` and registered, so the first layer's lookup hits), `.rows(type, ids=None)` and `.type_rows(type)`;
+        node_feature is the types' resident feature matrices concatenated in type order (ValueError: a type with nodes and no
+        features, or differing widths).  On a host-only graph: the numpy definition's tuple as CPU tensors.
+        `gnn(*view[:5])[view.type_rows("paper")]` are the embeddings of all papers; `gnn(*view[:5], seeds=view.rows("paper", ids))`
+        is the exact output at those nodes."""
+        from .view import whole_graph
+        return whole_graph(self, node_time, max_time, leave_out, self_loops, plan)
+
     def get_types(self):
         return list(self.types)
 
