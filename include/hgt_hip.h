@@ -1381,6 +1381,117 @@ int hgt_view_build(const hgt_view_triple* table_dev, int32_t n_triples, int32_t 
                    int64_t* edge_index, int64_t edge_index_stride, int64_t* edge_type, int64_t* edge_time, int32_t* rel_ptr, void* tmp,
                    uint64_t tmp_bytes, void* head_host_pinned, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Exact L-hop neighbourhood of a seed set from the resident graph (csrc/hgt_neighbourhood.hip): a frontier walk over the in-edge
+ * CSRs whose result stands in the seed trim's hop-major order.  Added under ABI 8 (new symbols only).
+ * pyhgt_amd.neighbourhood.np_neighbourhood is the definition: array for array the whole-graph view, trimmed to the seeds.
+ *
+ *   the tables            hgt_nb_type[n_types] and hgt_nb_triple[n_triples] in DEVICE memory (the triples ordered by (relation id,
+ *                         target type), as in the view); hgt_nb_expand / hgt_nb_fill take the triple table once more in HOST memory,
+ *                         of which they read only tgt_type / src_type.  Per type: the RESIDENT mark array (int32[n_nodes], -1
+ *                         everywhere between calls; during a call HGT_NB_CLAIMED, then the node's new row), the type's first view
+ *                         row, its feature matrix (float32, leading dimension ld; read by hgt_nb_finish only).  Per triple: the CSR,
+ *                         the leave-out flags and the node times as in hgt_view_triple.  The CSRs are trusted.
+ *   the head              int64[HGT_NB_HEAD_WORDS] in device memory: [HGT_NB_HEAD_N] the size of the level that was numbered last, [_DEG] / [_CHUNKS] the CSR entries / the chunks of that level's
+ *                         rows over the triples into their types (summed only under `expand`), [_KEPT] the kept entries of the
+ *                         level that was expanded last, [_FLAGS] HGT_NB_BAD_SEED | HGT_NB_BAD_TIME, [_TYPE_BEGIN + t, _TYPE_END + t)
+ *                         the rows of type t inside the level that was numbered last (both 0 for a type without rows).  The
+ *                         caller copies it to the host once per level: that is the only synchronisation of a call, L + 1 reads at
+ *                         the most for L layers.
+ *   a call                hgt_nb_seeds; hgt_nb_number (level 0); read.  Then per level h < L with rows: hgt_nb_expand (h);
+ *                         hgt_nb_number (h + 1, capacity = the level's CSR entries, skipped when there are none); hgt_nb_fill (h);
+ *                         read.  Then hgt_nb_finish and, per level, hgt_nb_reset.  All on one stream.  Calls on one graph are NOT
+ *                         reentrant: they share the marks.  Launches, the radix sort's own kernels aside (one sort per numbered
+ *                         level): 5 for level 0 (head reset, memset, claim, head reset, numbering), 11 per expanded level (head reset,
+ *                         memset, chunks and entries per item, two scans, count + claim, scan, head reset, numbering, fill, self
+ *                         loops), 2 for hgt_nb_finish, 1 reset per numbered level (at most L + 1): 8 + 12 L at the most.  No grid, loop
+ *                         or scratch size is proportional to the graph's N or E.
+ *   hgt_nb_seeds          zeroes the head; a seed (seed_type int32, seed_id int64) outside its type's nodes sets HGT_NB_BAD_SEED and
+ *                         claims nothing; every other seed claims its node (integer compare-and-swap -1 -> HGT_NB_CLAIMED), the
+ *                         winner writes its key (type << 32 | id) to cand[s], its own slot of cand[n_seeds] (filled with all-ones
+ *                         keys first): no counter.
+ *   hgt_nb_number         radix-sorts cand[capacity] into keys_out[capacity] (rocPRIM; sort_tmp of hgt_nb_sort_bytes); the keys that
+ *                         are not all-ones are the level, their count goes to head[_N], and row i of them gets mark = row_base + i, order_out[i] = the node's view row,
+ *                         node_type_out[i], row_id_out[i]; the type ranges and, with expand != 0, the entry and chunk totals go to the
+ *                         head.  The ORDER of a level is the sort's, never an atomic's.
+ *   hgt_nb_expand         level h: chunks per item (an item = (row of the level, triple into its type), triple-major; a row of d
+ *                         entries has ceil(d / HGT_NB_CHUNK) chunks) and entries per item, their single-workgroup scans into
+ *                         item_chunks[n_items + 1] / item_entries[n_items + 1], then one wavefront per chunk: the kept entries of the
+ *                         chunk into chunk_cnt, the sources of the kept entries claimed, a winner's key written to the slot of its
+ *                         own entry in cand[capacity] (entries in front of the item + place in the row; all-ones keys elsewhere);
+ *                         chunk_cnt[n_chunks + 1] scanned, its total in head[_KEPT].
+ *                         n_chunks must be head[_CHUNKS] as read, capacity >= head[_DEG], type_begin / type_end (host, int64[n_types])
+ *                         the head's ranges.  n_chunks == 0: only head[_N] = head[_KEPT] = 0.
+ *   hgt_nb_fill           level h again, after hgt_nb_number of level h + 1: the kept entries in (triple, row, stored) order to
+ *                         src_out (the source's new row, from its mark) / dst_out (row_base + the row's place in its level) /
+ *                         edge_type_out / edge_time_out (has_time: tgt_time - src_time + 120; outside [0, 240) sets
+ *                         HGT_NB_BAD_TIME), positions from the scan and wavefront ballots; with self_loops the level's loops follow
+ *                         at [head[_KEPT], + n_level).  Every output has edge_capacity >= head[_DEG] (+ n_level) elements.
+ *   hgt_nb_finish         feature_out[n_rows, width] = the rows' feature rows (node_type / row_id as hgt_nb_number wrote them);
+ *                         out_rows[s] = the mark of seed s.
+ *   hgt_nb_reset          mark = -1 at every key of keys[n] that is not all-ones: the end of a call and its error paths.
+ *   All: a NULL table or head, n_types outside [1, HGT_SAMPLER_MAX_TYPES], n_triples outside [0, HGT_SAMPLER_MAX_TRIPLES], a
+ *   negative size or one >= 2^31 - 1, a NULL array the sizes say is read or written, type ranges outside the level, a triple type
+ *   outside [0, n_types): HGT_ERR_INVALID_ARG; sort_bytes too small: HGT_ERR_WORKSPACE; no launch.  hgt_nb_sort_bytes asks rocPRIM,
+ *   which answers by the device's architecture: without a device it (and hgt_nb_number with valid arguments and sort_bytes >= 256)
+ *   returns HGT_ERR_LAUNCH; sort_bytes < 256 is refused as HGT_ERR_WORKSPACE before the question.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_NB_CHUNK 1024          /* entries of a row one wavefront takes; a longer row is split */
+#define HGT_NB_WAVE_ROWS 64        /* rows of a level whose entry and chunk totals one wavefront of the numbering kernel sums (the
+                                    * wavefront width: one atomic add per that many rows) */
+#define HGT_NB_CLAIMED (-2)
+#define HGT_NB_BAD_SEED 1
+#define HGT_NB_BAD_TIME 2
+#define HGT_NB_HEAD_N 0
+#define HGT_NB_HEAD_DEG 1
+#define HGT_NB_HEAD_CHUNKS 2
+#define HGT_NB_HEAD_KEPT 3
+#define HGT_NB_HEAD_FLAGS 4
+#define HGT_NB_HEAD_TYPE_BEGIN 8
+#define HGT_NB_HEAD_TYPE_END 24
+#define HGT_NB_HEAD_WORDS 40
+typedef struct hgt_nb_type {
+    int32_t* mark;
+    const float* feat;
+    int64_t ld;
+    int64_t row_off;
+    int32_t n_nodes;
+    int32_t reserved;
+} hgt_nb_type;
+typedef struct hgt_nb_triple {
+    const int32_t* indptr;
+    const int32_t* src;
+    const int32_t* time;
+    const uint8_t* tgt_flags;
+    const uint8_t* src_flags;
+    const int32_t* tgt_time;
+    const int32_t* src_time;
+    int32_t tgt_type;
+    int32_t src_type;
+    int32_t rel_id;
+    int32_t reserved;
+} hgt_nb_triple;
+int hgt_nb_constants(int32_t* chunk, int32_t* wave_rows, int32_t* head_words);
+int hgt_nb_sort_bytes(int64_t capacity, int32_t n_types, uint64_t* bytes_host);
+int hgt_nb_seeds(const hgt_nb_type* types_dev, int32_t n_types, const int32_t* seed_type, const int64_t* seed_id, int64_t n_seeds,
+                 uint64_t* cand, int64_t* head, void* stream);
+int hgt_nb_number(const hgt_nb_type* types_dev, int32_t n_types, const hgt_nb_triple* triples_dev, int32_t n_triples,
+                  const uint64_t* cand, int64_t capacity, uint64_t* keys_out, void* sort_tmp, uint64_t sort_bytes, int64_t row_base,
+                  int32_t expand, int64_t* order_out, int64_t* node_type_out, int64_t* row_id_out, int64_t* head, void* stream);
+int hgt_nb_expand(const hgt_nb_type* types_dev, int32_t n_types, const hgt_nb_triple* triples_dev, const hgt_nb_triple* triples_host,
+                  int32_t n_triples, const uint64_t* keys, const int64_t* type_begin_host, const int64_t* type_end_host, int64_t n_level,
+                  int64_t n_chunks, int32_t has_max_time, int32_t max_time, int32_t* item_chunks, int32_t* item_entries, int32_t* chunk_cnt,
+                  uint64_t* cand, int64_t capacity, int64_t* head, void* stream);
+int hgt_nb_fill(const hgt_nb_type* types_dev, int32_t n_types, const hgt_nb_triple* triples_dev, const hgt_nb_triple* triples_host,
+                int32_t n_triples, const uint64_t* keys, const int64_t* type_begin_host, const int64_t* type_end_host, int64_t n_level,
+                int64_t n_chunks, int32_t has_max_time, int32_t max_time, int32_t has_time, int32_t self_loops, int32_t rel_self,
+                int64_t row_base, const int32_t* item_chunks, int32_t* chunk_cnt, int64_t* src_out, int64_t* dst_out,
+                int64_t* edge_type_out, int64_t* edge_time_out, int64_t edge_capacity, int64_t* head, void* stream);
+int hgt_nb_finish(const hgt_nb_type* types_dev, int32_t n_types, const int64_t* node_type, const int64_t* row_id, int64_t n_rows,
+                  int32_t width, float* feature_out, const int32_t* seed_type, const int64_t* seed_id, int64_t n_seeds, int64_t* out_rows,
+                  void* stream);
+int hgt_nb_reset(const hgt_nb_type* types_dev, int32_t n_types, const uint64_t* keys, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

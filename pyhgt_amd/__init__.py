@@ -16,6 +16,7 @@ from .optim import AdamW, np_adamw_step  # noqa: F401
 from .graph_build import np_edge_lists_to_csr, neighbour_mean, np_neighbour_mean  # noqa: F401
 from .trim import np_trim_to_seeds, np_trim_graph, trim_to_seeds, TrimmedGraph  # noqa: F401
 from .view import np_whole_graph, label_edge_flags  # noqa: F401
+from .neighbourhood import np_neighbourhood, NeighbourhoodGraph, NeighbourhoodArrays  # noqa: F401
 
 __all__ = ["HGTConv", "DenseHGTConv", "GeneralConv", "RelTemporalEncoding", "GraphPlan", "install_into", "GNN", "Classifier", "Matcher",
            "set_deterministic", "set_recompute", "DeviceHeteroGraph", "sample_subgraph_device", "sample_subgraph_host", "sample_subgraphs_device",

@@ -45,6 +45,11 @@ HGT_SAMPLER_MAX_BATCH = 64
 HGT_TRIM_MAX_LAYERS = 8
 HGT_VIEW_TILE = 512          # entries of the whole-graph view's entry space one wavefront takes (a workgroup takes four such tiles)
 HGT_VIEW_BAD_TIME = 1
+HGT_NB_CHUNK = 1024          # entries of a row one wavefront of the neighbourhood walk takes; a longer row is split into chunks
+HGT_NB_WAVE_ROWS = 64        # rows of a level whose totals one wavefront of the numbering kernel sums (the wavefront width)
+HGT_NB_BAD_SEED, HGT_NB_BAD_TIME = 1, 2
+HGT_NB_HEAD_N, HGT_NB_HEAD_DEG, HGT_NB_HEAD_CHUNKS, HGT_NB_HEAD_KEPT, HGT_NB_HEAD_FLAGS = 0, 1, 2, 3, 4
+HGT_NB_HEAD_TYPE_BEGIN, HGT_NB_HEAD_TYPE_END, HGT_NB_HEAD_WORDS = 8, 24, 40
 
 
 class HgtLayout(C.Structure):
@@ -111,6 +116,17 @@ class HgtViewTriple(C.Structure):
     _fields_ = [("indptr", C.c_void_p), ("src", C.c_void_p), ("time", C.c_void_p), ("tgt_flags", C.c_void_p), ("src_flags", C.c_void_p),
                 ("tgt_time", C.c_void_p), ("src_time", C.c_void_p), ("first", C.c_int64), ("n_rows", C.c_int32), ("tgt_off", C.c_int32),
                 ("src_off", C.c_int32), ("rel_id", C.c_int32)]
+
+
+class HgtNbType(C.Structure):
+    _fields_ = [("mark", C.c_void_p), ("feat", C.c_void_p), ("ld", C.c_int64), ("row_off", C.c_int64), ("n_nodes", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class HgtNbTriple(C.Structure):
+    _fields_ = [("indptr", C.c_void_p), ("src", C.c_void_p), ("time", C.c_void_p), ("tgt_flags", C.c_void_p), ("src_flags", C.c_void_p),
+                ("tgt_time", C.c_void_p), ("src_time", C.c_void_p), ("tgt_type", C.c_int32), ("src_type", C.c_int32),
+                ("rel_id", C.c_int32), ("reserved", C.c_int32)]
 
 
 GRAPH_MEAN_CHUNK = 256      # HGT_GRAPH_MEAN_CHUNK: the most terms of a row one wavefront of hgt_neighbour_mean adds
@@ -312,6 +328,16 @@ SIGNATURES = {
     # tmp_bytes, head_host_pinned, stream)
     "hgt_view_tmp_bytes": (C.c_int, [_i64, C.POINTER(_u64)]),
     "hgt_view_build": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    # exact neighbourhoods (csrc/hgt_neighbourhood.hip): every call starts with (types_dev, n_types); include/hgt_hip.h has the rest
+    "hgt_nb_constants": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "hgt_nb_sort_bytes": (C.c_int, [_i64, _i32, C.POINTER(_u64)]),
+    "hgt_nb_seeds": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "hgt_nb_number": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "hgt_nb_expand": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "hgt_nb_fill": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _i64, _vp, _vp]),
+    "hgt_nb_finish": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "hgt_nb_reset": (C.c_int, [_vp, _i32, _vp, _i64, _vp]),
 }
 
 _lib = None

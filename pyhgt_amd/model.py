@@ -214,7 +214,9 @@ class GNN(nn.Module):
             return torch.zeros(S, self.n_hid, dtype=torch.float32, device=node_feature.device)
         lib = _lib.load()
         if grad:
-            h = self._adapt_grad(node_feature[trim.order], trim.plan(1, conv0.use_RTE))
+            h = self._adapt_grad(node_feature if trim.gathered else node_feature[trim.order], trim.plan(1, conv0.use_RTE))
+        elif trim.gathered:                          # (a NeighbourhoodGraph: the rows are the trim's already, n_nodes = n_rows[0])
+            h = self._adapt(node_feature.detach().float().contiguous(), trim.plan(1, conv0.use_RTE))
         else:
             x = node_feature.detach().float()
             x = x if x.stride(1) == 1 else x.contiguous()

@@ -137,6 +137,9 @@ class DeviceHeteroGraph:
         self._batch_state = {}                               # the same three for batched calls (sample_subgraphs_device): [B, n] arrays
         self._batch_nodes = None                             # of their own, sized for the largest B seen, and a flag of their own
         self._batch_dirty = False
+        self._nb_mark = None                                 # neighbourhood(): one resident int32 mark per node, -1 between calls,
+        self._nb_dirty = False                               # and the flag that a call did not walk them back
+        self._nb_tables = {}                                 # the callers' node_time / leave_out tables in their resident device form
         return [keep[i] for i in order]
 
     def set_features(self, features):
@@ -246,6 +249,36 @@ class DeviceHeteroGraph:
         is the exact output at those nodes."""
         from .view import whole_graph
         return whole_graph(self, node_time, max_time, leave_out, self_loops, plan)
+
+    def neighbourhood(self, seeds, n_layers, node_time=None, max_time=None, leave_out=None, self_loops=True, max_rows=None,
+                      max_edges=None):
+        """The exact n_layers-hop neighbourhood of `seeds` = {type name: ids} (tensor, array or list, on the device or the host; any
+        order, repeats allowed; the dict's order is the order of the result rows) as a `NeighbourhoodGraph`: array for array the
+        whole-graph view of the same arguments trimmed to the seeds (pyhgt_amd/neighbourhood.py has the rule, `np_neighbourhood`),
+        with the rows' features already gathered.  `gnn(*nb.inputs, trim=nb)` is the exact output at the seeds -- equal to
+        `gnn(*view[:5], seeds=...)` -- at a cost that follows the neighbourhood: a frontier walk over the in-edge CSRs
+        (csrc/hgt_neighbourhood.hip), no launch and no allocation proportional to the graph after the first call, one host read per
+        level (at most n_layers + 1).  Under grad the same call is full-neighbour mini-batch training.  max_rows / max_edges: a
+        protective cap on the rows / edges reached so far, checked after every level (OverflowError names the level and the size).
+        KeyError: an unknown seed type or leave_out triple.  IndexError: a seed id outside its type, a kept edge whose time
+        difference is outside [0, 240).  ValueError: n_layers outside [1, HGT_TRIM_MAX_LAYERS], the view's node_time rules, feature
+        widths that differ.  After any of these the next call is correct.  Calls on one graph share its resident marks: they are
+        NOT reentrant (one call at a time, on one stream).  On a host-only graph: the definition's arrays as CPU tensors.
+
+        node_time / leave_out tables are per-node arrays, so THEIR cost is of the graph's size -- once: the first call that is handed a
+        table object validates it (host arrays on the host; an int64 device tensor with one host read, counted in `host_reads`),
+        converts it to int32 / uint8 and keeps that device form with the graph under the object's identity (the object is held);
+        every later call with the SAME object touches nothing of N.  An int32 (uint8) device tensor is taken as it is.  A table
+        changed in place keeps its identity: call `forget_neighbourhood_tables()` (or pass a new object).  The caps are checked when a
+        level's exact size is known; the buffers of a level are sized before that by the CSR entries of its rows -- an upper bound that
+        `max_time` / `leave_out` can undercut by any factor -- so on a filtered call the caps bound the result, not the scratch of the
+        level that trips them (unfiltered, the bound is exact and `max_edges` is checked before anything is allocated)."""
+        from .neighbourhood import neighbourhood
+        return neighbourhood(self, seeds, n_layers, node_time, max_time, leave_out, self_loops, max_rows, max_edges)
+
+    def forget_neighbourhood_tables(self):
+        """drop the resident forms of the node_time / leave_out tables `neighbourhood` keeps (after a table was changed in place)"""
+        self._nb_tables.clear()
 
     def get_types(self):
         return list(self.types)

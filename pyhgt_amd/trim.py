@@ -116,6 +116,7 @@ class TrimmedGraph:
     int64[n_edges[1]]; `.out_rows` int64[len(seeds)] = new_id[seeds]; the renumbered graph in the new order `.node_type`
     int64[n_rows[0]], `.edge_index` int64[2, n_edges[1]], `.edge_type`, `.edge_time` (None without times).  Host tuples `.n_rows`,
     `.n_edges` (indexed by the layer, 0..L), `.n_layers`, `.n_nodes`, `.n_seeds`.  `.plan(l, use_rte)` is the GraphPlan of layer l."""
+    gathered = False       # True (NeighbourhoodGraph): the caller's node_feature already stands in the trim's row order
 
     def __init__(self):
         self._plans = {}
