@@ -1492,6 +1492,41 @@ int hgt_nb_finish(const hgt_nb_type* types_dev, int32_t n_types, const int64_t* 
                   void* stream);
 int hgt_nb_reset(const hgt_nb_type* types_dev, int32_t n_types, const uint64_t* keys, int64_t n, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Matcher retrieval (csrc/hgt_matcher_topk.hip): the k best candidates of every query and the exact rank of one candidate per query
+ * over ALL candidates, without the [n_cand, n_query] score matrix that Matcher.forward(infer=True) returns (pyHGT/model.py:16-49:
+ * "we will consider millions or even billions of nodes as candidates").  Added under ABI 8 (new symbols only).
+ *
+ *   score   s(c, q) = (row c of tx . row q of ty, a k-ordered fp32 fma chain on v_mfma_f32_32x32x2_f32) * scale, the scale applied
+ *           once to the finished sum (hgt_row_dot's convention).  The bits of s(c, q) are a function of the two rows, d and scale
+ *           alone: the same in both calls, for every n_cand, n_query, chunk_rows and position of the rows.
+ *   order   scores compare as floats, -0 == +0, every NaN is one value above +inf; among equal scores the lower candidate position
+ *           comes first (hgt_rank_metrics's tie rule).
+ *
+ *   hgt_matcher_topk_bytes  *bytes_host = the device scratch either call needs (the rank call asks with k = 1).  Host arithmetic only.
+ *   hgt_matcher_topk        values_out float32 [n_query, k], indices_out int64 [n_query, k]: the first min(k, n_cand) candidates of
+ *                           every query in that order; slots beyond n_cand hold -inf and -1.  A returned -0 reads +0 and a NaN reads
+ *                           the positive quiet NaN (values are decoded from the selection key).  chunk_rows == 0: the library cuts the
+ *                           candidates into chunks itself; > 0: chunks of at most that many rows, rounded up to 128 (the rows a
+ *                           workgroup takes per step).  The output is the same bits for every chunk_rows.
+ *   hgt_matcher_rank        rank_out[q] (int64) = #{ c : c comes before index[q] in the order of query q }, 0-based; index[q] (int64,
+ *                           device) outside [0, n_cand): -1.  rank < k  <=>  index[q] is among hgt_matcher_topk's first k of query q.
+ *
+ *   tx [n_cand, d] and ty [n_query, d] float32 device arrays with leading dimensions ld_x, ld_y >= d (rows 16-byte aligned take
+ *   16-byte loads).  Supported: d % 4 == 0, 4 <= d <= 1024, 1 <= k <= HGT_TOPK_MAX_K, n_cand < 2^31 - 1.  Caller-owned scratch, no
+ *   allocation, no synchronisation, no float atomics; n_query == 0: HGT_OK without a launch; n_cand == 0 writes the padding (-1 ranks).
+ *   Refusals, all before a launch: a NULL array that would be read or written, NULL bytes_host, a negative size, ld < d, k < 1, a NaN or
+ *   infinite scale: HGT_ERR_INVALID_ARG; k > HGT_TOPK_MAX_K, d % 4 != 0, d < 4, d > 1024, n_query >= 2^31 - 1: HGT_ERR_UNSUPPORTED;
+ *   n_cand >= 2^31 - 1 (or a chunk_rows so small that the chunks' lists pass 2^62 bytes or 2^31 - 1 workgroups): HGT_ERR_TOO_LARGE;
+ *   ws NULL or ws_bytes below hgt_matcher_topk_bytes: HGT_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGT_TOPK_MAX_K 128
+int hgt_matcher_topk_bytes(int64_t n_cand, int64_t n_query, int32_t k, int64_t chunk_rows, uint64_t* bytes_host);
+int hgt_matcher_topk(const float* tx, int64_t ld_x, int64_t n_cand, const float* ty, int64_t ld_y, int64_t n_query, int32_t d, float scale,
+                     int32_t k, int64_t chunk_rows, float* values_out, int64_t* indices_out, void* ws, uint64_t ws_bytes, void* stream);
+int hgt_matcher_rank(const float* tx, int64_t ld_x, int64_t n_cand, const float* ty, int64_t ld_y, int64_t n_query, int32_t d, float scale,
+                     int64_t chunk_rows, const int64_t* index, int64_t* rank_out, void* ws, uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

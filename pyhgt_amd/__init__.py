@@ -12,6 +12,7 @@ from .sampler import LabelSpace, seed_edge_mask, np_label_distribution, np_label
 from .sampler import candidate_pairs  # noqa: F401
 from .metrics import Segments, rank_metrics, pair_rank_loss, class_loss, np_rank_metrics, np_pair_rank_loss, np_class_loss  # noqa: F401
 from .metrics import class_predict, VoteTable, np_class_predict, np_vote_add  # noqa: F401
+from .metrics import np_matcher_scores, np_matcher_topk, np_matcher_rank, matcher_scale, matcher_topk, matcher_rank  # noqa: F401
 from .optim import AdamW, np_adamw_step  # noqa: F401
 from .graph_build import np_edge_lists_to_csr, neighbour_mean, np_neighbour_mean  # noqa: F401
 from .trim import np_trim_to_seeds, np_trim_graph, trim_to_seeds, TrimmedGraph  # noqa: F401

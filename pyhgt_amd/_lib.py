@@ -135,6 +135,7 @@ HGT_GRAPH_TIME_BY_NBR = 1
 RANK_LIST_CAP = 1024    # HGT_RANK_LIST_CAP: positives a pass of hgt_rank_metrics holds
 CLASS_LOSS_WAVE_COLS = 256   # HGT_CLASS_LOSS_WAVE_COLS: the longest row of hgt_class_loss that takes a wavefront
 OPTIM_CHUNK = 4096          # HGT_OPTIM_CHUNK: the most elements of one tensor a workgroup of the optimizer kernels takes
+TOPK_MAX_K = 128           # HGT_TOPK_MAX_K: the most candidates per query hgt_matcher_topk returns
 PREDICT_MAX_SPLITS = 8     # HGT_PREDICT_MAX_SPLITS: the most splits hgt_class_predict counts in one call
 ABI_VERSION = 8          # HGT_ABI_VERSION of include/hgt_hip.h this binding was written against
 
@@ -338,6 +339,11 @@ SIGNATURES = {
                               _vp, _vp, _i64, _vp, _vp]),
     "hgt_nb_finish": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "hgt_nb_reset": (C.c_int, [_vp, _i32, _vp, _i64, _vp]),
+    # matcher retrieval (csrc/hgt_matcher_topk.hip): (n_cand, n_query, k, chunk_rows, bytes); (tx, ld_x, n_cand, ty, ld_y, n_query, d, scale,
+    # k, chunk_rows, values_out, indices_out, ws, ws_bytes, stream); (tx .. scale, chunk_rows, index, rank_out, ws, ws_bytes, stream)
+    "hgt_matcher_topk_bytes": (C.c_int, [_i64, _i64, _i32, _i64, C.POINTER(_u64)]),
+    "hgt_matcher_topk": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, C.c_float, _i32, _i64, _vp, _vp, _vp, _u64, _vp]),
+    "hgt_matcher_rank": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, C.c_float, _i64, _vp, _vp, _vp, _u64, _vp]),
 }
 
 _lib = None

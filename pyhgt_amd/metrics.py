@@ -54,6 +54,20 @@ of the test papers it contains through `res.tolist()` and a dict, and the answer
 
 The prediction is taken on the scores as given.  The scripts take argmax of log-probabilities; on raw logits that is the same
 position except where the float32 rounding of (x - m) - ls makes the log-probabilities of two different logits equal.
+
+Matcher retrieval (`matcher_topk`, `matcher_rank`, csrc/hgt_matcher_topk.hip; the rules are `np_matcher_scores`, `np_matcher_topk` and
+`np_matcher_rank`).  With projected candidates tx [N, d] and projected queries ty [Q, d], both float32:
+
+    s(c, q) = fl32(tx_c . ty_q accumulated in fp32) * scale, scale = the float32 nearest to 1 / sqrt(n_hid), applied once to the sum
+    order of query q: scores compare as floats, -0 == +0, every NaN is one value above +inf (torch.topk's reading: a broken model
+    shows); among equal scores the lower candidate position comes first
+    topk: the first min(k, N) candidates of every query in that order -- values float32 [Q, k], indices int64 [Q, k], slots beyond N
+    hold -inf and -1; a -0 is returned as +0 and a NaN as the quiet NaN
+    rank[q] = #{ c : c comes before index[q] in the order of query q }, int64, 0-based; an index outside [0, N) gives -1
+
+The numpy rules accumulate in float64 and round once; the kernels accumulate in fp32.  Where every product and partial sum is exact
+(small integers) the two agree bit for bit; elsewhere a score differs from the rule's by at most gamma_d * sum_i |tx_ci ty_qi| * scale
+with gamma_d = d 2^-24 / (1 - d 2^-24).  MRR and Hits@k follow from the ranks: mean of 1 / (1 + rank) and mean of rank < k.
 """
 import numpy as np
 import torch
@@ -61,10 +75,68 @@ import torch
 from . import _lib
 
 __all__ = ["Segments", "rank_metrics", "pair_rank_loss", "class_loss", "np_rank_metrics", "np_pair_rank_loss", "np_class_loss", "np_ranks",
-           "class_predict", "VoteTable", "np_class_predict", "np_vote_add"]
+           "class_predict", "VoteTable", "np_class_predict", "np_vote_add", "np_matcher_scores", "np_matcher_topk", "np_matcher_rank",
+           "matcher_scale", "matcher_topk", "matcher_rank"]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rule
+def matcher_scale(n_hid):
+    """the float32 nearest to 1 / sqrt(n_hid): the scale of the Matcher's scores"""
+    return np.float32(1.0 / np.sqrt(np.float64(n_hid)))
+
+
+def np_matcher_scores(tx, ty, scale):
+    """s [N, Q] float32: fl32(tx @ ty^T, accumulated in float64) * scale in float32"""
+    tx, ty = np.asarray(tx, dtype=np.float32), np.asarray(ty, dtype=np.float32)
+    if tx.ndim != 2 or ty.ndim != 2 or tx.shape[1] != ty.shape[1]:
+        raise ValueError("pyhgt_amd: tx is [N, d] and ty is [Q, d]")
+    with np.errstate(invalid="ignore", over="ignore"):
+        dot = (tx.astype(np.float64) @ ty.astype(np.float64).T).astype(np.float32)
+        return (dot * np.float32(scale)).astype(np.float32)
+
+
+def _np_order_image(s):
+    """int64 image of float32 scores that sorts like the order of the module docstring: -0 == +0, every NaN one value above +inf"""
+    s = np.where(np.isnan(s), np.float32(np.nan), s.astype(np.float32) + np.float32(0.0))      # one NaN; -0 + 0 = +0
+    u = np.ascontiguousarray(s, dtype=np.float32).view(np.uint32).astype(np.int64)
+    u = np.where(np.isnan(s), 0x7FC00000, u)
+    return np.where(u & 0x80000000, 0xFFFFFFFF - u, u | 0x80000000)
+
+
+def np_matcher_topk(tx, ty, k, scale):
+    """(values float32 [Q, k], indices int64 [Q, k]): the rule of the module docstring"""
+    if int(k) != k or k < 1:
+        raise ValueError("pyhgt_amd: k is an integer >= 1")
+    k = int(k)
+    s = np_matcher_scores(tx, ty, scale)
+    N, Q = s.shape
+    values = np.full((Q, k), -np.inf, np.float32)
+    indices = np.full((Q, k), -1, np.int64)
+    m = min(k, N)
+    for q in range(Q):
+        order = np.argsort(-_np_order_image(s[:, q]), kind="stable")[:m]
+        col = s[order, q]
+        values[q, :m] = np.where(np.isnan(col), np.float32(np.nan), col + np.float32(0.0))
+        indices[q, :m] = order
+    return values, indices
+
+
+def np_matcher_rank(tx, ty, index, scale):
+    """rank int64 [Q]: how many candidates come before index[q] in the order of query q; -1 for an index outside [0, N)"""
+    s = np_matcher_scores(tx, ty, scale)
+    N, Q = s.shape
+    index = np.asarray(index, dtype=np.int64).reshape(-1)
+    if index.size != Q:
+        raise ValueError("pyhgt_amd: one index per query")
+    rank = np.full(Q, -1, np.int64)
+    for q in range(Q):
+        t = int(index[q])
+        if 0 <= t < N:
+            img = _np_order_image(s[:, q])
+            rank[q] = int(np.sum(img > img[t])) + int(np.sum(img[:t] == img[t]))
+    return rank
+
+
 def np_ranks(values):
     """0-based descending ranks of a 1-d array, a tie to the lower position (-0.0 == 0.0, as everywhere in IEEE comparisons)"""
     values = np.asarray(values)
@@ -681,3 +753,62 @@ class VoteTable:
         """the share of the voted (and labelled) slots whose prediction equals its label: a Python float after one host read"""
         n_voted, n_correct = self.predict(labels)[1].tolist()
         return n_correct / n_voted if n_voted else float("nan")
+
+
+# ---------------------------------------------------------------------------------------------------------------- matcher retrieval
+def _matcher_args(tx, ty, what):
+    for t, name in ((tx, "tx"), (ty, "ty")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2:
+            raise TypeError("pyhgt_amd: %s: %s must be a float32 [rows, d] tensor" % (what, name))
+    if not tx.is_cuda or not ty.is_cuda:
+        raise RuntimeError("pyhgt_amd: %s runs only on ROCm GPU tensors; np_%s is the definition on the host" % (what, what))
+    if tx.device != ty.device:
+        raise ValueError("pyhgt_amd: %s: tx is on %s, ty on %s" % (what, tx.device, ty.device))
+    if tx.size(1) != ty.size(1):
+        raise ValueError("pyhgt_amd: %s: tx has %d columns, ty has %d" % (what, tx.size(1), ty.size(1)))
+    tx, ty = _rows_f32(tx.detach(), "tx"), _rows_f32(ty.detach(), "ty")
+    ld = lambda t: max(int(t.stride(0)), int(t.size(1))) if t.size(0) > 1 else int(t.size(1))
+    return tx, ty, ld(tx), ld(ty)
+
+
+def _matcher_scratch(lib, n, q, k, chunk_rows, device):
+    nb = _lib.C.c_uint64()
+    _lib.check(lib.hgt_matcher_topk_bytes(n, q, k, chunk_rows, _lib.C.byref(nb)), "hgt_matcher_topk_bytes")
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+
+
+def matcher_topk(tx, ty, k, scale, chunk_rows=0):
+    """(values float32 [Q, k], indices int64 [Q, k]) of the scores (tx @ ty^T) * scale without the [N, Q] matrix: the rule is
+    np_matcher_topk (module docstring).  tx [N, d], ty [Q, d]: float32 device tensors with unit column stride (row slices and column
+    slices of wider tensors are read in place); d % 4 == 0, d <= 1024, 1 <= k <= _lib.TOPK_MAX_K.  chunk_rows > 0 fixes the length of
+    the candidate chunks (the result does not depend on it).  Two launches on the current stream, no synchronisation."""
+    tx, ty, ldx, ldy = _matcher_args(tx, ty, "matcher_topk")
+    if int(k) != k or k < 1 or k > 2 ** 31 - 1:
+        raise ValueError("pyhgt_amd: k is an integer >= 1")
+    lib = _lib.load()
+    n, q, d, k = tx.size(0), ty.size(0), tx.size(1), int(k)
+    with torch.cuda.device(tx.device):
+        ws = _matcher_scratch(lib, n, q, k, int(chunk_rows), tx.device)       # (refuses k > _lib.TOPK_MAX_K before anything is allocated)
+        values = torch.empty(q, k, dtype=torch.float32, device=tx.device)
+        indices = torch.empty(q, k, dtype=torch.int64, device=tx.device)
+        _lib.check(lib.hgt_matcher_topk(_ptr(tx), ldx, n, _ptr(ty), ldy, q, d, float(scale), k, int(chunk_rows), _ptr(values), _ptr(indices),
+                                        ws.data_ptr(), ws.numel(), _stream(tx)), "hgt_matcher_topk")
+    return values, indices
+
+
+def matcher_rank(tx, ty, index, scale, chunk_rows=0):
+    """rank int64 [Q] of candidate index[q] among all N candidates of query q (0 = best; an index outside [0, N) gives -1): the rule is
+    np_matcher_rank.  Same tensors and limits as matcher_topk, and the same score bits: matcher_rank(index=indices[:, j]) == j.
+    MRR = mean of 1 / (1 + rank), Hits@k = mean of rank < k over the queries with a rank >= 0."""
+    tx, ty, ldx, ldy = _matcher_args(tx, ty, "matcher_rank")
+    lib = _lib.load()
+    n, q, d = tx.size(0), ty.size(0), tx.size(1)
+    index = torch.as_tensor(index, device=tx.device).reshape(-1).to(torch.int64).contiguous()
+    if index.numel() != q:
+        raise ValueError("pyhgt_amd: one index per query")
+    with torch.cuda.device(tx.device):
+        ws = _matcher_scratch(lib, n, q, 1, int(chunk_rows), tx.device)
+        rank = torch.empty(q, dtype=torch.int64, device=tx.device)
+        _lib.check(lib.hgt_matcher_rank(_ptr(tx), ldx, n, _ptr(ty), ldy, q, d, float(scale), int(chunk_rows), _ptr(index), _ptr(rank),
+                                        ws.data_ptr(), ws.numel(), _stream(tx)), "hgt_matcher_rank")
+    return rank

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from . import _lib
 from .conv import GeneralConv, GraphPlan, _ptr, _stream
-from .metrics import _one_label_form, class_loss, class_predict
+from .metrics import _one_label_form, class_loss, class_predict, matcher_rank, matcher_scale, matcher_topk
 
 __all__ = ["GNN", "Classifier", "Matcher"]
 
@@ -344,6 +344,39 @@ class Matcher(nn.Module):
             return out
         # tx @ ty^T / sqrt(n_hid): the typed-linear kernel with ty as the "weight" and no bias
         return _dense_linear(tx, ty / self.sqrt_hd, None, deterministic=_det(self))
+
+    def _projected(self, x, y, infer, what):
+        """(tx, ty) of forward(): candidates x through left_linear -- under infer=True from / into self.cache --, queries y through
+        right_linear; without autograd"""
+        if not y.is_cuda or not ((infer and self.cache is not None) or x.is_cuda):
+            raise RuntimeError("pyhgt_amd: Matcher.%s runs only on ROCm GPU tensors; metrics.np_matcher_%s is the definition on the host"
+                               % (what, "topk" if what == "topk" else "rank"))
+        with torch.no_grad():
+            ty = _dense_linear(y, self.right_linear.weight, self.right_linear.bias, deterministic=_det(self))
+            if infer and self.cache is not None:
+                tx = self.cache
+            else:
+                tx = _dense_linear(x, self.left_linear.weight, self.left_linear.bias, deterministic=_det(self))
+                if infer:
+                    self.cache = tx
+        return tx.detach(), ty
+
+    def topk(self, x, y, k, infer=False):
+        """(values float32 [Q, k], indices int64 [Q, k]): for every query row of y the k candidates (rows of x) the model scores highest,
+        best first, over ALL candidates and without the [N, Q] matrix of forward(x, y, infer=True) -- one streaming pass over the
+        projected candidates (metrics.matcher_topk; the rule is metrics.np_matcher_topk: ties go to the lower row, a NaN stands above
+        +inf, slots beyond N hold -inf / -1).  The score is (left_linear(x) . right_linear(y)) * fl32(1 / sqrt(n_hid)).  infer=True uses
+        and fills self.cache exactly as forward does.  Not differentiable; 1 <= k <= 128 (_lib.TOPK_MAX_K), n_hid % 4 == 0, <= 1024."""
+        tx, ty = self._projected(x, y, infer, "topk")
+        return matcher_topk(tx, ty, k, matcher_scale(self.n_hid))
+
+    def rank_of(self, x, y, index, infer=False):
+        """rank int64 [Q]: how many of ALL candidates (rows of x) the model places before candidate index[q] for query row q of y --
+        0 = the model's first answer, -1 for an index outside [0, N) (metrics.matcher_rank; the rule is metrics.np_matcher_rank).  The
+        scores are topk's bit for bit, so rank_of(x, y, indices[:, j]) == j.  The metrics of a link-prediction evaluation follow from the
+        ranks: MRR = mean of 1 / (1 + rank), Hits@k = mean of rank < k.  infer=True as in forward.  Not differentiable."""
+        tx, ty = self._projected(x, y, infer, "rank_of")
+        return matcher_rank(tx, ty, index, matcher_scale(self.n_hid))
 
     def __repr__(self):
         return '{}(n_hid={})'.format(self.__class__.__name__, self.n_hid)
