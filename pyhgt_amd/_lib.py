@@ -6,6 +6,9 @@ returns an error code, a RuntimeError is raised.
 """
 import ctypes as C
 import os
+import threading
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HGT_LIB_PATH", os.path.join(_HERE, "lib", "libhgt_hip.so"))   # override: development A/B builds
@@ -378,3 +381,27 @@ def layout_for(d_out, n_heads):
     lay = HgtLayout()
     check(load().hgt_layout_for(d_out, n_heads, C.byref(lay)), "hgt_layout_for(d=%d, heads=%d)" % (d_out, n_heads))
     return lay
+
+
+def ptr(t):
+    """the address of a tensor for a C call; None (NULL) for None or an empty tensor"""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def table_to_device(table, dev):
+    """a ctypes array of structures -> its bytes as a uint8 tensor on `dev`"""
+    return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+
+
+_pinned = threading.local()
+
+
+def pinned(name, words, dtype):
+    """The pinned host buffer `name` of this thread for a call's read-back, allocated on first use and kept: allocating pinned memory
+    costs more than the calls it serves.  A buffer is busy from its copy to its read; the same call makes both, so a buffer per thread
+    is never handed out while busy."""
+    buf = getattr(_pinned, name, None)
+    if buf is None:
+        buf = torch.zeros(words, dtype=dtype).pin_memory()
+        setattr(_pinned, name, buf)
+    return buf

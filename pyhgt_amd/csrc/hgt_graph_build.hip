@@ -16,11 +16,10 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "hgt_common.h"
+#include "hgt_graph_rule.h"
 
 namespace {
 
-constexpr int32_t TIME_NONE = INT32_MIN;      // HGT_SAMPLER_TIME_NONE of the Python side
 constexpr int BS = 256;
 
 static inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
@@ -113,7 +112,7 @@ __global__ void k_mark(const uint64_t* __restrict__ keys, const int32_t* __restr
     const int32_t e = vals[p];
     keep[e] = head ? 1 : 0;
     if (!tail) return;
-    int32_t tm = TIME_NONE;
+    int32_t tm = HGT_TIME_NONE;
     if (edge_time) tm = edge_time[e];
     else if (node_time) tm = node_time[by_nbr ? (uint32_t)(key & ((1ull << nb) - 1)) : (uint32_t)(key >> nb)];
     int64_t h = p;

@@ -18,7 +18,7 @@
 //                 the ids behind the last entry get the total from workgroup 0.
 // Integers only; the only atomic is the OR into the flag word.  Nothing synchronises: where the caller gives a pinned buffer (a filtered
 // build's one host read), rel_ptr and the flag travel there with one hipMemcpyAsync on the caller's stream.
-#include "hgt_common.h"
+#include "hgt_graph_rule.h"
 
 namespace {
 
@@ -28,8 +28,6 @@ constexpr int STEPS = TILE / 64;
 constexpr int WALK_BATCHES = 4;                        // row starts looked at 64 at a time before the walk gives up
 constexpr int SCAN_BS = 1024;
 constexpr int64_t LIMIT = (1ll << 31) - 1;
-constexpr int32_t TIME_NONE = HGT_SAMPLER_TIME_NONE;
-constexpr int32_t RTE_SELF = 120;                      // data.py:250 for an edge between nodes of one time
 
 struct ViewArgs {
     const hgt_view_triple* tab;                        // [M + 1] in device memory: the triples, then the self run
@@ -100,7 +98,7 @@ __device__ __forceinline__ int32_t view_tile(const ViewArgs& a, int64_t w0, int3
         const int64_t e = e0 + lane;
         const int64_t seg_end = e0 + 64 < a.E ? e0 + 64 : a.E;
         bool keep = false;
-        int32_t s = 0, d = 0, t = RTE_SELF, rel = 0, rel_lo = 0, rel_hi = -1;
+        int32_t s = 0, d = 0, t = HGT_RTE_SELF, rel = 0, rel_lo = 0, rel_hi = -1;
         int64_t cur = e0;
         while (cur < seg_end) {                                        // the triples this step touches (uniform over the wavefront)
             const hgt_view_triple tr = a.tab[m];
@@ -120,24 +118,12 @@ __device__ __forceinline__ int32_t view_tile(const ViewArgs& a, int64_t w0, int3
                 cursor = __shfl(row, (int)(hi - 1 - e0));
                 if (member) {
                     const int32_t sl = tr.src[p];
-                    bool k = true;
-                    if (FILTER) {
-                        if (a.has_max_time) {
-                            int32_t st = tr.time ? tr.time[p] : TIME_NONE;
-                            if (st == TIME_NONE) {                      // data.py:125: the neighbour inherits the target's time
-                                if (tr.tgt_time) k = tr.tgt_time[row] <= a.max_time;
-                            } else {
-                                k = st <= a.max_time;
-                            }
-                        }
-                        if (tr.tgt_flags && tr.tgt_flags[row]) k = false;
-                        if (tr.src_flags && tr.src_flags[sl]) k = false;
-                    }
+                    const bool k = !FILTER || entry_kept(tr, row, p, sl, a.has_max_time, a.max_time);
                     keep = k;
                     if (!COUNT) {
                         s = tr.src_off + sl; d = tr.tgt_off + row; rel = tr.rel_id;
                         if (tr.tgt_time) {
-                            const int64_t dt = (int64_t)tr.tgt_time[row] - (int64_t)tr.src_time[sl] + RTE_SELF;
+                            const int64_t dt = entry_time_diff(tr, row, sl);
                             if (k && (dt < 0 || dt >= HGT_RTE_LEN)) bad = true;
                             // written as it is (saturated to int32 only): the plan build and every layer that reads edge_time
                             // flag a value outside [0, 240) themselves, as they do for any caller's tensors
@@ -147,7 +133,7 @@ __device__ __forceinline__ int32_t view_tile(const ViewArgs& a, int64_t w0, int3
                 }
             } else if (member) {                                       // the self run: never filtered
                 keep = true;
-                s = d = (int32_t)(e - tr.first); rel = tr.rel_id; t = RTE_SELF;
+                s = d = (int32_t)(e - tr.first); rel = tr.rel_id; t = HGT_RTE_SELF;
             }
             cur = hi;
             if (hi == end) { prev_rel = tr.rel_id; ++m; cursor = -1; }

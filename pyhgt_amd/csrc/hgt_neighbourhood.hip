@@ -16,13 +16,13 @@
 //              pass (kept entries per chunk, and the claims) -> one single-workgroup scan -> fill pass (after level h + 1 has its
 //              numbers: it reads the sources' new rows from the marks), a kept entry's position = the scan's value for its chunk + the
 //              kept entries of the wavefront's earlier steps + its rank in a ballot.  The self loops of the bucket follow.
-//   predicate  the whole-graph view's (hgt_graph_view.hip, restated): stored time <= max_time, a TIME_NONE entry takes the target's
-//              time, leave-out flags of either end; time difference = tgt_time - src_time + 120, flagged outside [0, 240).
+//   predicate  the whole-graph view's, from the one statement both call (hgt_graph_rule.h: entry_kept, entry_time_diff); a time
+//              difference outside [0, 240) is written as it is and sets HGT_NB_BAD_TIME.
 // Integers only, vector stores only; the atomics are the claim, the level totals and the OR into the flag word -- none of them
 // decides a position.  Nothing here synchronises: the caller reads the head once per level.
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "hgt_common.h"
+#include "hgt_graph_rule.h"
 
 namespace {
 
@@ -32,8 +32,6 @@ constexpr int WAVE_ROWS = HGT_NB_WAVE_ROWS;          // rows whose entry and chu
 static_assert(WAVE_ROWS == 64 && BS % WAVE_ROWS == 0, "a wavefront of gfx950");
 constexpr int SCAN_BS = 1024;
 constexpr int64_t LIMIT = (1ll << 31) - 1;
-constexpr int32_t TIME_NONE = HGT_SAMPLER_TIME_NONE;
-constexpr int32_t RTE_SELF = 120;
 constexpr int32_t CLAIMED = HGT_NB_CLAIMED;
 constexpr uint64_t PAD_KEY = ~0ull;
 constexpr int MAX_T = HGT_SAMPLER_MAX_TYPES, MAX_M = HGT_SAMPLER_MAX_TRIPLES;
@@ -212,17 +210,7 @@ __global__ __launch_bounds__(BS) void k_nb_walk(WalkArgs a, ItemTab it) {
         int32_t sl = 0;
         if (p < p1) {
             sl = tr.src[p];
-            k = true;
-            if (a.has_max_time) {
-                const int32_t st = tr.time ? tr.time[p] : TIME_NONE;
-                if (st == TIME_NONE) {                                  // data.py:125: the neighbour inherits the target's time
-                    if (tr.tgt_time) k = tr.tgt_time[row] <= a.max_time;
-                } else {
-                    k = st <= a.max_time;
-                }
-            }
-            if (tr.tgt_flags && tr.tgt_flags[row]) k = false;
-            if (tr.src_flags && tr.src_flags[sl]) k = false;
+            k = entry_kept(tr, row, p, sl, a.has_max_time, a.max_time);
         }
         const unsigned long long mask = __ballot(k);
         if (!FILL) {
@@ -239,7 +227,7 @@ __global__ __launch_bounds__(BS) void k_nb_walk(WalkArgs a, ItemTab it) {
                 a.dst[pos] = a.row_base + lrow;
                 a.etype[pos] = tr.rel_id;
                 if (a.etime) {
-                    const int64_t dt = (int64_t)tr.tgt_time[row] - (int64_t)tr.src_time[sl] + RTE_SELF;
+                    const int64_t dt = entry_time_diff(tr, row, sl);
                     if (dt < 0 || dt >= HGT_RTE_LEN) bad = true;
                     a.etime[pos] = dt;
                 }
@@ -265,7 +253,7 @@ __global__ __launch_bounds__(BS) void k_nb_self(const int64_t* __restrict__ head
     src[pos] = row_base + i;
     dst[pos] = row_base + i;
     etype[pos] = rel_self;
-    if (etime) etime[pos] = RTE_SELF;
+    if (etime) etime[pos] = HGT_RTE_SELF;
 }
 
 // one wavefront per result row: its feature row from its type's matrix

@@ -41,7 +41,7 @@
 //                           argument space.  The row logic below exists once; the single entry points keep their own instantiations.
 //   hgt_sampler_gather_features   the feature rows of a batched call in one launch, one wavefront per output row
 // No float atomics in this file; compiled without fast-math like the rest of the library.
-#include "hgt_common.h"
+#include "hgt_graph_rule.h"
 #include "hgt_philox.h"
 
 namespace {
@@ -501,7 +501,7 @@ __device__ __forceinline__ void induce_row(const View<BATCHED>& V, const hgt_sam
             if (ser >= 0 && e >= 0 && e < io.n_edges) {
                 io.src_out[e] = s_off + ser;
                 io.dst_out[e] = tgt;
-                io.time_out[e] = v_time - stamp_time(S.stamp[s]) + 120;           // data.py:250
+                io.time_out[e] = v_time - stamp_time(S.stamp[s]) + HGT_RTE_SELF;  // data.py:250
             }
         }
         run += total;
@@ -705,7 +705,7 @@ __device__ __forceinline__ void induce_nodes(const View<BATCHED>& V, const int32
     if (e >= 0 && e < n_edges) {
         src_out[e] = g;
         dst_out[e] = g;
-        time_out[e] = 120;
+        time_out[e] = HGT_RTE_SELF;
     }
 }
 

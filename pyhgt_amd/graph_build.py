@@ -213,7 +213,7 @@ def build_from_edge_lists(cls, types, n_nodes, edges, edge_time=None, node_time=
                 by = _lib.HGT_GRAPH_TIME_BY_NBR if tsrc is not None and tsrc[0] == "nbr" else _lib.HGT_GRAPH_TIME_BY_ROW
                 n_rows, n_nbrs = int(n_nodes[tt]), int(n_nodes[st])
                 indptr, nbr_out, time_out = i32(n_rows + 1), i32(E), i32(E)
-                ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+                ptr = _lib.ptr
                 _lib.check(lib.hgt_graph_csr_build(ptr(rows), rows.stride(0), ptr(nbrs), nbrs.stride(0), rows.element_size(), ptr(et), ptr(nt),
                                                    by, E, n_rows, n_nbrs, indptr.data_ptr(), ptr(nbr_out), ptr(time_out),
                                                    status[2 * j:].data_ptr(), ws.data_ptr(), ws.numel(), stream.cuda_stream),

@@ -419,8 +419,7 @@ def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
+_ptr = _lib.ptr
 
 
 def _rows_f32(t, what):

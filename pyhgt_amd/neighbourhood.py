@@ -37,16 +37,16 @@ Host reads: ONE per level that has rows, through pinned memory -- at most n_laye
 node_time table on the call that first sees it (its int32 range check); `host_reads` counts them all.
 """
 import ctypes as C
-import threading
 from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .sampler import TIME_NONE, _host_array
+from .sampler import _host_array
 from .trim import TrimmedGraph, _check_layers
-from .view import _RTE_SELF, _is_device, _leave_out_table, _node_time_tables, _host_flags, _type_off
+from .view import (_RTE_SELF, _feature_width, _flags_u8, _is_device, _leave_out_table, _node_time_tables, _np_kept, _np_time_diff,
+                   _type_off)
 
 __all__ = ["np_neighbourhood", "neighbourhood", "NeighbourhoodGraph", "NeighbourhoodArrays", "NB_CHUNK", "NB_WAVE_ROWS"]
 
@@ -85,21 +85,6 @@ def _seed_lists(dgraph, seeds):
             raise IndexError("pyhgt_amd: seed ids of %r outside [0, %d)" % (name, dgraph.n_nodes[t]))
         out.append((t, a))
     return out
-
-
-def _feature_width(n_nodes, feats, types):
-    """the common width of the feature matrices of the types that have nodes (ValueError: a type without one, differing widths); 0
-    for a graph whose types are all empty"""
-    widths = set()
-    for t, n, f in zip(types, n_nodes, feats):
-        if n == 0:
-            continue
-        if f is None:
-            raise ValueError("pyhgt_amd: no feature matrix for node type %r" % t)
-        widths.add(int(np.shape(f)[1]))
-    if len(widths) > 1:
-        raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (sorted(widths),))
-    return widths.pop() if widths else 0
 
 
 def _check_caps(level, rows, edges, max_rows, max_edges):
@@ -170,27 +155,11 @@ def np_neighbourhood(dgraph, seeds, n_layers, node_time=None, max_time=None, lea
             rows = np.repeat(ids, deg)
             pos = np.repeat(indptr[ids].astype(np.int64) - np.concatenate([[0], np.cumsum(deg)[:-1]]), deg) + np.arange(int(deg.sum()))
             s = src[pos].astype(np.int64)
-            keep = np.ones(s.size, bool)
-            if max_time is not None:
-                t_ = time[pos].astype(np.int64)
-                none = t_ == TIME_NONE
-                if times is not None:
-                    t_ = np.where(none, times[tt][rows], t_)
-                    none = np.zeros_like(none)
-                keep &= none | (t_ <= int(max_time))
-            if table is not None:
-                tf, sf = (_host_flags(f) for f in table[m])
-                if tf is not None:
-                    keep &= ~tf[rows]
-                if sf is not None:
-                    keep &= ~sf[s]
+            keep = _np_kept(time[pos], rows, s, None if times is None else times[tt], max_time, None if table is None else table[m])
             rows, s = rows[keep], s[keep]
             dt = None
             if times is not None:
-                dt = times[tt][rows] - times[st][s] + _RTE_SELF
-                if dt.size and (dt.min() < 0 or dt.max() >= _lib.HGT_RTE_LEN):
-                    raise IndexError("pyhgt_amd: neighbourhood: a time difference of %r outside [0, %d)"
-                                     % (dgraph.triples[m], _lib.HGT_RTE_LEN))
+                dt = _np_time_diff(times[tt], times[st], rows, s, "neighbourhood: a time difference of %r" % (dgraph.triples[m],))
             pending.append((st, s, mark[tt][rows], rel, dt))
             found[st].append(s[mark[st][s] < 0])
         level = [np.unique(np.concatenate(f + [np.zeros(0, np.int64)])) for f in found]
@@ -273,17 +242,6 @@ def _host_neighbourhood(dgraph, seeds, L, node_time, max_time, leave_out, self_l
 
 
 # ------------------------------------------------------------------------------------------------------------ the device build
-_pinned = threading.local()
-
-
-def _pinned_head():
-    """One pinned int64 buffer per thread for the per-level host read (each read waits for its copy before the next one is issued)."""
-    buf = getattr(_pinned, "buf", None)
-    if buf is None:
-        buf = _pinned.buf = torch.zeros(_lib.HGT_NB_HEAD_WORDS, dtype=torch.int64).pin_memory()
-    return buf
-
-
 def _marks(dgraph):
     """the resident marks: allocated and cleared on first use; cleared again in full if a call was interrupted"""
     dev = dgraph.device
@@ -356,7 +314,7 @@ def neighbourhood(dgraph, seeds, n_layers, node_time=None, max_time=None, leave_
     lib = _lib.load()
     i64 = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    ptr = _lib.ptr
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
         st = stream.cuda_stream
@@ -367,9 +325,7 @@ def neighbourhood(dgraph, seeds, n_layers, node_time=None, max_time=None, leave_
             """a leave-out array as resident uint8 on the device: one conversion and upload per OBJECT, then nothing of its size"""
             if f is None:
                 return None
-            make = lambda: (f if isinstance(f, torch.Tensor) and f.dtype == torch.uint8 else (f != 0) if isinstance(f, torch.Tensor) else
-                            torch.from_numpy(np.ascontiguousarray(np.asarray(f) != 0))).to(device=dev, dtype=torch.uint8).contiguous()
-            return ptr(_resident(dgraph, f, "flags", make)[0])
+            return ptr(_resident(dgraph, f, "flags", lambda: _flags_u8(f, dev))[0])
 
         types_c = (_lib.HgtNbType * T)()
         for t in range(T):
@@ -382,8 +338,7 @@ def neighbourhood(dgraph, seeds, n_layers, node_time=None, max_time=None, leave_
             tri_c[m] = _lib.HgtNbTriple(ip.data_ptr(), ptr(src), ptr(tm), flags(tf), flags(sf),
                                         None if time_ptr is None else time_ptr[tt], None if time_ptr is None else time_ptr[s_t],
                                         tt, s_t, rel, 0)
-        types_dev = torch.frombuffer(bytearray(bytes(types_c)), dtype=torch.uint8).to(dev)
-        tri_dev = torch.frombuffer(bytearray(bytes(tri_c)), dtype=torch.uint8).to(dev)
+        types_dev, tri_dev = _lib.table_to_device(types_c, dev), _lib.table_to_device(tri_c, dev)
         S = sum(int(a.numel() if isinstance(a, torch.Tensor) else a.size) for _, a in seed_lists)
         if S >= _LIMIT:
             raise ValueError("pyhgt_amd: neighbourhood takes fewer than 2^31 - 1 seeds")
@@ -394,7 +349,7 @@ def neighbourhood(dgraph, seeds, n_layers, node_time=None, max_time=None, leave_
         else:
             seed_id, seed_type = i64(0), i32(0)
         head = i64(_lib.HGT_NB_HEAD_WORDS)
-        host = _pinned_head()
+        host = _lib.pinned("nb_head", _lib.HGT_NB_HEAD_WORDS, torch.int64)   # (each read waits for its copy before the next is issued)
         mt = 0 if max_time is None else max(-2 ** 31, min(2 ** 31 - 1, int(max_time)))
         keys, rows_out, edges_out = [], [], []              # per level: sorted key list; (order, node_type, row_id); (src, dst, type, time)
         n_level, e_level = [], []

@@ -562,7 +562,7 @@ def sample_subgraph_host(dgraph, max_time, sampled_depth, sampled_number, inp, s
 # ---------------------------------------------------------------------------------------------------------------- device
 def _triple_table(dgraph):
     """the resident CSRs as the C table of meta triples"""
-    ptr = lambda t: t.data_ptr() if t.numel() else None
+    ptr = _lib.ptr
     triples_c = (_lib.HgtSamplerTriple * max(len(dgraph.triples), 1))()
     for m, ((tt, st, rel), (ip, src, tm)) in enumerate(zip(dgraph.tri_types, dgraph.csr_dev)):
         triples_c[m] = _lib.HgtSamplerTriple(ip.data_ptr(), ptr(src), ptr(tm), tt, st, rel, 0)
@@ -607,7 +607,7 @@ class DeviceSamplerState:
         self.sampled = [torch.zeros(c, **i32) for c in self.cap_s]
         self.cand = [torch.zeros(c, **i32) for c in self.cap_c]
         self.counts = torch.zeros(T, 4, **i32)
-        ptr = lambda t: t.data_ptr() if t.numel() else None
+        ptr = _lib.ptr
         self.types_c = (_lib.HgtSamplerType * T)()
         for t in range(T):
             self.types_c[t] = _lib.HgtSamplerType(ptr(self.score[t]), ptr(self.stamp[t]), ptr(self.serial[t]), ptr(self.sampled[t]),
@@ -674,7 +674,7 @@ class DeviceSamplerState:
         i32 = dict(dtype=torch.int32, device=self.dev)
         src, dst, etime = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
         node_time, node_id = torch.empty(N, **i32), torch.empty(N, **i32)
-        ptr = lambda t: t.data_ptr() if t.numel() else None
+        ptr = _lib.ptr
         _lib.check(fill(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
                         self.type_off.data_ptr(), N, E, ptr(src), ptr(dst), ptr(etime), ptr(node_time), ptr(node_id), *tail, self._stream()),
                    what + " (fill)")
@@ -809,7 +809,7 @@ class BatchedDeviceSamplerState:
         self.sampled = [torch.zeros(B, c, **i32) for c in self.cap_s]
         self.cand = [torch.zeros(B, c, **i32) for c in self.cap_c]
         self.counts = torch.zeros(B, T, 4, **i32)
-        ptr = lambda t: t.data_ptr() if t.numel() else None
+        ptr = _lib.ptr
         self.types_c = (_lib.HgtSamplerType * T)()           # the table of replica 0; the kernels shift it by b strides
         for t in range(T):
             self.types_c[t] = _lib.HgtSamplerType(ptr(self.score[t]), ptr(self.stamp[t]), ptr(self.serial[t]), ptr(self.sampled[t]),
@@ -891,7 +891,7 @@ class BatchedDeviceSamplerState:
         i32 = dict(dtype=torch.int32, device=self.dev)
         src, dst, etime = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
         node_time, node_id = torch.empty(N, **i32), torch.empty(N, **i32)
-        ptr = lambda t: t.data_ptr() if t.numel() else None
+        ptr = _lib.ptr
         _lib.check(fill(self.types_c, T, self.triples_c, M, B, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
                         self.type_off.data_ptr(), self.sizes.data_ptr(), self.offs.data_ptr(), N, E, ptr(src), ptr(dst), ptr(etime),
                         ptr(node_time), ptr(node_id), *tail, self._stream()), what + " (fill)")
@@ -1137,7 +1137,7 @@ class LabelSpace:
         if self.device is not None:
             self.col_of_dev = torch.from_numpy(self.col_of).to(self.device)
             ip, src, tm = dgraph.csr_dev[self.m]
-            ptr = lambda t: t.data_ptr() if t.numel() else None
+            ptr = _lib.ptr
             self._triple_c = _lib.HgtSamplerTriple(ip.data_ptr(), ptr(src), ptr(tm), *dgraph.tri_types[self.m], 0)
 
     def _device_ids(self, ids):

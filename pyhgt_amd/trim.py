@@ -20,7 +20,6 @@ rows and edges that leaves and in which order they stand; `trim_to_seeds` builds
 A seed or an edge end outside [0, n_nodes) raises IndexError; n_layers outside [1, MAX_LAYERS] raises ValueError.
 """
 import ctypes as C
-import threading
 from collections import namedtuple
 
 import numpy as np
@@ -86,17 +85,6 @@ def np_trim_graph(trim, node_type, edge_index, edge_type, edge_time=None):
 
 
 # --------------------------------------------------------------------------------------------------------------- the device build
-_pinned = threading.local()
-
-
-def _pinned_counts():
-    """One pinned int32 buffer per thread for the trim's single host read (the read waits for its event before the next trim starts)."""
-    buf = getattr(_pinned, "buf", None)
-    if buf is None:
-        buf = _pinned.buf = torch.zeros(2 * MAX_LAYERS + 2, dtype=torch.int32).pin_memory()
-    return buf
-
-
 def _graph_tensors(graph, num_types, num_relations):
     if isinstance(graph, tuple) and len(graph) == 7:           # a _DeviceGraph / the 7-tuple of to_torch on the device
         _, node_type, edge_time, edge_index, edge_type, node_dict, edge_dict = graph
@@ -187,7 +175,7 @@ def trim_to_seeds(graph, seeds, n_layers, num_types=None, num_relations=None):
     need = C.c_uint64()
     _lib.check(lib.hgt_trim_tmp_bytes(N, E, L, C.byref(need)), "hgt_trim_tmp_bytes")
     i64 = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    ptr = _lib.ptr
     sr, sc = (edge_index.stride(0), edge_index.stride(1)) if E > 0 else (0, 1)
     t = TrimmedGraph()
     with torch.cuda.device(dev):
@@ -198,7 +186,7 @@ def trim_to_seeds(graph, seeds, n_layers, num_types=None, num_relations=None):
         ei_out, et_out, out_rows = i64(2, E), i64(E), i64(S)
         tm_out = None if edge_time is None else i64(E)
         counts = torch.empty(2 * L + 2, dtype=torch.int32, device=dev)
-        host = _pinned_counts()
+        host = _lib.pinned("trim_counts", 2 * MAX_LAYERS + 2, torch.int32)   # (the read waits for its event before the next trim starts)
         _lib.check(lib.hgt_trim_hops(ptr(edge_index), sr, sc, N, E, ptr(seeds), S, L, tmp.data_ptr(), tmp.numel(), stream.cuda_stream),
                    "hgt_trim_hops")
         _lib.check(lib.hgt_trim_fill(ptr(edge_index), sr, sc, ptr(edge_type), ptr(edge_time), ptr(node_type), N, E, ptr(seeds), S, L,

@@ -120,21 +120,37 @@ def _host_flags(f):
     return None if f is None else (f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)) != 0
 
 
+def _flags_u8(f, dev):
+    """a leave-out array (bool / uint8 / anything compared with 0) as a contiguous uint8 tensor on `dev`"""
+    if not isinstance(f, torch.Tensor):
+        f = torch.from_numpy(np.ascontiguousarray(np.asarray(f) != 0))
+    elif f.dtype != torch.uint8:
+        f = f != 0
+    return f.to(device=dev, dtype=torch.uint8).contiguous()
+
+
+def _feature_width(n_nodes, feats, types):
+    """the common width of the feature matrices of the types that have nodes (ValueError: a type without one, differing widths); 0
+    for a graph whose types are all empty"""
+    widths = set()
+    for t, n, f in zip(types, n_nodes, feats):
+        if n == 0:
+            continue
+        if f is None:
+            raise ValueError("pyhgt_amd: no feature matrix for node type %r" % t)
+        widths.add(int(np.shape(f)[1]))
+    if len(widths) > 1:
+        raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (sorted(widths),))
+    return widths.pop() if widths else 0
+
+
 def _host_features(dgraph):
     """the types' feature matrices concatenated in type order (float32), or None for a graph that carries none"""
     feats = dgraph.features_host
     if feats is None:
         return None
-    mats = []
-    for t, n, f in zip(dgraph.types, dgraph.n_nodes, feats):
-        if f is None or n == 0:
-            if n > 0:
-                raise ValueError("pyhgt_amd: no feature matrix for node type %r" % t)
-            continue
-        mats.append(_host_array(f))
-    widths = sorted({m.shape[1] for m in mats})
-    if len(widths) > 1:
-        raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (widths,))
+    _feature_width(dgraph.n_nodes, feats, dgraph.types)
+    mats = [_host_array(f) for n, f in zip(dgraph.n_nodes, feats) if n > 0]
     return np.concatenate(mats, axis=0) if mats else np.zeros((0, 0), np.float32)
 
 
@@ -170,6 +186,37 @@ def label_edge_flags(dgraph, relations, node_type, ids):
 
 
 # ------------------------------------------------------------------------------------------------------------ the definition
+def _np_kept(time, rows, src, tgt_times, max_time, flags):
+    """The entry rule (module docstring: max_time, leave_out) for entries of one triple: time[i] the stored time of entry i, rows[i] its
+    target and src[i] its source (ids inside their types), tgt_times the node times of the target type or None for no tables,
+    flags = (target_flags, source_flags) as `_leave_out_table` gives them, or None.  -> bool mask, True = kept.  The device statement
+    is entry_kept (csrc/hgt_graph_rule.h)."""
+    keep = np.ones(len(src), bool)
+    if max_time is not None:
+        t = np.asarray(time).astype(np.int64)
+        none = t == TIME_NONE
+        if tgt_times is not None:
+            t = np.where(none, tgt_times[rows], t)
+            none = np.zeros_like(none)
+        keep &= none | (t <= int(max_time))
+    if flags is not None:
+        tf, sf = (_host_flags(f) for f in flags)
+        if tf is not None:
+            keep &= ~tf[rows]
+        if sf is not None:
+            keep &= ~sf[src]
+    return keep
+
+
+def _np_time_diff(tgt_times, src_times, rows, src, what):
+    """edge_time of kept entries (module docstring: node_time) as int64; IndexError for a value outside [0, 240), with `what` = the
+    caller and its triple in the message.  The device statement is entry_time_diff (csrc/hgt_graph_rule.h)."""
+    dt = tgt_times[rows] - src_times[src] + _RTE_SELF
+    if dt.size and (dt.min() < 0 or dt.max() >= _lib.HGT_RTE_LEN):
+        raise IndexError("pyhgt_amd: %s outside [0, %d)" % (what, _lib.HGT_RTE_LEN))
+    return dt
+
+
 def np_whole_graph(dgraph, node_time=None, max_time=None, leave_out=None, self_loops=True):
     """The definition (module docstring) on `dgraph.csr`.  -> WholeGraphArrays: the numpy arrays of the 7-tuple (node_feature float32
     [N, width] or None for a graph without features, node_type int64[N], edge_time int64[E] or None, edge_index int64[2, E] with row 0
@@ -191,28 +238,12 @@ def np_whole_graph(dgraph, node_time=None, max_time=None, leave_out=None, self_l
     for m, ((tt, st, rel), (indptr, src, time)) in enumerate(zip(dgraph.tri_types, dgraph.csr)):
         row = np.repeat(np.arange(dgraph.n_nodes[tt], dtype=np.int64), np.diff(indptr))
         s = src.astype(np.int64)
-        keep = np.ones(s.size, bool)
-        if max_time is not None:
-            t = time.astype(np.int64)
-            none = t == TIME_NONE
-            if times is not None:
-                t = np.where(none, times[tt][row], t)
-                none = np.zeros_like(none)
-            keep &= none | (t <= int(max_time))
-        if table is not None:
-            tf, sf = (_host_flags(f) for f in table[m])
-            if tf is not None:
-                keep &= ~tf[row]
-            if sf is not None:
-                keep &= ~sf[s]
+        keep = _np_kept(time, row, s, None if times is None else times[tt], max_time, None if table is None else table[m])
         row, s = row[keep], s[keep]
         srcs.append(s + type_off[st])
         dsts.append(row + type_off[tt])
         if times is not None:
-            dt = times[tt][row] - times[st][s] + _RTE_SELF
-            if dt.size and (dt.min() < 0 or dt.max() >= _lib.HGT_RTE_LEN):
-                raise IndexError("pyhgt_amd: whole_graph: a time difference of %r outside [0, %d)" % (dgraph.triples[m], _lib.HGT_RTE_LEN))
-            tms.append(dt)
+            tms.append(_np_time_diff(times[tt], times[st], row, s, "whole_graph: a time difference of %r" % (dgraph.triples[m],)))
         per_rel[rel] += row.size
     if self_loops:
         srcs.append(np.arange(N, dtype=np.int64)); dsts.append(np.arange(N, dtype=np.int64))
@@ -233,26 +264,6 @@ def np_whole_graph(dgraph, node_time=None, max_time=None, leave_out=None, self_l
 
 
 # ------------------------------------------------------------------------------------------------------------ the view
-class _PinnedHeads:
-    """Pinned host buffers for the one read-back of a FILTERED view (rel_ptr and the flag word), kept and reused: allocating pinned
-    memory costs more than the build it would serve.  A buffer is out of the list from its copy to its read, which the same call
-    makes; an unfiltered view copies nothing to the host."""
-    WORDS = _lib.HGT_SAMPLER_MAX_TRIPLES + 3
-    free = []
-
-    @classmethod
-    def take(cls):
-        try:
-            return cls.free.pop()
-        except IndexError:
-            return torch.zeros(cls.WORDS, dtype=torch.int32).pin_memory()
-
-    @classmethod
-    def give(cls, buf):
-        if len(cls.free) < 16:
-            cls.free.append(buf)
-
-
 class _Rows:
     """what a whole-graph view knows about its rows"""
     _n_nodes = None        # {type: count}
@@ -314,16 +325,8 @@ def _device_features(dgraph):
     feats = dgraph.features
     if feats is None:
         raise ValueError("pyhgt_amd: the DeviceHeteroGraph carries no features")
-    mats = []
-    for t, n, f in zip(dgraph.types, dgraph.n_nodes, feats):
-        if n == 0:
-            continue
-        if f is None:
-            raise ValueError("pyhgt_amd: no feature matrix for node type %r" % t)
-        mats.append(f)
-    widths = sorted({f.size(1) for f in mats})
-    if len(widths) > 1:
-        raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (widths,))
+    _feature_width(dgraph.n_nodes, feats, dgraph.types)
+    mats = [f for n, f in zip(dgraph.n_nodes, feats) if n > 0]
     if not mats:
         return torch.zeros(0, 0, dtype=torch.float32, device=dgraph.device)
     return mats[0] if len(mats) == 1 else torch.cat(mats, dim=0)
@@ -356,7 +359,7 @@ def whole_graph(dgraph, node_time=None, max_time=None, leave_out=None, self_loop
             return None
         t = (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dtype).contiguous()
         keep_alive.append(t)
-        return t.data_ptr() if t.numel() else None
+        return _lib.ptr(t)
 
     with torch.cuda.device(dev):
         time_ptr = None if times is None else [dev_array(a, torch.int32) for a in times]
@@ -366,11 +369,10 @@ def whole_graph(dgraph, node_time=None, max_time=None, leave_out=None, self_loop
             if f is None:
                 return None
             if id(f) not in flag_ptr:
-                flag_ptr[id(f)] = dev_array(f if isinstance(f, torch.Tensor) and f.dtype == torch.uint8 else
-                                            (f != 0) if isinstance(f, torch.Tensor) else np.asarray(f) != 0, torch.uint8)
+                flag_ptr[id(f)] = dev_array(_flags_u8(f, dev), torch.uint8)
             return flag_ptr[id(f)]
 
-        ptr = lambda t: t.data_ptr() if t.numel() else None
+        ptr = _lib.ptr
         tab = (_lib.HgtViewTriple * (M + 1))()
         for m, ((tt, st, rel), (ip, src, tm)) in enumerate(zip(dgraph.tri_types, dgraph.csr_dev)):
             tf, sf = (None, None) if table is None else table[m]
@@ -378,31 +380,30 @@ def whole_graph(dgraph, node_time=None, max_time=None, leave_out=None, self_loop
                                         None if time_ptr is None else time_ptr[tt], None if time_ptr is None else time_ptr[st],
                                         int(first[m]), dgraph.n_nodes[tt], int(type_off[tt]), int(type_off[st]), rel)
         tab[M] = _lib.HgtViewTriple(None, None, None, None, None, None, None, int(first[M]), N, 0, 0, R - 1)
-        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        tab_dev = _lib.table_to_device(tab, dev)
         has_time = times is not None
         i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
         i64 = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
         src32, dst32, time32 = i32(E_cap), i32(E_cap), (i32(E_cap) if has_time else None)
         ei, et, tm64 = i64(2, E_cap), i64(E_cap), (i64(E_cap) if has_time else None)
         head = i32(R + 2)
-        head_host = _PinnedHeads.take() if filtered else None
+        # (the one read-back of a FILTERED view, rel_ptr and the flag word; an unfiltered view touches no pinned memory)
+        head_host = _lib.pinned("view_head", _lib.HGT_SAMPLER_MAX_TRIPLES + 3, torch.int32) if filtered else None
         lib = _lib.load()
         need = C.c_uint64()
         _lib.check(lib.hgt_view_tmp_bytes(E_cap, C.byref(need)), "hgt_view_tmp_bytes")
         tmp = torch.empty(int(need.value) if filtered else 0, dtype=torch.uint8, device=dev)
         mt = 0 if max_time is None else max(-2 ** 31, min(2 ** 31 - 1, int(max_time)))
         stream = torch.cuda.current_stream(dev)
-        opt = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
         _lib.check(lib.hgt_view_build(tab_dev.data_ptr(), M, R, E_cap, int(filtered), int(max_time is not None), mt, int(has_time),
-                                      opt(src32), opt(dst32), opt(time32), opt(ei), E_cap, opt(et), opt(tm64), head.data_ptr(),
-                                      opt(tmp), tmp.numel(), opt(head_host), stream.cuda_stream), "hgt_view_build")
+                                      ptr(src32), ptr(dst32), ptr(time32), ptr(ei), E_cap, ptr(et), ptr(tm64), head.data_ptr(),
+                                      ptr(tmp), tmp.numel(), ptr(head_host), stream.cuda_stream), "hgt_view_build")
         # (the table, the scratch and the uploaded copies were allocated on this stream: the allocator hands their memory to later
         #  work of the same stream only, so they may go out of scope here)
         E = E_cap
         if filtered:
             stream.synchronize()                                 # the one host read of a filtered view: rel_ptr and the flag word
             E, flag = int(head_host[R]), int(head_host[R + 1])
-            _PinnedHeads.give(head_host)
             if flag & _lib.HGT_VIEW_BAD_TIME:
                 raise IndexError("pyhgt_amd: whole_graph: a time difference outside [0, %d)" % _lib.HGT_RTE_LEN)
             src32, dst32, et = src32[:E], dst32[:E], et[:E]

@@ -95,6 +95,49 @@ def test_filters_do_what_they_say():
     assert a.edge_index.shape[1] == 14 and a.node_type.size == 14 and np.array_equal(a.sorted[3], [0, 0, 0, 0, 0, 0, 14])
 
 
+def test_entry_rule_truth_table():
+    """_np_kept / _np_time_diff, the one numpy statement of the entry rule both np_whole_graph and np_neighbourhood call, entry by
+    entry against a loop written out here: stored time below / at / above max_time / TIME_NONE x target table absent / target time
+    <= max_time / > max_time x target flag x source flag x max_time None / given (and each flag array absent)."""
+    from pyhgt_amd.sampler import TIME_NONE
+    from pyhgt_amd.view import _np_kept, _np_time_diff
+    MAX = 2000
+    tgt_table = np.array([MAX, MAX, MAX + 5, MAX + 5], np.int64)          # target nodes: time <= / > max_time x flag unset / set
+    tf, sf = np.array([0, 1, 0, 1], bool), np.array([0, 1], np.uint8)
+    stored, rows, src = (np.array(x) for x in zip(*itertools.product([MAX - 1, MAX, MAX + 1, TIME_NONE], range(4), range(2))))
+    stored = stored.astype(np.int32)
+
+    def kept(st, r, s, tgt_times, max_time, flags):
+        if max_time is not None:
+            if st == TIME_NONE:                                           # the entry takes the target's time, if there is one
+                if tgt_times is not None and tgt_times[r] > max_time:
+                    return False
+            elif st > max_time:
+                return False
+        if flags is not None and flags[0] is not None and flags[0][r]:
+            return False
+        if flags is not None and flags[1] is not None and flags[1][s]:
+            return False
+        return True
+
+    seen = set()
+    for tgt_times, max_time, flags in itertools.product([None, tgt_table], [None, MAX], [None, (tf, sf), (tf, None), (None, sf)]):
+        got = _np_kept(stored, rows, src, tgt_times, max_time, flags)
+        want = [kept(st, r, s, tgt_times, max_time, flags) for st, r, s in zip(stored.tolist(), rows, src)]
+        assert got.dtype == bool and got.tolist() == want, (tgt_times, max_time, flags)
+        seen.update(want)
+    assert seen == {True, False}
+    # the time difference: 0 and 239 are the ends of the RTE table, -1 and 240 lie outside
+    tt, st = np.array([2000, 2100], np.int64), np.array([2120, 1981, 2000], np.int64)
+    r, s = np.array([0, 1, 0, 1]), np.array([0, 1, 2, 2])
+    dt = _np_time_diff(tt, st, r, s, "whole_graph: a time difference of ('a', 'b', 'link')")
+    assert dt.dtype == np.int64 and dt.tolist() == [0, 239, 120, 220]
+    assert _np_time_diff(tt, st, r[:0], s[:0], "whole_graph").size == 0
+    for what, src_time in (("whole_graph", 2121), ("neighbourhood", 1880)):        # 2000 - 2121 + 120 = -1; 2000 - 1880 + 120 = 240
+        with pytest.raises(IndexError, match=what + r".*outside \[0, 240\)"):
+            _np_time_diff(tt, np.array([src_time], np.int64), np.array([0]), np.array([0]), what + ": a time difference of x")
+
+
 def test_argument_errors():
     dg = W.hand_graph()
     with pytest.raises(ValueError):

@@ -6,23 +6,13 @@
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -Iinclude -Ipyhgt_amd/csrc tools/batch_abi_check.cpp pyhgt_amd/csrc/hgt_sampler.hip -o batch_abi_check && ./batch_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "batch_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
 
 int main() {
     const int T = HGT_SAMPLER_MAX_TYPES, M = HGT_SAMPLER_MAX_TRIPLES, R = M + 1, B = HGT_SAMPLER_MAX_BATCH;
@@ -136,6 +126,5 @@ int main() {
     rows[T - 1] = -1;
     EXPECT(hgt_sampler_gather_features(feats.data(), rows.data(), T, B, 4, q, q, q, 3, out, nullptr), HGT_ERR_INVALID_ARG);
 
-    std::printf(failures ? "batch_abi_check: %d FAILED\n" : "batch_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("batch_abi_check");
 }

@@ -7,23 +7,13 @@
 //         -Iinclude -Ipyhgt_amd/csrc tools/class_loss_abi_check.cpp pyhgt_amd/csrc/hgt_task_loss.hip pyhgt_amd/csrc/hgt_sampler_labels.hip \
 //         -o class_loss_abi_check && ./class_loss_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "class_loss_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
 
 int main() {
     std::vector<uint64_t> buf(64, 0);      // host memory behind every pointer: no call may reach a kernel
@@ -117,6 +107,5 @@ int main() {
     tr.time = i, tr.src = nullptr;
     EXPECT(hgt_sampler_label_columns(&tr, 4, 4, i, 2, i, 8, 0, 0, 0, i, 4, i, nullptr), HGT_ERR_INVALID_ARG);
 
-    std::printf(failures ? "class_loss_abi_check: %d FAILED\n" : "class_loss_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("class_loss_abi_check");
 }

@@ -7,30 +7,13 @@
 //         -Iinclude -Ipyhgt_amd/csrc tools/graph_build_abi_check.cpp pyhgt_amd/csrc/hgt_graph_build.hip -o graph_build_abi_check \
 //         && ./graph_build_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "graph_build_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
-#define CHECK(cond)                                                    \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            std::printf("line %d: %s is false\n", __LINE__, #cond);   \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 int main() {
     std::vector<uint64_t> buf(64, 0);      // host memory behind every pointer: no call may reach a kernel
@@ -129,6 +112,5 @@ int main() {
     EXPECT(hgt_neighbour_mean(tab.data(), 2, f, 128, 7, 10 * C, 128, f, 128, p, m1 - 1, nullptr), HGT_ERR_WORKSPACE);
     EXPECT(hgt_neighbour_mean(tab.data(), 2, f, 128, 7, 9, 128, f, 128, p, 0, nullptr), HGT_ERR_WORKSPACE);
 
-    std::printf(failures ? "graph_build_abi_check: %d FAILED\n" : "graph_build_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("graph_build_abi_check");
 }

@@ -7,31 +7,14 @@
 //         -Iinclude -Ipyhgt_amd/csrc tools/matcher_topk_abi_check.cpp pyhgt_amd/csrc/hgt_matcher_topk.hip -o matcher_topk_abi_check \
 //         && ./matcher_topk_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "matcher_topk_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
-#define CHECK(cond)                                                    \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            std::printf("line %d: %s is false\n", __LINE__, #cond);   \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 int main() {
     std::vector<int64_t> buf(64, 0);       // host memory behind every pointer: no call may reach a kernel
@@ -125,6 +108,5 @@ int main() {
     EXPECT(RANK(f, 64, 5000, f, 64, 64, 64, 0.125f, 0, p, p, p, r - 1), WS);
     EXPECT(RANK(f, 64, 5000, f, 64, 64, 64, 0.125f, 128, p, p, p, r), WS);
 
-    std::printf(failures ? "matcher_topk_abi_check: %d FAILED\n" : "matcher_topk_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("matcher_topk_abi_check");
 }

@@ -7,23 +7,13 @@
 //         -Iinclude -Ipyhgt_amd/csrc tools/metrics_abi_check.cpp pyhgt_amd/csrc/hgt_task_metrics.hip -o metrics_abi_check \
 //         && ./metrics_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "metrics_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
 
 int main() {
     std::vector<uint64_t> buf(64, 0);      // host memory behind every pointer: no call may reach a kernel
@@ -86,6 +76,5 @@ int main() {
     EXPECT(hgt_segment_first_nll_bwd(f, q, 3, 8, f, nullptr, f, nullptr), HGT_ERR_INVALID_ARG);
     EXPECT(hgt_segment_first_nll_bwd(f, q, INT_MAX, INT_MAX, f, f, nullptr, nullptr), HGT_ERR_INVALID_ARG);
 
-    std::printf(failures ? "metrics_abi_check: %d FAILED\n" : "metrics_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("metrics_abi_check");
 }

@@ -9,30 +9,13 @@
 //         -Iinclude -Ipyhgt_amd/csrc tools/neighbourhood_abi_check.cpp pyhgt_amd/csrc/hgt_neighbourhood.hip -o neighbourhood_abi_check \
 //         && ./neighbourhood_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "neighbourhood_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
-#define CHECK(cond)                                                    \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            std::printf("line %d: %s is false\n", __LINE__, #cond);   \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 int main() {
     std::vector<int64_t> buf(64, 0);       // host memory behind every pointer: no call may reach a kernel
@@ -186,6 +169,5 @@ int main() {
     EXPECT(hgt_nb_reset(ty, 2, u, -1, nullptr), INV);
     EXPECT(hgt_nb_reset(ty, 2, u, big, nullptr), INV);
 
-    std::printf(failures ? "neighbourhood_abi_check: %d FAILED\n" : "neighbourhood_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("neighbourhood_abi_check");
 }

@@ -7,31 +7,14 @@
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -Iinclude -Ipyhgt_amd/csrc tools/optim_abi_check.cpp pyhgt_amd/csrc/hgt_optim.hip -o optim_abi_check && ./optim_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "optim_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
-#define CHECK(cond)                                                    \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            std::printf("line %d: %s is false\n", __LINE__, #cond);   \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 int main() {
     std::vector<uint64_t> buf(64, 0);      // host memory behind every pointer: no call may reach a kernel
@@ -140,6 +123,5 @@ int main() {
     EXPECT(hgt_adamw_step(T, 3, G, 1, Ch, big, f, 0.5f, nullptr), HGT_ERR_UNSUPPORTED);
     EXPECT(hgt_adamw_step(T, 3, G, 1, Ch, big, nullptr, 0.0f, nullptr), HGT_ERR_UNSUPPORTED);
 
-    std::printf(failures ? "optim_abi_check: %d FAILED\n" : "optim_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("optim_abi_check");
 }

@@ -7,23 +7,13 @@
 //         -Iinclude -Ipyhgt_amd/csrc tools/task_abi_check.cpp pyhgt_amd/csrc/hgt_sampler.hip pyhgt_amd/csrc/hgt_sampler_labels.hip \
 //         -o task_abi_check && ./task_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "task_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
 
 int main() {
     const int T = HGT_SAMPLER_MAX_TYPES, M = HGT_SAMPLER_MAX_TRIPLES, R = M + 1;
@@ -97,6 +87,5 @@ int main() {
     EXPECT(hgt_sampler_labels(&no_time, 8, 8, q, 2, q, 4, 1, 0, 0, d, 4, q, q, nullptr), HGT_ERR_INVALID_ARG);
     EXPECT(hgt_sampler_labels(&no_indptr, 8, 8, q, 2, q, 4, 0, 0, 0, d, 4, q, q, nullptr), HGT_ERR_INVALID_ARG);
 
-    std::printf(failures ? "task_abi_check: %d FAILED\n" : "task_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("task_abi_check");
 }

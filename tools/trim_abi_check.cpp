@@ -6,30 +6,13 @@
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -Iinclude -Ipyhgt_amd/csrc tools/trim_abi_check.cpp pyhgt_amd/csrc/hgt_trim.hip -o trim_abi_check && ./trim_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "trim_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
-#define CHECK(cond)                                                    \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            std::printf("line %d: %s is false\n", __LINE__, #cond);   \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 int main() {
     std::vector<int64_t> buf(64, 0);       // host memory behind every pointer: no call may reach a kernel
@@ -102,6 +85,5 @@ int main() {
     EXPECT(FILL(p, p, p, p, 1000, 5000, p, 3, 2, p, a, i32, p, p, p, p, p, p, p, p, i32, nullptr), INV);
     EXPECT(FILL(p, p, p, p, 1000, 5000, p, 3, 2, p, a - 1, i32, p, p, p, p, p, p, p, p, i32, p), HGT_ERR_WORKSPACE);
 
-    std::printf(failures ? "trim_abi_check: %d FAILED\n" : "trim_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("trim_abi_check");
 }

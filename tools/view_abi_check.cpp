@@ -6,30 +6,13 @@
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -Iinclude -Ipyhgt_amd/csrc tools/view_abi_check.cpp pyhgt_amd/csrc/hgt_graph_view.hip -o view_abi_check && ./view_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "view_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
-#define CHECK(cond)                                                    \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            std::printf("line %d: %s is false\n", __LINE__, #cond);   \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 int main() {
     std::vector<int64_t> buf(64, 0);       // host memory behind every pointer: no call may reach a kernel
@@ -86,6 +69,5 @@ int main() {
     EXPECT(BUILD(tab, 3, 4, 5000, 1, 1, i32, i32, i32, p, 5000, p, p, i32, p, 0), HGT_ERR_WORKSPACE);
     EXPECT(BUILD(tab, 3, 4, 5000, 1, 0, i32, i32, nullptr, nullptr, 0, nullptr, nullptr, i32, p, 3), HGT_ERR_WORKSPACE);
 
-    std::printf(failures ? "view_abi_check: %d FAILED\n" : "view_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("view_abi_check");
 }

@@ -6,24 +6,14 @@
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -Iinclude -Ipyhgt_amd/csrc tools/vote_abi_check.cpp pyhgt_amd/csrc/hgt_task_vote.hip -o vote_abi_check && ./vote_abi_check
 //
+// (`make -C pyhgt_amd/csrc abicheck` builds and runs all the *_abi_check programs this way; it reads the .hip names from the line above.)
 // Exit status 0 and "vote_abi_check: ok" = every call returned the documented code and the sanitizers found nothing.  (n_rows == 0
 // with counts_out zeroes the counts on the stream: that path needs a device and is covered by the GPU tests.)
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
+#include "abi_check.h"
 #include "hgt_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, code)                                                                        \
-    do {                                                                                          \
-        const int rc_ = (call);                                                                   \
-        if (rc_ != (code)) {                                                                      \
-            std::printf("line %d: %s returned %d, expected %d\n", __LINE__, #call, rc_, (code)); \
-            ++failures;                                                                           \
-        }                                                                                         \
-    } while (0)
 
 int main() {
     std::vector<uint64_t> buf(64, 0);      // host memory behind every pointer: no call may reach a kernel
@@ -112,6 +102,5 @@ int main() {
     EXPECT(hgt_vote_add(f, LLONG_MAX, INT_MAX, q, two, 2, i, 4, f, LLONG_MAX, i, 4, nullptr), HGT_ERR_UNSUPPORTED);
     EXPECT(hgt_vote_add(f, LLONG_MAX, INT_MAX - 1023, q, two, 2, i, 4, f, LLONG_MAX, i, 4, nullptr), HGT_ERR_UNSUPPORTED);
 
-    std::printf(failures ? "vote_abi_check: %d FAILED\n" : "vote_abi_check: ok\n", failures);
-    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+    return abi_check_report("vote_abi_check");
 }
