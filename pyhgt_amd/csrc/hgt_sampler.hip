@@ -833,28 +833,58 @@ constexpr int HUB_BLOCKS = 256;      // workgroups of the hub launches: each loo
 
 }  // namespace
 
-extern "C" int hgt_sampler_seed(const hgt_sampler_type* types_host, int32_t n_types, int32_t type, const int32_t* ids, const int32_t* times,
-                                int32_t n, int32_t step, void* stream) {
+// One host body per step, for the single entry points (BATCHED = false: n_batch is 1, the Philox key is `seed`) and the batched ones
+// (include/hgt_hip.h, "Batched device sampler": n_batch replicas in gridDim.y of the launches of one batch, the keys from seeds_host).
+// Both run the same checks in the same order; `if constexpr` stands around what differs: batch_check and make_keys, which wrapper is
+// launched with which trailing arguments, and in the fill pass the offsets launch and BatchIO.
+static int batch_check(int32_t n_batch) {
+    if (n_batch < 1) return HGT_ERR_INVALID_ARG;
+    if (n_batch > HGT_SAMPLER_MAX_BATCH) return HGT_ERR_UNSUPPORTED;
+    return HGT_OK;
+}
+
+static int make_keys(const uint64_t* seeds_host, int32_t n_batch, Keys* out) {
+    if (!seeds_host) return HGT_ERR_INVALID_ARG;
+    for (int b = 0; b < HGT_SAMPLER_MAX_BATCH; ++b) {
+        const uint64_t seed = b < n_batch ? seeds_host[b] : 0;
+        out->k[b][0] = (uint32_t)seed;
+        out->k[b][1] = (uint32_t)(seed >> 32);
+    }
+    return HGT_OK;
+}
+
+template <bool BATCHED>
+static int seed_step(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, int32_t type, const int32_t* ids,
+                      const int32_t* times, int32_t n, int32_t step, void* stream) {
     Tables tb;
     if (int rc = make_tables(types_host, n_types, nullptr, 0, &tb, nullptr)) return rc;
+    if constexpr (BATCHED)
+        if (int rc = batch_check(n_batch)) return rc;
     if (type < 0 || type >= n_types || n < 0 || step < 0) return HGT_ERR_INVALID_ARG;
     if (n > types_host[type].cap_sampled) return HGT_ERR_WORKSPACE;
     if (n > 0 && (!ids || !times)) return HGT_ERR_INVALID_ARG;
-    k_seed<<<blocks_for(n > 0 ? n : 1, 256), 256, 0, (hipStream_t)stream>>>(tb, type, ids, times, n, step);
+    (BATCHED ? k_seed_batched : k_seed)<<<dim3(blocks_for(n > 0 ? n : 1, 256), n_batch), 256, 0, (hipStream_t)stream>>>(tb, type, ids, times, n, step);
     HGT_CHECK_LAUNCH();
     return HGT_OK;
 }
 
-extern "C" int hgt_sampler_add_budget(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
-                                      int32_t n_triples, int32_t type, int32_t step, int32_t sampled_number, int32_t max_new,
-                                      int32_t has_max_time, int32_t max_time, uint64_t seed, int32_t* hub, int64_t hub_entries, void* stream) {
+template <bool BATCHED>
+static int budget_step(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
+                      int32_t n_batch, int32_t type, int32_t step, int32_t sampled_number, int32_t max_new, int32_t has_max_time,
+                      int32_t max_time, uint64_t seed, const uint64_t* seeds_host, int32_t* hub, int64_t hub_entries, void* stream) {
     Tables tb;
+    Keys keys;
     if (int rc = make_tables(types_host, n_types, triples_host, n_triples, &tb, nullptr)) return rc;
+    if constexpr (BATCHED) {
+        if (int rc = batch_check(n_batch)) return rc;
+        if (int rc = make_keys(seeds_host, n_batch, &keys)) return rc;
+    }
     if (type < 0 || type >= n_types || step < 0 || sampled_number < 1 || max_new < 0) return HGT_ERR_INVALID_ARG;
     if (sampled_number > HGT_SAMPLER_MAX_NUMBER) return HGT_ERR_UNSUPPORTED;
     BudgetParams P;
     P.t = type; P.step = step; P.sn = sampled_number; P.has_max = has_max_time != 0; P.max_time = max_time; P.max_new = max_new;
-    P.k0 = (uint32_t)seed; P.k1 = (uint32_t)(seed >> 32);
+    P.k0 = BATCHED ? 0 : (uint32_t)seed;                      // batched: the replicas' keys ride in `keys`
+    P.k1 = BATCHED ? 0 : (uint32_t)(seed >> 32);
     P.ntr = 0;
     for (int m = 0; m < HGT_SAMPLER_MAX_TRIPLES; ++m) P.sel[m] = 0;
     for (int m = 0; m < n_triples; ++m) {
@@ -869,18 +899,31 @@ extern "C" int hgt_sampler_add_budget(const hgt_sampler_type* types_host, int32_
     if (!hub) return HGT_ERR_INVALID_ARG;
     if (hub_entries < rows + 1) return HGT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hub, 0, 4, st) != hipSuccess) return HGT_ERR_LAUNCH;
-    k_budget<<<blocks_for(rows, 4), 256, 0, st>>>(tb, P, hub, (int)rows);
-    HGT_CHECK_LAUNCH();
-    k_budget_hub<<<(unsigned)(rows < HUB_BLOCKS ? rows : HUB_BLOCKS), BIG, 0, st>>>(tb, P, hub, (int)rows);
+    if (hipMemsetAsync(hub, 0, 4 * (size_t)n_batch, st) != hipSuccess) return HGT_ERR_LAUNCH;
+    const dim3 grid(blocks_for(rows, 4), n_batch), hub_grid((unsigned)(rows < HUB_BLOCKS ? rows : HUB_BLOCKS), n_batch);
+    if constexpr (BATCHED) {
+        k_budget_batched<<<grid, 256, 0, st>>>(tb, P, keys, hub, hub_entries - 1, (int)rows);
+        HGT_CHECK_LAUNCH();
+        k_budget_hub_batched<<<hub_grid, BIG, 0, st>>>(tb, P, keys, hub, hub_entries - 1, (int)rows);
+    } else {
+        k_budget<<<grid, 256, 0, st>>>(tb, P, hub, (int)rows);
+        HGT_CHECK_LAUNCH();
+        k_budget_hub<<<hub_grid, BIG, 0, st>>>(tb, P, hub, (int)rows);
+    }
     HGT_CHECK_LAUNCH();
     return HGT_OK;
 }
 
-extern "C" int hgt_sampler_select(const hgt_sampler_type* types_host, int32_t n_types, int32_t type, int32_t step, int32_t sampled_number,
-                                  uint64_t seed, uint64_t* keys, int32_t* tmp, int64_t tmp_entries, void* stream) {
+template <bool BATCHED>
+static int select_step(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, int32_t type, int32_t step, int32_t sampled_number,
+                  uint64_t seed, const uint64_t* seeds_host, uint64_t* keys, int32_t* tmp, int64_t tmp_entries, void* stream) {
     Tables tb;
+    Keys seeds;
     if (int rc = make_tables(types_host, n_types, nullptr, 0, &tb, nullptr)) return rc;
+    if constexpr (BATCHED) {
+        if (int rc = batch_check(n_batch)) return rc;
+        if (int rc = make_keys(seeds_host, n_batch, &seeds)) return rc;
+    }
     if (type < 0 || type >= n_types || step < 0 || sampled_number < 1) return HGT_ERR_INVALID_ARG;
     if (sampled_number > HGT_SAMPLER_MAX_NUMBER) return HGT_ERR_UNSUPPORTED;
     const int cap = types_host[type].cap_cand;
@@ -888,18 +931,18 @@ extern "C" int hgt_sampler_select(const hgt_sampler_type* types_host, int32_t n_
     if (!keys || !tmp) return HGT_ERR_INVALID_ARG;
     if (tmp_entries < cap) return HGT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    k_select_keys<<<blocks_for(cap, 256), 256, 0, st>>>(tb, type, step, (uint32_t)seed, (uint32_t)(seed >> 32), keys);
-    HGT_CHECK_LAUNCH();
-    k_select_pick<<<1, BIG, 0, st>>>(tb, type, sampled_number, keys, tmp);
+    const dim3 grid(blocks_for(cap, 256), n_batch), pick_grid(1, n_batch);
+    if constexpr (BATCHED) {
+        k_select_keys_batched<<<grid, 256, 0, st>>>(tb, type, step, seeds, keys, tmp_entries);
+        HGT_CHECK_LAUNCH();
+        k_select_pick_batched<<<pick_grid, BIG, 0, st>>>(tb, type, sampled_number, keys, tmp, tmp_entries);
+    } else {
+        k_select_keys<<<grid, 256, 0, st>>>(tb, type, step, (uint32_t)seed, (uint32_t)(seed >> 32), keys);
+        HGT_CHECK_LAUNCH();
+        k_select_pick<<<pick_grid, BIG, 0, st>>>(tb, type, sampled_number, keys, tmp);
+    }
     HGT_CHECK_LAUNCH();
     return HGT_OK;
-}
-
-extern "C" int hgt_sampler_induce_slots(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
-                                        int32_t n_triples, int64_t* n_slots_host) {
-    Tables tb;
-    if (!n_slots_host) return HGT_ERR_INVALID_ARG;
-    return make_tables(types_host, n_types, triples_host, n_triples, &tb, n_slots_host);
 }
 
 static int induce_check(const hgt_sampler_type* types_host, int32_t T, const hgt_sampler_triple* triples_host, int32_t M, int32_t R, Tables* tb,
@@ -928,84 +971,166 @@ static int make_masks(const hgt_sampler_mask* masks_host, int32_t M, bool masked
     return HGT_OK;
 }
 
-static int induce_count(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
-                        int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries, int32_t* type_off_out, int32_t* rel_ptr_out,
-                        int32_t* sizes_out, const hgt_sampler_mask* masks_host, bool masked, void* stream) {
+// batched: the hub queues of the induce passes are n_batch counters, then n_entries - 1 >= slots entries per replica
+template <bool BATCHED>
+static int count_step(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
+                        int32_t n_batch, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries, int32_t* type_off_out,
+                        int32_t* rel_ptr_out, int32_t* sizes_out, const hgt_sampler_mask* masks_host, bool masked, void* stream) {
     Tables tb;
     Masks mk;
     int64_t slots = 0;
     if (int rc = induce_check(types_host, n_types, triples_host, n_triples, n_relations, &tb, &slots)) return rc;
+    if constexpr (BATCHED)
+        if (int rc = batch_check(n_batch)) return rc;
     if (int rc = make_masks(masks_host, n_triples, masked, &mk)) return rc;
     if (!rowoff || !hub || !type_off_out || !rel_ptr_out || !sizes_out) return HGT_ERR_INVALID_ARG;
     if (n_entries < slots + 1) return HGT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hub, 0, 4, st) != hipSuccess) return HGT_ERR_LAUNCH;
-    if (slots > 0) {
-        k_induce<false><<<blocks_for(slots, 4), 256, 0, st>>>(tb, mk, (int)slots, rowoff, hub, nullptr, nullptr, nullptr, nullptr, 0);
-        HGT_CHECK_LAUNCH();
-        k_induce_hub<false><<<(unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), BIG, 0, st>>>(tb, mk, (int)slots, rowoff, hub, nullptr, nullptr,
-                                                                                              nullptr, nullptr, 0);
-        HGT_CHECK_LAUNCH();
+    if (hipMemsetAsync(hub, 0, 4 * (size_t)n_batch, st) != hipSuccess) return HGT_ERR_LAUNCH;
+    const dim3 grid(blocks_for(slots, 4), n_batch), hub_grid((unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), n_batch), scan_grid(1, n_batch);
+    if constexpr (BATCHED) {
+        const BatchIO io{rowoff, hub, n_entries, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+        if (slots > 0) {
+            k_induce_batched<false><<<grid, 256, 0, st>>>(tb, mk, (int)slots, io);
+            HGT_CHECK_LAUNCH();
+            k_induce_hub_batched<false><<<hub_grid, BIG, 0, st>>>(tb, mk, (int)slots, io);
+            HGT_CHECK_LAUNCH();
+        }
+        k_induce_scan_batched<<<scan_grid, BIG, 0, st>>>(tb, (int)slots, n_relations, rowoff, n_entries, type_off_out, rel_ptr_out, sizes_out);
+    } else {
+        if (slots > 0) {
+            k_induce<false><<<grid, 256, 0, st>>>(tb, mk, (int)slots, rowoff, hub, nullptr, nullptr, nullptr, nullptr, 0);
+            HGT_CHECK_LAUNCH();
+            k_induce_hub<false><<<hub_grid, BIG, 0, st>>>(tb, mk, (int)slots, rowoff, hub, nullptr, nullptr, nullptr, nullptr, 0);
+            HGT_CHECK_LAUNCH();
+        }
+        k_induce_scan<<<scan_grid, BIG, 0, st>>>(tb, (int)slots, n_relations, rowoff, type_off_out, rel_ptr_out, sizes_out);
     }
-    k_induce_scan<<<1, BIG, 0, st>>>(tb, (int)slots, n_relations, rowoff, type_off_out, rel_ptr_out, sizes_out);
     HGT_CHECK_LAUNCH();
     return HGT_OK;
+}
+
+// sizes and offs_out: the batched call's (the count pass's sizes, the prefix sums the fill pass writes first); NULL in the single one
+template <bool BATCHED>
+static int fill_step(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
+                       int32_t n_batch, int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries,
+                       const int32_t* type_off, const int32_t* sizes, int32_t* offs_out, int64_t n_nodes, int64_t n_edges, int32_t* src_out,
+                       int32_t* dst_out, int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out, const hgt_sampler_mask* masks_host,
+                       bool masked, void* stream) {
+    Tables tb;
+    Masks mk;
+    int64_t slots = 0;
+    if (int rc = induce_check(types_host, n_types, triples_host, n_triples, n_relations, &tb, &slots)) return rc;
+    if constexpr (BATCHED)
+        if (int rc = batch_check(n_batch)) return rc;
+    if (int rc = make_masks(masks_host, n_triples, masked, &mk)) return rc;
+    if (!rowoff || !hub || !type_off || (BATCHED && (!sizes || !offs_out)) || n_nodes < 0 || n_edges < n_nodes) return HGT_ERR_INVALID_ARG;
+    if (n_edges > 0x7fffffff) return HGT_ERR_TOO_LARGE;
+    if (n_entries < slots + 1) return HGT_ERR_WORKSPACE;
+    if (n_edges > 0 && (!src_out || !dst_out || !time_out)) return HGT_ERR_INVALID_ARG;
+    if (n_nodes > 0 && (!node_time_out || !node_id_out)) return HGT_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* ro = const_cast<int32_t*>(rowoff);              // the FILL instantiations only read the scratch
+    int32_t* hb = const_cast<int32_t*>(hub);
+    const int e_ns = (int)(n_edges - n_nodes);
+    const bool edges = slots > 0 && e_ns > 0;
+    const dim3 grid(blocks_for(slots, 4), n_batch), hub_grid((unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), n_batch);
+    if constexpr (BATCHED) {
+        k_batch_offsets<<<1, 64, 0, st>>>(sizes, n_batch, n_types, n_triples, offs_out);
+        HGT_CHECK_LAUNCH();
+        const BatchIO io{ro, hb, n_entries, type_off, offs_out, src_out, dst_out, time_out, (int)n_nodes, (int)n_edges};
+        if (edges) {
+            k_induce_batched<true><<<grid, 256, 0, st>>>(tb, mk, (int)slots, io);
+            HGT_CHECK_LAUNCH();
+            k_induce_hub_batched<true><<<hub_grid, BIG, 0, st>>>(tb, mk, (int)slots, io);
+            HGT_CHECK_LAUNCH();
+        }
+        if (n_nodes > 0) {
+            int64_t cap = 0;                                  // no replica has more nodes than the lists hold
+            for (int t = 0; t < n_types; ++t) cap += types_host[t].cap_sampled;
+            if (cap > n_nodes) cap = n_nodes;
+            k_induce_nodes_batched<<<dim3(blocks_for(cap > 0 ? cap : 1, 256), n_batch), 256, 0, st>>>(
+                tb, type_off, offs_out, (int)n_edges, (int)n_nodes, src_out, dst_out, time_out, node_time_out, node_id_out);
+            HGT_CHECK_LAUNCH();
+        }
+    } else {
+        if (edges) {
+            k_induce<true><<<grid, 256, 0, st>>>(tb, mk, (int)slots, ro, hb, type_off, src_out, dst_out, time_out, e_ns);
+            HGT_CHECK_LAUNCH();
+            k_induce_hub<true><<<hub_grid, BIG, 0, st>>>(tb, mk, (int)slots, ro, hb, type_off, src_out, dst_out, time_out, e_ns);
+            HGT_CHECK_LAUNCH();
+        }
+        if (n_nodes > 0) {
+            k_induce_nodes<<<blocks_for(n_nodes, 256), 256, 0, st>>>(tb, type_off, e_ns, (int)n_edges, (int)n_nodes, src_out, dst_out, time_out,
+                                                                     node_time_out, node_id_out);
+            HGT_CHECK_LAUNCH();
+        }
+    }
+    return HGT_OK;
+}
+
+template <bool BATCHED>
+static int reset_step(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, void* stream) {
+    Tables tb;
+    if (int rc = make_tables(types_host, n_types, nullptr, 0, &tb, nullptr)) return rc;
+    if constexpr (BATCHED)
+        if (int rc = batch_check(n_batch)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    (BATCHED ? k_reset_nodes_batched : k_reset_nodes)<<<dim3(256, n_batch), 256, 0, st>>>(tb);
+    HGT_CHECK_LAUNCH();
+    (BATCHED ? k_reset_counts_batched : k_reset_counts)<<<dim3(1, n_batch), 64, 0, st>>>(tb);
+    HGT_CHECK_LAUNCH();
+    return HGT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the exported step functions: forwarders
+// The single entry points stand before the batched ones: that is the order in which the k_induce* templates are first needed, and
+// so the order of the kernels in the code object.
+extern "C" int hgt_sampler_seed(const hgt_sampler_type* types_host, int32_t n_types, int32_t type, const int32_t* ids, const int32_t* times,
+                                int32_t n, int32_t step, void* stream) {
+    return seed_step<false>(types_host, n_types, 1, type, ids, times, n, step, stream);
+}
+
+extern "C" int hgt_sampler_add_budget(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                      int32_t n_triples, int32_t type, int32_t step, int32_t sampled_number, int32_t max_new,
+                                      int32_t has_max_time, int32_t max_time, uint64_t seed, int32_t* hub, int64_t hub_entries, void* stream) {
+    return budget_step<false>(types_host, n_types, triples_host, n_triples, 1, type, step, sampled_number, max_new, has_max_time, max_time, seed,
+                             nullptr, hub, hub_entries, stream);
+}
+
+extern "C" int hgt_sampler_select(const hgt_sampler_type* types_host, int32_t n_types, int32_t type, int32_t step, int32_t sampled_number,
+                                  uint64_t seed, uint64_t* keys, int32_t* tmp, int64_t tmp_entries, void* stream) {
+    return select_step<false>(types_host, n_types, 1, type, step, sampled_number, seed, nullptr, keys, tmp, tmp_entries, stream);
+}
+
+extern "C" int hgt_sampler_induce_slots(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
+                                        int32_t n_triples, int64_t* n_slots_host) {
+    Tables tb;
+    if (!n_slots_host) return HGT_ERR_INVALID_ARG;
+    return make_tables(types_host, n_types, triples_host, n_triples, &tb, n_slots_host);
 }
 
 extern "C" int hgt_sampler_induce_count(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
                                         int32_t n_triples, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries,
                                         int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out, void* stream) {
-    return induce_count(types_host, n_types, triples_host, n_triples, n_relations, rowoff, hub, n_entries, type_off_out, rel_ptr_out, sizes_out,
-                        nullptr, false, stream);
+    return count_step<false>(types_host, n_types, triples_host, n_triples, 1, n_relations, rowoff, hub, n_entries, type_off_out, rel_ptr_out,
+                               sizes_out, nullptr, false, stream);
 }
 
 extern "C" int hgt_sampler_induce_count_masked(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
                                                int32_t n_triples, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries,
                                                int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out,
                                                const hgt_sampler_mask* masks_host, void* stream) {
-    return induce_count(types_host, n_types, triples_host, n_triples, n_relations, rowoff, hub, n_entries, type_off_out, rel_ptr_out, sizes_out,
-                        masks_host, true, stream);
-}
-
-static int induce_fill(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
-                       int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries, const int32_t* type_off,
-                       int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out, int32_t* time_out, int32_t* node_time_out,
-                       int32_t* node_id_out, const hgt_sampler_mask* masks_host, bool masked, void* stream) {
-    Tables tb;
-    Masks mk;
-    int64_t slots = 0;
-    if (int rc = induce_check(types_host, n_types, triples_host, n_triples, n_relations, &tb, &slots)) return rc;
-    if (int rc = make_masks(masks_host, n_triples, masked, &mk)) return rc;
-    if (!rowoff || !hub || !type_off || n_nodes < 0 || n_edges < n_nodes) return HGT_ERR_INVALID_ARG;
-    if (n_edges > 0x7fffffff) return HGT_ERR_TOO_LARGE;
-    if (n_entries < slots + 1) return HGT_ERR_WORKSPACE;
-    if (n_edges > 0 && (!src_out || !dst_out || !time_out)) return HGT_ERR_INVALID_ARG;
-    if (n_nodes > 0 && (!node_time_out || !node_id_out)) return HGT_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const int e_ns = (int)(n_edges - n_nodes);
-    if (slots > 0 && e_ns > 0) {
-        int32_t* ro = const_cast<int32_t*>(rowoff);      // the FILL instantiations only read it
-        k_induce<true><<<blocks_for(slots, 4), 256, 0, st>>>(tb, mk, (int)slots, ro, const_cast<int32_t*>(hub), type_off, src_out, dst_out, time_out,
-                                                            e_ns);
-        HGT_CHECK_LAUNCH();
-        k_induce_hub<true><<<(unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), BIG, 0, st>>>(tb, mk, (int)slots, ro, const_cast<int32_t*>(hub), type_off, src_out,
-                                                                                             dst_out, time_out, e_ns);
-        HGT_CHECK_LAUNCH();
-    }
-    if (n_nodes > 0) {
-        k_induce_nodes<<<blocks_for(n_nodes, 256), 256, 0, st>>>(tb, type_off, e_ns, (int)n_edges, (int)n_nodes, src_out, dst_out, time_out,
-                                                                 node_time_out, node_id_out);
-        HGT_CHECK_LAUNCH();
-    }
-    return HGT_OK;
+    return count_step<false>(types_host, n_types, triples_host, n_triples, 1, n_relations, rowoff, hub, n_entries, type_off_out, rel_ptr_out,
+                               sizes_out, masks_host, true, stream);
 }
 
 extern "C" int hgt_sampler_induce_fill(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
                                        int32_t n_triples, int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries,
                                        const int32_t* type_off, int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out,
                                        int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out, void* stream) {
-    return induce_fill(types_host, n_types, triples_host, n_triples, n_relations, rowoff, hub, n_entries, type_off, n_nodes, n_edges, src_out,
-                       dst_out, time_out, node_time_out, node_id_out, nullptr, false, stream);
+    return fill_step<false>(types_host, n_types, triples_host, n_triples, 1, n_relations, rowoff, hub, n_entries, type_off, nullptr, nullptr,
+                              n_nodes, n_edges, src_out, dst_out, time_out, node_time_out, node_id_out, nullptr, false, stream);
 }
 
 extern "C" int hgt_sampler_induce_fill_masked(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
@@ -1013,142 +1138,39 @@ extern "C" int hgt_sampler_induce_fill_masked(const hgt_sampler_type* types_host
                                               int64_t n_entries, const int32_t* type_off, int64_t n_nodes, int64_t n_edges, int32_t* src_out,
                                               int32_t* dst_out, int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out,
                                               const hgt_sampler_mask* masks_host, void* stream) {
-    return induce_fill(types_host, n_types, triples_host, n_triples, n_relations, rowoff, hub, n_entries, type_off, n_nodes, n_edges, src_out,
-                       dst_out, time_out, node_time_out, node_id_out, masks_host, true, stream);
+    return fill_step<false>(types_host, n_types, triples_host, n_triples, 1, n_relations, rowoff, hub, n_entries, type_off, nullptr, nullptr,
+                              n_nodes, n_edges, src_out, dst_out, time_out, node_time_out, node_id_out, masks_host, true, stream);
 }
 
 extern "C" int hgt_sampler_reset(const hgt_sampler_type* types_host, int32_t n_types, void* stream) {
-    Tables tb;
-    if (int rc = make_tables(types_host, n_types, nullptr, 0, &tb, nullptr)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    k_reset_nodes<<<256, 256, 0, st>>>(tb);
-    HGT_CHECK_LAUNCH();
-    k_reset_counts<<<1, 64, 0, st>>>(tb);
-    HGT_CHECK_LAUNCH();
-    return HGT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ batched entry points
-// n_batch replicas in gridDim.y of the launches of one batch (include/hgt_hip.h, "Batched device sampler")
-static int batch_check(int32_t n_batch) {
-    if (n_batch < 1) return HGT_ERR_INVALID_ARG;
-    if (n_batch > HGT_SAMPLER_MAX_BATCH) return HGT_ERR_UNSUPPORTED;
-    return HGT_OK;
-}
-
-static int make_keys(const uint64_t* seeds_host, int32_t n_batch, Keys* out) {
-    if (!seeds_host) return HGT_ERR_INVALID_ARG;
-    for (int b = 0; b < HGT_SAMPLER_MAX_BATCH; ++b) {
-        const uint64_t seed = b < n_batch ? seeds_host[b] : 0;
-        out->k[b][0] = (uint32_t)seed;
-        out->k[b][1] = (uint32_t)(seed >> 32);
-    }
-    return HGT_OK;
+    return reset_step<false>(types_host, n_types, 1, stream);
 }
 
 extern "C" int hgt_sampler_seed_batched(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, int32_t type, const int32_t* ids,
                                         const int32_t* times, int32_t n, int32_t step, void* stream) {
-    Tables tb;
-    if (int rc = make_tables(types_host, n_types, nullptr, 0, &tb, nullptr)) return rc;
-    if (int rc = batch_check(n_batch)) return rc;
-    if (type < 0 || type >= n_types || n < 0 || step < 0) return HGT_ERR_INVALID_ARG;
-    if (n > types_host[type].cap_sampled) return HGT_ERR_WORKSPACE;
-    if (n > 0 && (!ids || !times)) return HGT_ERR_INVALID_ARG;
-    k_seed_batched<<<dim3(blocks_for(n > 0 ? n : 1, 256), n_batch), 256, 0, (hipStream_t)stream>>>(tb, type, ids, times, n, step);
-    HGT_CHECK_LAUNCH();
-    return HGT_OK;
+    return seed_step<true>(types_host, n_types, n_batch, type, ids, times, n, step, stream);
 }
 
 extern "C" int hgt_sampler_add_budget_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
                                               int32_t n_triples, int32_t n_batch, int32_t type, int32_t step, int32_t sampled_number,
                                               int32_t max_new, int32_t has_max_time, int32_t max_time, const uint64_t* seeds_host, int32_t* hub,
                                               int64_t hub_entries, void* stream) {
-    Tables tb;
-    Keys keys;
-    if (int rc = make_tables(types_host, n_types, triples_host, n_triples, &tb, nullptr)) return rc;
-    if (int rc = batch_check(n_batch)) return rc;
-    if (int rc = make_keys(seeds_host, n_batch, &keys)) return rc;
-    if (type < 0 || type >= n_types || step < 0 || sampled_number < 1 || max_new < 0) return HGT_ERR_INVALID_ARG;
-    if (sampled_number > HGT_SAMPLER_MAX_NUMBER) return HGT_ERR_UNSUPPORTED;
-    BudgetParams P;
-    P.t = type; P.step = step; P.sn = sampled_number; P.has_max = has_max_time != 0; P.max_time = max_time; P.max_new = max_new;
-    P.k0 = P.k1 = 0;                                          // the replicas' keys ride in `keys`
-    P.ntr = 0;
-    for (int m = 0; m < HGT_SAMPLER_MAX_TRIPLES; ++m) P.sel[m] = 0;
-    for (int m = 0; m < n_triples; ++m) {
-        if (triples_host[m].tgt_type != type) continue;
-        const hgt_sampler_triple& tr = triples_host[m];
-        if (types_host[tr.src_type].n_nodes > 0 && types_host[type].n_nodes > 0 && (!tr.src || !tr.time)) return HGT_ERR_INVALID_ARG;
-        P.sel[P.ntr++] = (uint8_t)m;
-    }
-    const int64_t rows = (int64_t)max_new * P.ntr;
-    if (rows == 0) return HGT_OK;
-    if (rows > 0x3fffffff) return HGT_ERR_TOO_LARGE;
-    if (!hub) return HGT_ERR_INVALID_ARG;
-    if (hub_entries < rows + 1) return HGT_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hub, 0, 4 * (size_t)n_batch, st) != hipSuccess) return HGT_ERR_LAUNCH;
-    k_budget_batched<<<dim3(blocks_for(rows, 4), n_batch), 256, 0, st>>>(tb, P, keys, hub, hub_entries - 1, (int)rows);
-    HGT_CHECK_LAUNCH();
-    k_budget_hub_batched<<<dim3((unsigned)(rows < HUB_BLOCKS ? rows : HUB_BLOCKS), n_batch), BIG, 0, st>>>(tb, P, keys, hub, hub_entries - 1, (int)rows);
-    HGT_CHECK_LAUNCH();
-    return HGT_OK;
+    return budget_step<true>(types_host, n_types, triples_host, n_triples, n_batch, type, step, sampled_number, max_new, has_max_time, max_time, 0,
+                            seeds_host, hub, hub_entries, stream);
 }
 
 extern "C" int hgt_sampler_select_batched(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, int32_t type, int32_t step,
                                           int32_t sampled_number, const uint64_t* seeds_host, uint64_t* keys, int32_t* tmp, int64_t tmp_entries,
                                           void* stream) {
-    Tables tb;
-    Keys seeds;
-    if (int rc = make_tables(types_host, n_types, nullptr, 0, &tb, nullptr)) return rc;
-    if (int rc = batch_check(n_batch)) return rc;
-    if (int rc = make_keys(seeds_host, n_batch, &seeds)) return rc;
-    if (type < 0 || type >= n_types || step < 0 || sampled_number < 1) return HGT_ERR_INVALID_ARG;
-    if (sampled_number > HGT_SAMPLER_MAX_NUMBER) return HGT_ERR_UNSUPPORTED;
-    const int cap = types_host[type].cap_cand;
-    if (cap == 0) return HGT_OK;
-    if (!keys || !tmp) return HGT_ERR_INVALID_ARG;
-    if (tmp_entries < cap) return HGT_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    k_select_keys_batched<<<dim3(blocks_for(cap, 256), n_batch), 256, 0, st>>>(tb, type, step, seeds, keys, tmp_entries);
-    HGT_CHECK_LAUNCH();
-    k_select_pick_batched<<<dim3(1, n_batch), BIG, 0, st>>>(tb, type, sampled_number, keys, tmp, tmp_entries);
-    HGT_CHECK_LAUNCH();
-    return HGT_OK;
-}
-
-// the hub queues of the induce passes: n_batch counters, then n_entries - 1 >= slots entries per replica
-static int induce_count_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
-                                int32_t n_batch, int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries, int32_t* type_off_out,
-                                int32_t* rel_ptr_out, int32_t* sizes_out, const hgt_sampler_mask* masks_host, bool masked, void* stream) {
-    Tables tb;
-    Masks mk;
-    int64_t slots = 0;
-    if (int rc = induce_check(types_host, n_types, triples_host, n_triples, n_relations, &tb, &slots)) return rc;
-    if (int rc = batch_check(n_batch)) return rc;
-    if (int rc = make_masks(masks_host, n_triples, masked, &mk)) return rc;
-    if (!rowoff || !hub || !type_off_out || !rel_ptr_out || !sizes_out) return HGT_ERR_INVALID_ARG;
-    if (n_entries < slots + 1) return HGT_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hub, 0, 4 * (size_t)n_batch, st) != hipSuccess) return HGT_ERR_LAUNCH;
-    const BatchIO io{rowoff, hub, n_entries, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    if (slots > 0) {
-        k_induce_batched<false><<<dim3(blocks_for(slots, 4), n_batch), 256, 0, st>>>(tb, mk, (int)slots, io);
-        HGT_CHECK_LAUNCH();
-        k_induce_hub_batched<false><<<dim3((unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), n_batch), BIG, 0, st>>>(tb, mk, (int)slots, io);
-        HGT_CHECK_LAUNCH();
-    }
-    k_induce_scan_batched<<<dim3(1, n_batch), BIG, 0, st>>>(tb, (int)slots, n_relations, rowoff, n_entries, type_off_out, rel_ptr_out, sizes_out);
-    HGT_CHECK_LAUNCH();
-    return HGT_OK;
+    return select_step<true>(types_host, n_types, n_batch, type, step, sampled_number, 0, seeds_host, keys, tmp, tmp_entries, stream);
 }
 
 extern "C" int hgt_sampler_induce_count_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
                                                 int32_t n_triples, int32_t n_batch, int32_t n_relations, int32_t* rowoff, int32_t* hub,
                                                 int64_t n_entries, int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out,
                                                 void* stream) {
-    return induce_count_batched(types_host, n_types, triples_host, n_triples, n_batch, n_relations, rowoff, hub, n_entries, type_off_out,
-                                rel_ptr_out, sizes_out, nullptr, false, stream);
+    return count_step<true>(types_host, n_types, triples_host, n_triples, n_batch, n_relations, rowoff, hub, n_entries, type_off_out,
+                              rel_ptr_out, sizes_out, nullptr, false, stream);
 }
 
 extern "C" int hgt_sampler_induce_count_masked_batched(const hgt_sampler_type* types_host, int32_t n_types,
@@ -1156,46 +1178,8 @@ extern "C" int hgt_sampler_induce_count_masked_batched(const hgt_sampler_type* t
                                                        int32_t n_relations, int32_t* rowoff, int32_t* hub, int64_t n_entries,
                                                        int32_t* type_off_out, int32_t* rel_ptr_out, int32_t* sizes_out,
                                                        const hgt_sampler_mask* masks_host, void* stream) {
-    return induce_count_batched(types_host, n_types, triples_host, n_triples, n_batch, n_relations, rowoff, hub, n_entries, type_off_out,
-                                rel_ptr_out, sizes_out, masks_host, true, stream);
-}
-
-static int induce_fill_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host, int32_t n_triples,
-                               int32_t n_batch, int32_t n_relations, const int32_t* rowoff, const int32_t* hub, int64_t n_entries,
-                               const int32_t* type_off, const int32_t* sizes, int32_t* offs_out, int64_t n_nodes, int64_t n_edges,
-                               int32_t* src_out, int32_t* dst_out, int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out,
-                               const hgt_sampler_mask* masks_host, bool masked, void* stream) {
-    Tables tb;
-    Masks mk;
-    int64_t slots = 0;
-    if (int rc = induce_check(types_host, n_types, triples_host, n_triples, n_relations, &tb, &slots)) return rc;
-    if (int rc = batch_check(n_batch)) return rc;
-    if (int rc = make_masks(masks_host, n_triples, masked, &mk)) return rc;
-    if (!rowoff || !hub || !type_off || !sizes || !offs_out || n_nodes < 0 || n_edges < n_nodes) return HGT_ERR_INVALID_ARG;
-    if (n_edges > 0x7fffffff) return HGT_ERR_TOO_LARGE;
-    if (n_entries < slots + 1) return HGT_ERR_WORKSPACE;
-    if (n_edges > 0 && (!src_out || !dst_out || !time_out)) return HGT_ERR_INVALID_ARG;
-    if (n_nodes > 0 && (!node_time_out || !node_id_out)) return HGT_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    k_batch_offsets<<<1, 64, 0, st>>>(sizes, n_batch, n_types, n_triples, offs_out);
-    HGT_CHECK_LAUNCH();
-    const BatchIO io{const_cast<int32_t*>(rowoff), const_cast<int32_t*>(hub), n_entries, type_off, offs_out, src_out, dst_out, time_out,
-                     (int)n_nodes, (int)n_edges};      // the FILL instantiations only read the scratch
-    if (slots > 0 && n_edges > n_nodes) {
-        k_induce_batched<true><<<dim3(blocks_for(slots, 4), n_batch), 256, 0, st>>>(tb, mk, (int)slots, io);
-        HGT_CHECK_LAUNCH();
-        k_induce_hub_batched<true><<<dim3((unsigned)(slots < HUB_BLOCKS ? slots : HUB_BLOCKS), n_batch), BIG, 0, st>>>(tb, mk, (int)slots, io);
-        HGT_CHECK_LAUNCH();
-    }
-    if (n_nodes > 0) {
-        int64_t cap = 0;                                      // no replica has more nodes than the lists hold
-        for (int t = 0; t < n_types; ++t) cap += types_host[t].cap_sampled;
-        if (cap > n_nodes) cap = n_nodes;
-        k_induce_nodes_batched<<<dim3(blocks_for(cap > 0 ? cap : 1, 256), n_batch), 256, 0, st>>>(tb, type_off, offs_out, (int)n_edges, (int)n_nodes,
-                                                                                             src_out, dst_out, time_out, node_time_out, node_id_out);
-        HGT_CHECK_LAUNCH();
-    }
-    return HGT_OK;
+    return count_step<true>(types_host, n_types, triples_host, n_triples, n_batch, n_relations, rowoff, hub, n_entries, type_off_out,
+                              rel_ptr_out, sizes_out, masks_host, true, stream);
 }
 
 extern "C" int hgt_sampler_induce_fill_batched(const hgt_sampler_type* types_host, int32_t n_types, const hgt_sampler_triple* triples_host,
@@ -1203,8 +1187,8 @@ extern "C" int hgt_sampler_induce_fill_batched(const hgt_sampler_type* types_hos
                                                const int32_t* hub, int64_t n_entries, const int32_t* type_off, const int32_t* sizes,
                                                int32_t* offs_out, int64_t n_nodes, int64_t n_edges, int32_t* src_out, int32_t* dst_out,
                                                int32_t* time_out, int32_t* node_time_out, int32_t* node_id_out, void* stream) {
-    return induce_fill_batched(types_host, n_types, triples_host, n_triples, n_batch, n_relations, rowoff, hub, n_entries, type_off, sizes,
-                               offs_out, n_nodes, n_edges, src_out, dst_out, time_out, node_time_out, node_id_out, nullptr, false, stream);
+    return fill_step<true>(types_host, n_types, triples_host, n_triples, n_batch, n_relations, rowoff, hub, n_entries, type_off, sizes,
+                             offs_out, n_nodes, n_edges, src_out, dst_out, time_out, node_time_out, node_id_out, nullptr, false, stream);
 }
 
 extern "C" int hgt_sampler_induce_fill_masked_batched(const hgt_sampler_type* types_host, int32_t n_types,
@@ -1214,20 +1198,12 @@ extern "C" int hgt_sampler_induce_fill_masked_batched(const hgt_sampler_type* ty
                                                       int64_t n_edges, int32_t* src_out, int32_t* dst_out, int32_t* time_out,
                                                       int32_t* node_time_out, int32_t* node_id_out, const hgt_sampler_mask* masks_host,
                                                       void* stream) {
-    return induce_fill_batched(types_host, n_types, triples_host, n_triples, n_batch, n_relations, rowoff, hub, n_entries, type_off, sizes,
-                               offs_out, n_nodes, n_edges, src_out, dst_out, time_out, node_time_out, node_id_out, masks_host, true, stream);
+    return fill_step<true>(types_host, n_types, triples_host, n_triples, n_batch, n_relations, rowoff, hub, n_entries, type_off, sizes,
+                             offs_out, n_nodes, n_edges, src_out, dst_out, time_out, node_time_out, node_id_out, masks_host, true, stream);
 }
 
 extern "C" int hgt_sampler_reset_batched(const hgt_sampler_type* types_host, int32_t n_types, int32_t n_batch, void* stream) {
-    Tables tb;
-    if (int rc = make_tables(types_host, n_types, nullptr, 0, &tb, nullptr)) return rc;
-    if (int rc = batch_check(n_batch)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    k_reset_nodes_batched<<<dim3(256, n_batch), 256, 0, st>>>(tb);
-    HGT_CHECK_LAUNCH();
-    k_reset_counts_batched<<<dim3(1, n_batch), 64, 0, st>>>(tb);
-    HGT_CHECK_LAUNCH();
-    return HGT_OK;
+    return reset_step<true>(types_host, n_types, n_batch, stream);
 }
 
 extern "C" int hgt_sampler_gather_features(const float* const* features_host, const int32_t* type_nodes_host, int32_t n_types, int32_t n_batch,

@@ -585,40 +585,204 @@ def _masks_c(table, M):
     return masks_c
 
 
-class DeviceSamplerState:
-    """The device state of one (seed counts, depth, sampled_number) shape of call and the step-level calls on it (one method per C
-    entry point).  `sample_subgraph_device` strings them together; the tests call them one by one."""
+def _need_gpu(dgraph, call):
+    if dgraph.device is None or dgraph.device.type != "cuda":
+        raise RuntimeError("pyhgt_amd: %s_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host sibling is %s_host)"
+                           % (call, call))
 
-    def __init__(self, dgraph, n_seed, depth, sn):
-        if dgraph.device is None or dgraph.device.type != "cuda":
-            raise RuntimeError("pyhgt_amd: sample_subgraph_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host "
-                               "sibling is sample_subgraph_host)")
+
+class _SamplerState:
+    """The device state of one (seed counts, depth, sampled_number) shape of call and the step-level calls on it (one method per C
+    entry point), written once for the single call and for n_batch replicas drawn at once.  `lead` is the leading shape of every
+    array: () for `DeviceSamplerState`, (n_batch,) for `BatchedDeviceSamplerState`, where replica b of every launch is blockIdx.y = b,
+    replica b's arrays are base + b * stride and the strides are the fields of the one table the kernels get (n_nodes, cap_sampled,
+    cap_cand).  The two specialisations name the entry points (`_suffix`), the public call that error messages speak of (`_public`)
+    and the attributes of the graph that hold their per-node arrays, their cache and (`dirty`) their flag.  `draw` strings the steps
+    together for the public calls; the tests call them one by one."""
+
+    def __init__(self, dgraph, n_seed, depth, sn, lead):
+        _need_gpu(dgraph, self._public)
+        if lead and not 1 <= lead[0] <= _lib.HGT_SAMPLER_MAX_BATCH:
+            raise ValueError("pyhgt_amd: 1 <= n_batch <= %d" % _lib.HGT_SAMPLER_MAX_BATCH)
         self.g, self.dev, self.sn, self.depth = dgraph, dgraph.device, int(sn), int(depth)
+        self.lead = lead = tuple(int(b) for b in lead)
+        self.B = B = lead[0] if lead else 1
         self.lib = _lib.load()
         T, M, dev = len(dgraph.types), len(dgraph.triples), self.dev
         self.T, self.M, self.R = T, M, len(dgraph.edge_dict)
         self.cap_s, self.cap_c = _capacities(dgraph, n_seed, depth, sn)
-        if dgraph._dev_nodes is None:                        # the per-node arrays are shared by every shape of call
-            dgraph._dev_nodes = ([torch.zeros(n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
-                                 [torch.zeros(n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
-                                 [torch.full((n,), -1, dtype=torch.int32, device=dev) for n in dgraph.n_nodes])
-        self.score, self.stamp, self.serial = dgraph._dev_nodes
+        # The per-node arrays (score / stamp / serial over every node of every type, 20 bytes x nodes x B) live on the graph, shared by
+        # every shape of call; the batched set is apart from the single call's and sized for the largest n_batch seen.  New arrays are
+        # clean, and the cached states point into the arrays that go.
+        nodes = getattr(dgraph, self._nodes)
+        if nodes is None or (lead and nodes[0][0].size(0) < B):
+            getattr(dgraph, self._cache).clear()
+            nodes = ([torch.zeros(*lead, n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
+                     [torch.zeros(*lead, n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
+                     [torch.full((*lead, n), -1, dtype=torch.int32, device=dev) for n in dgraph.n_nodes])
+            setattr(dgraph, self._nodes, nodes)
+            self.dirty = False
+        self.score, self.stamp, self.serial = nodes
         i32 = dict(dtype=torch.int32, device=dev)
-        self.sampled = [torch.zeros(c, **i32) for c in self.cap_s]
-        self.cand = [torch.zeros(c, **i32) for c in self.cap_c]
-        self.counts = torch.zeros(T, 4, **i32)
+        self.sampled = [torch.zeros(*lead, c, **i32) for c in self.cap_s]
+        self.cand = [torch.zeros(*lead, c, **i32) for c in self.cap_c]
+        self.counts = torch.zeros(*lead, T, 4, **i32)
         ptr = _lib.ptr
-        self.types_c = (_lib.HgtSamplerType * T)()
+        self.types_c = (_lib.HgtSamplerType * T)()           # the table of replica 0; the batched kernels shift it by b strides
         for t in range(T):
             self.types_c[t] = _lib.HgtSamplerType(ptr(self.score[t]), ptr(self.stamp[t]), ptr(self.serial[t]), ptr(self.sampled[t]),
-                                                  ptr(self.cand[t]), self.counts[t].data_ptr(), dgraph.n_nodes[t], self.cap_s[t], self.cap_c[t], 0)
+                                                  ptr(self.cand[t]), self.counts.data_ptr() + 16 * t, dgraph.n_nodes[t], self.cap_s[t],
+                                                  self.cap_c[t], 0)
         self.triples_c = _triple_table(dgraph)
-        self.n_entries = _scratch_entries(self.lib, dgraph, self.types_c, self.triples_c, n_seed, sn)
-        self.rowoff, self.hub = torch.zeros(self.n_entries, **i32), torch.zeros(self.n_entries, **i32)
-        self.keys = torch.zeros(max(self.cap_c + [1]), dtype=torch.int64, device=dev)
-        self.tmp = torch.zeros(max(self.cap_c + [1]), **i32)
-        self.type_off, self.rel_ptr = torch.zeros(T + 1, **i32), torch.zeros(self.R + 1, **i32)
-        self.sizes = torch.zeros(T + M + 2, **i32)
+        self.n_entries = _scratch_entries(self.lib, dgraph, self.types_c, self.triples_c, n_seed, sn)      # per replica
+        self.rowoff, self.hub = torch.zeros(*lead, self.n_entries, **i32), torch.zeros(B * self.n_entries, **i32)
+        self.n_tmp = max(self.cap_c + [1])
+        self.keys = torch.zeros(*lead, self.n_tmp, dtype=torch.int64, device=dev)
+        self.tmp = torch.zeros(*lead, self.n_tmp, **i32)
+        self.type_off, self.rel_ptr = torch.zeros(*lead, T + 1, **i32), torch.zeros(*lead, self.R + 1, **i32)
+        self.sizes = torch.zeros(*lead, T + M + 2, **i32)
+        self.fill_extra = ()                                 # batched: sizes and the offsets the fill pass writes, [2 * (B + 1)]
+        if lead:
+            self.offs = torch.zeros(2 * (B + 1), **i32)
+            self.fill_extra = (self.sizes.data_ptr(), self.offs.data_ptr())
+
+    # The entry points are bound when the library is set, not looked up by name on every call.  The tests put a counting library
+    # into `lib` after construction; setting it binds again.
+    @property
+    def lib(self):
+        return self._library
+
+    @lib.setter
+    def lib(self, lib):
+        self._library = lib
+        entry = lambda step: getattr(lib, "hgt_sampler_" + step + self._suffix)
+        self.c_seed, self.c_add_budget, self.c_select, self.c_reset = entry("seed"), entry("add_budget"), entry("select"), entry("reset")
+        self.c_induce = {False: (entry("induce_count"), entry("induce_fill"), "hgt_sampler_induce" + self._suffix),
+                         True: (entry("induce_count_masked"), entry("induce_fill_masked"), "hgt_sampler_induce_masked" + self._suffix)}
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _seeds_c(self, seeds):
+        """the Philox seeds of a batched call as the HOST array the entry points take"""
+        if len(seeds) != self.B:
+            raise ValueError("pyhgt_amd: %d Philox seeds for %d replicas" % (len(seeds), self.B))
+        return (C.c_uint64 * self.B)(*[int(s) & (2 ** 64 - 1) for s in seeds])
+
+    def seed_nodes(self, t, ids, times, step):
+        """ids, times: [n], batched [n_batch, n]"""
+        ids, times = (np.ascontiguousarray(a, dtype=np.int32) for a in (ids, times))
+        if self.lead and (ids.ndim != 2 or ids.shape[0] != self.B or times.shape != ids.shape):
+            raise ValueError("pyhgt_amd: seed ids and times must be [%d, n]" % self.B)
+        n = ids.shape[-1]
+        ids, times = (torch.from_numpy(a).to(self.dev) for a in (ids, times))
+        self.dirty = True
+        _lib.check(self.c_seed(self.types_c, self.T, *self.lead, t, ids.data_ptr() if n else None, times.data_ptr() if n else None, n, step,
+                               self._stream()), "hgt_sampler_seed" + self._suffix)
+        ids.record_stream(torch.cuda.current_stream(self.dev))
+        times.record_stream(torch.cuda.current_stream(self.dev))
+
+    def add_budget(self, t, step, max_new, max_time, seed):
+        """seed: the Philox seed, batched the n_batch seeds"""
+        self.dirty = True
+        key = self._seeds_c(seed) if self.lead else seed & (2 ** 64 - 1)
+        _lib.check(self.c_add_budget(self.types_c, self.T, self.triples_c, self.M, *self.lead, t, step, self.sn, max_new,
+                                     0 if max_time is None else 1, 0 if max_time is None else int(max_time), key, self.hub.data_ptr(),
+                                     self.n_entries, self._stream()), "hgt_sampler_add_budget" + self._suffix)
+
+    def select(self, t, step, seed):
+        self.dirty = True
+        key = self._seeds_c(seed) if self.lead else seed & (2 ** 64 - 1)
+        _lib.check(self.c_select(self.types_c, self.T, *self.lead, t, step, self.sn, key, self.keys.data_ptr(), self.tmp.data_ptr(),
+                                 self.n_tmp, self._stream()), "hgt_sampler_select" + self._suffix)
+
+    def induce(self, mask=None):
+        """count pass, the one host read of the call (sizes [T + M + 2] per replica), fill pass -> (src, dst, edge_time, rel_ptr,
+        type_off, node_time, node_id, nodes per type).  Batched: the buffers hold the replicas one after the other with indices local
+        to each piece, rel_ptr is [B, R + 1], type_off [B, T + 1], nodes per type [B][T], and the node offsets [B + 1] and the edge
+        offsets [B + 1] follow.  mask (dict or the table of _mask_table): the masked entry points, the same launches with the
+        thresholds as one more argument; None or {}: the unmasked ones."""
+        T, M = self.T, self.M
+        table = _mask_table(self.g, mask)
+        count, fill, what = self.c_induce[table is not None]
+        tail = () if table is None else (_masks_c(table, M),)
+        head = (self.types_c, T, self.triples_c, M, *self.lead, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
+                self.type_off.data_ptr())
+        _lib.check(count(*head, self.rel_ptr.data_ptr(), self.sizes.data_ptr(), *tail, self._stream()), what + " (count)")
+        sizes = self.sizes.cpu().numpy().reshape(self.B, T + M + 2)      # the host synchronisation of the call
+        if sizes[:, T + M].any():
+            raise RuntimeError("pyhgt_amd: a sampler list overflowed its static capacity or a seed id was out of range")
+        n_per_type = [[int(v) for v in row[:T]] for row in sizes]
+        nodes = [sum(row) for row in n_per_type]
+        edges = [n + int(row[T + M + 1]) for n, row in zip(nodes, sizes)]
+        N, E = sum(nodes), sum(edges)
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        src, dst, etime = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
+        node_time, node_id = torch.empty(N, **i32), torch.empty(N, **i32)
+        ptr = _lib.ptr
+        _lib.check(fill(*head, *self.fill_extra, N, E, ptr(src), ptr(dst), ptr(etime), ptr(node_time), ptr(node_id), *tail, self._stream()),
+                   what + " (fill)")
+        out = (src, dst, etime, self.rel_ptr.clone(), self.type_off.clone(), node_time, node_id)
+        if not self.lead:
+            return out + (n_per_type[0],)
+        prefix = lambda v: np.concatenate([[0], np.cumsum(v, dtype=np.int64)])
+        return out + (n_per_type, prefix(nodes), prefix(edges))
+
+    def reset(self):
+        _lib.check(self.c_reset(self.types_c, self.T, *self.lead, self._stream()), "hgt_sampler_reset" + self._suffix)
+        self.dirty = False
+
+    def clear(self):
+        """full clear of the per-node arrays (all the graph holds of this set, not only this state's replicas): after a call that
+        failed half way.  The counters of every cached state go with them: the state that failed is not the one that finds the graph
+        dirty when the next call has another shape."""
+        for a in self.score + self.stamp:
+            a.zero_()
+        for a in self.serial:
+            a.fill_(-1)
+        for st in [self] + list(getattr(self.g, self._cache).values()):
+            st.counts.zero_()
+        self.dirty = False
+
+    def draw(self, seeds, max_time, seed, table):
+        """one whole draw up to the induced graph: seeds = per type (ids, times) in the form of seed_nodes -> what induce returns"""
+        T = self.T
+        if self.dirty:
+            self.clear()
+        for t, (ids, tms) in enumerate(seeds):
+            if ids.shape[-1]:
+                self.seed_nodes(t, ids, tms, t)
+        for t, (ids, _) in enumerate(seeds):
+            if ids.shape[-1]:
+                self.add_budget(t, t, ids.shape[-1], max_time, seed)
+        for layer in range(self.depth):
+            for t in range(T):
+                if self.cap_c[t] == 0:                       # nothing can ever be a candidate of this type
+                    continue
+                step = T * (1 + layer) + t
+                self.select(t, step, seed)
+                self.add_budget(t, step, self.sn, max_time, seed)
+        return self.induce(table)
+
+    def snapshot(self):
+        """host copies of the state (tests): score / stamp as uint64, serial, the two lists cut to their counts, as one dict; batched:
+        a list of such dicts, one per replica"""
+        rows = (lambda a: a) if self.lead else (lambda a: a[None])
+        counts = rows(self.counts.cpu().numpy())
+        score, stamp = ([rows(a.cpu().numpy().view(np.uint64)) for a in v] for v in (self.score, self.stamp))
+        serial, sampled, cand = ([rows(a.cpu().numpy()) for a in v] for v in (self.serial, self.sampled, self.cand))
+        out = [dict(score=[a[b] for a in score], stamp=[a[b] for a in stamp], serial=[a[b] for a in serial],
+                    sampled=[a[b, :counts[b, t, 0]].astype(np.int64) for t, a in enumerate(sampled)],
+                    cand=[a[b, :counts[b, t, 2]].astype(np.int64) for t, a in enumerate(cand)], counts=counts[b]) for b in range(self.B)]
+        return out if self.lead else out[0]
+
+
+class DeviceSamplerState(_SamplerState):
+    """the state of `sample_subgraph_device`: one draw, 1-D arrays per type, counts [T, 4]"""
+    _suffix, _public, _nodes, _cache = "", "sample_subgraph", "_dev_nodes", "_dev_state"
+
+    def __init__(self, dgraph, n_seed, depth, sn):
+        super().__init__(dgraph, n_seed, depth, sn, ())
 
     # Clean or dirty is a fact about the per-node arrays, which every shape of call shares: it lives on the graph.  A state that
     # starts on a graph another state left dirty (a call that raised half way, a state evicted from the cache) sees it.
@@ -630,88 +794,76 @@ class DeviceSamplerState:
     def dirty(self, value):
         self.g._dev_dirty = bool(value)
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.dev).cuda_stream
 
-    def seed_nodes(self, t, ids, times, step):
-        ids, times = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.dev) for a in (ids, times))
-        self.dirty = True
-        _lib.check(self.lib.hgt_sampler_seed(self.types_c, self.T, t, ids.data_ptr() if ids.numel() else None,
-                                             times.data_ptr() if ids.numel() else None, ids.numel(), step, self._stream()), "hgt_sampler_seed")
-        ids.record_stream(torch.cuda.current_stream(self.dev))
-        times.record_stream(torch.cuda.current_stream(self.dev))
+class BatchedDeviceSamplerState(_SamplerState):
+    """the state of `sample_subgraphs_device`: n_batch replicas, every array one [n_batch, .] tensor, counts [n_batch, T, 4].  The
+    lists, keys and induction scratch (a few hundred KB per replica at the training shapes) belong to the state."""
+    _suffix, _public, _nodes, _cache = "_batched", "sample_subgraphs", "_batch_nodes", "_batch_state"
 
-    def add_budget(self, t, step, max_new, max_time, seed):
-        self.dirty = True
-        _lib.check(self.lib.hgt_sampler_add_budget(self.types_c, self.T, self.triples_c, self.M, t, step, self.sn, max_new,
-                                                   0 if max_time is None else 1, 0 if max_time is None else int(max_time),
-                                                   seed & (2 ** 64 - 1), self.hub.data_ptr(), self.n_entries, self._stream()),
-                   "hgt_sampler_add_budget")
+    def __init__(self, dgraph, n_seed, depth, sn, n_batch):
+        super().__init__(dgraph, n_seed, depth, sn, (n_batch,))
 
-    def select(self, t, step, seed):
-        self.dirty = True
-        _lib.check(self.lib.hgt_sampler_select(self.types_c, self.T, t, step, self.sn, seed & (2 ** 64 - 1), self.keys.data_ptr(),
-                                               self.tmp.data_ptr(), self.tmp.numel(), self._stream()), "hgt_sampler_select")
+    # the state rule of the single call with a flag of its own: the batched per-node arrays are another set of arrays
+    @property
+    def dirty(self):
+        return self.g._batch_dirty
 
-    def induce(self, mask=None):
-        """count pass, the one host read, fill pass -> (src, dst, edge_time, rel_ptr, type_off, node_time, node_id, nodes per type).
-        mask (dict or the table of _mask_table): the masked entry points, the same launches with the thresholds as one more argument;
-        None or {}: the unmasked ones."""
-        lib, T, M = self.lib, self.T, self.M
-        table = _mask_table(self.g, mask)
-        if table is None:
-            count, fill, tail, what = lib.hgt_sampler_induce_count, lib.hgt_sampler_induce_fill, (), "hgt_sampler_induce"
-        else:
-            count, fill, tail = lib.hgt_sampler_induce_count_masked, lib.hgt_sampler_induce_fill_masked, (_masks_c(table, M),)
-            what = "hgt_sampler_induce_masked"
-        _lib.check(count(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
-                         self.type_off.data_ptr(), self.rel_ptr.data_ptr(), self.sizes.data_ptr(), *tail, self._stream()), what + " (count)")
-        sizes = self.sizes.cpu().numpy()                     # the host synchronisation of the batch
-        if sizes[T + M]:
-            raise RuntimeError("pyhgt_amd: a sampler list overflowed its static capacity or a seed id was out of range")
-        n_per_type = [int(v) for v in sizes[:T]]
-        N, E = sum(n_per_type), int(sizes[T + M + 1]) + sum(n_per_type)
-        i32 = dict(dtype=torch.int32, device=self.dev)
-        src, dst, etime = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
-        node_time, node_id = torch.empty(N, **i32), torch.empty(N, **i32)
-        ptr = _lib.ptr
-        _lib.check(fill(self.types_c, T, self.triples_c, M, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
-                        self.type_off.data_ptr(), N, E, ptr(src), ptr(dst), ptr(etime), ptr(node_time), ptr(node_id), *tail, self._stream()),
-                   what + " (fill)")
-        return src, dst, etime, self.rel_ptr.clone(), self.type_off.clone(), node_time, node_id, n_per_type
+    @dirty.setter
+    def dirty(self, value):
+        self.g._batch_dirty = bool(value)
 
-    def reset(self):
-        _lib.check(self.lib.hgt_sampler_reset(self.types_c, self.T, self._stream()), "hgt_sampler_reset")
-        self.dirty = False
+    def gather_features(self, type_off, node_id, n_per_type, width):
+        """the feature rows of every replica's nodes in one launch: float32 [nodes of the call, width].  self.offs still holds the
+        node offsets the fill pass wrote.  A type with rows and no matrix is an error of the caller, found here before the launch."""
+        N = int(node_id.numel())
+        feats = self.g.features
+        for t in range(self.T):
+            if width and feats[t] is None and any(row[t] for row in n_per_type):
+                raise ValueError("pyhgt_amd: no feature matrix for node type %r" % self.g.types[t])
+        out = torch.empty(N, width, dtype=torch.float32, device=self.dev)
+        mats = (C.c_void_p * self.T)(*[None if f is None or f.numel() == 0 else f.data_ptr() for f in feats])
+        rows = (C.c_int32 * self.T)(*[0 if f is None else int(f.size(0)) for f in feats])
+        _lib.check(self.lib.hgt_sampler_gather_features(mats, rows, self.T, self.B, width, type_off.data_ptr(), self.offs.data_ptr(),
+                                                        node_id.data_ptr() if N else None, N, out.data_ptr() if out.numel() else None,
+                                                        self._stream()), "hgt_sampler_gather_features")
+        return out
 
-    def clear(self):
-        """full clear of the per-node arrays: after a call that failed half way.  The counters of every cached state go with them: the
-        state that failed is not the one that finds the graph dirty when the next call has another shape."""
-        for a in self.score + self.stamp:
-            a.zero_()
-        for a in self.serial:
-            a.fill_(-1)
-        for st in [self] + list(self.g._dev_state.values()):
-            st.counts.zero_()
-        self.dirty = False
 
-    def snapshot(self):
-        """host copies of the state (tests): score / stamp as uint64, serial, the two lists cut to their counts"""
-        counts = self.counts.cpu().numpy()
-        u64 = lambda a: a.cpu().numpy().view(np.uint64)
-        return dict(score=[u64(a) for a in self.score], stamp=[u64(a) for a in self.stamp], serial=[a.cpu().numpy() for a in self.serial],
-                    sampled=[a.cpu().numpy()[:counts[t, 0]].astype(np.int64) for t, a in enumerate(self.sampled)],
-                    cand=[a.cpu().numpy()[:counts[t, 2]].astype(np.int64) for t, a in enumerate(self.cand)], counts=counts)
+def _cached_state(cls, dgraph, n_seed, depth, sn, *n_batch):
+    """the state of this shape of call from the graph's cache of `cls` states"""
+    cache = getattr(dgraph, cls._cache)
+    key = (tuple(n_seed), int(depth), int(sn)) + tuple(int(b) for b in n_batch)
+    st = cache.get(key)
+    if st is None:
+        if len(cache) >= 4:                                  # a loop uses one or two shapes of call; do not hoard lists
+            cache.clear()
+        st = cls(dgraph, n_seed, depth, sn, *n_batch)
+        cache[key] = st                                      # after the constructor: a larger n_batch empties the cache in there
+    return st
 
 
 def _device_state(dgraph, n_seed, depth, sn):
-    key = (tuple(n_seed), int(depth), int(sn))
-    st = dgraph._dev_state.get(key)
-    if st is None:
-        if len(dgraph._dev_state) >= 4:                      # a loop uses one or two shapes of call; do not hoard lists
-            dgraph._dev_state.clear()
-        st = dgraph._dev_state[key] = DeviceSamplerState(dgraph, n_seed, depth, sn)
-    return st
+    return _cached_state(DeviceSamplerState, dgraph, n_seed, depth, sn)
+
+
+def _batched_state(dgraph, n_seed, depth, sn, n_batch):
+    return _cached_state(BatchedDeviceSamplerState, dgraph, n_seed, depth, sn, n_batch)
+
+
+def _feature_width(dgraph):
+    widths = sorted({f.size(1) for f in dgraph.features if f is not None and f.size(0) > 0})
+    if len(widths) > 1:
+        raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (widths,))
+    return widths[0] if widths else 0
+
+
+def _call_table(dgraph, call, mask):
+    """the front of both public calls behind their seeds: the mask table, then what the graph must have"""
+    table = _mask_table(dgraph, mask)
+    _need_gpu(dgraph, call)
+    if dgraph.features is None:
+        raise ValueError("pyhgt_amd: the DeviceHeteroGraph carries no features")
+    return table
 
 
 def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp, seed, plan=True, mask=None):
@@ -725,38 +877,14 @@ def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp,
     and `.seed_rows(type)` name the seeds' rows in the result."""
     _check_args(dgraph, sampled_depth, sampled_number)
     seeds = _seed_arrays(dgraph, inp)
-    table = _mask_table(dgraph, mask)
-    T, sn, seed = len(dgraph.types), int(sampled_number), int(seed)
-    if dgraph.device is None or dgraph.device.type != "cuda":
-        raise RuntimeError("pyhgt_amd: sample_subgraph_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host sibling is "
-                           "sample_subgraph_host)")
-    if dgraph.features is None:
-        raise ValueError("pyhgt_amd: the DeviceHeteroGraph carries no features")
-    st = _device_state(dgraph, [ids.size for ids, _ in seeds], sampled_depth, sn)
+    table = _call_table(dgraph, "sample_subgraph", mask)
+    T = len(dgraph.types)
+    st = _device_state(dgraph, [ids.size for ids, _ in seeds], sampled_depth, sampled_number)
     dev = st.dev
     with torch.cuda.device(dev):
-        if st.dirty:
-            st.clear()
-        for t, (ids, tms) in enumerate(seeds):
-            if ids.size:
-                st.seed_nodes(t, ids, tms, t)
-        for t, (ids, _) in enumerate(seeds):
-            if ids.size:
-                st.add_budget(t, t, ids.size, max_time, seed)
-        for layer in range(sampled_depth):
-            for t in range(T):
-                if st.cap_c[t] == 0:                         # nothing can ever be a candidate of this type
-                    continue
-                step = T * (1 + layer) + t
-                st.select(t, step, seed)
-                st.add_budget(t, step, sn, max_time, seed)
-        src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type = st.induce(table)
-        N = sum(n_per_type)
-        widths = sorted({f.size(1) for f in dgraph.features if f is not None and f.size(0) > 0})
-        if len(widths) > 1:
-            raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (widths,))
-        width = widths[0] if widths else 0
-        feat = torch.empty(N, width, dtype=torch.float32, device=dev)
+        src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type = st.draw(seeds, max_time, int(seed), table)
+        width = _feature_width(dgraph)
+        feat = torch.empty(sum(n_per_type), width, dtype=torch.float32, device=dev)
         off, stream = 0, torch.cuda.current_stream(dev).cuda_stream
         for t, n in enumerate(n_per_type):
             if n and width:
@@ -779,177 +907,6 @@ def sample_subgraph_device(dgraph, max_time, sampled_depth, sampled_number, inp,
 
 
 # ---------------------------------------------------------------------------------------------------------------- batched calls
-class BatchedDeviceSamplerState:
-    """`DeviceSamplerState` with a batch dimension: the device state of n_batch replicas of one (seed counts, depth, sampled_number)
-    shape of call and the step-level calls on all of them at once (one method per batched C entry point; replica b of every launch
-    is blockIdx.y = b).  Every array is one [n_batch, .] tensor: replica b is base + b * stride, and the strides are the fields of the
-    one table the kernels get (n_nodes, cap_sampled, cap_cand).  The per-node arrays (score / stamp / serial over every node of every
-    type, 20 bytes x nodes x B) live on the graph, apart from the single call's, sized for the largest n_batch seen; the lists, keys
-    and induction scratch (a few hundred KB per replica at the training shapes) belong to the state."""
-
-    def __init__(self, dgraph, n_seed, depth, sn, n_batch):
-        if dgraph.device is None or dgraph.device.type != "cuda":
-            raise RuntimeError("pyhgt_amd: sample_subgraphs_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host "
-                               "sibling is sample_subgraphs_host)")
-        if not 1 <= n_batch <= _lib.HGT_SAMPLER_MAX_BATCH:
-            raise ValueError("pyhgt_amd: 1 <= n_batch <= %d" % _lib.HGT_SAMPLER_MAX_BATCH)
-        self.g, self.dev, self.sn, self.depth, self.B = dgraph, dgraph.device, int(sn), int(depth), int(n_batch)
-        self.lib = _lib.load()
-        T, M, dev, B = len(dgraph.types), len(dgraph.triples), self.dev, self.B
-        self.T, self.M, self.R = T, M, len(dgraph.edge_dict)
-        self.cap_s, self.cap_c = _capacities(dgraph, n_seed, depth, sn)
-        if dgraph._batch_nodes is None or dgraph._batch_nodes[0][0].size(0) < B:
-            dgraph._batch_state.clear()                      # the cached states point into the arrays that go
-            dgraph._batch_nodes = ([torch.zeros(B, n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
-                                   [torch.zeros(B, n, dtype=torch.int64, device=dev) for n in dgraph.n_nodes],
-                                   [torch.full((B, n), -1, dtype=torch.int32, device=dev) for n in dgraph.n_nodes])
-            dgraph._batch_dirty = False
-        self.score, self.stamp, self.serial = dgraph._batch_nodes
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.sampled = [torch.zeros(B, c, **i32) for c in self.cap_s]
-        self.cand = [torch.zeros(B, c, **i32) for c in self.cap_c]
-        self.counts = torch.zeros(B, T, 4, **i32)
-        ptr = _lib.ptr
-        self.types_c = (_lib.HgtSamplerType * T)()           # the table of replica 0; the kernels shift it by b strides
-        for t in range(T):
-            self.types_c[t] = _lib.HgtSamplerType(ptr(self.score[t]), ptr(self.stamp[t]), ptr(self.serial[t]), ptr(self.sampled[t]),
-                                                  ptr(self.cand[t]), self.counts[0, t].data_ptr(), dgraph.n_nodes[t], self.cap_s[t],
-                                                  self.cap_c[t], 0)
-        self.triples_c = _triple_table(dgraph)
-        self.n_entries = _scratch_entries(self.lib, dgraph, self.types_c, self.triples_c, n_seed, sn)      # per replica
-        self.rowoff, self.hub = torch.zeros(B, self.n_entries, **i32), torch.zeros(B * self.n_entries, **i32)
-        self.n_tmp = max(self.cap_c + [1])
-        self.keys = torch.zeros(B, self.n_tmp, dtype=torch.int64, device=dev)
-        self.tmp = torch.zeros(B, self.n_tmp, **i32)
-        self.type_off, self.rel_ptr = torch.zeros(B, T + 1, **i32), torch.zeros(B, self.R + 1, **i32)
-        self.sizes, self.offs = torch.zeros(B, T + M + 2, **i32), torch.zeros(2 * (B + 1), **i32)
-
-    # the state rule of the single call with a flag of its own: the batched per-node arrays are another set of arrays
-    @property
-    def dirty(self):
-        return self.g._batch_dirty
-
-    @dirty.setter
-    def dirty(self, value):
-        self.g._batch_dirty = bool(value)
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.dev).cuda_stream
-
-    def _seeds_c(self, seeds):
-        if len(seeds) != self.B:
-            raise ValueError("pyhgt_amd: %d Philox seeds for %d replicas" % (len(seeds), self.B))
-        return (C.c_uint64 * self.B)(*[int(s) & (2 ** 64 - 1) for s in seeds])
-
-    def seed_nodes(self, t, ids, times, step):
-        """ids, times: [n_batch, n]"""
-        ids, times = (np.ascontiguousarray(a, dtype=np.int32) for a in (ids, times))
-        if ids.ndim != 2 or ids.shape[0] != self.B or times.shape != ids.shape:
-            raise ValueError("pyhgt_amd: seed ids and times must be [%d, n]" % self.B)
-        n = ids.shape[1]
-        ids, times = (torch.from_numpy(a).to(self.dev) for a in (ids, times))
-        self.dirty = True
-        _lib.check(self.lib.hgt_sampler_seed_batched(self.types_c, self.T, self.B, t, ids.data_ptr() if n else None,
-                                                     times.data_ptr() if n else None, n, step, self._stream()), "hgt_sampler_seed_batched")
-        ids.record_stream(torch.cuda.current_stream(self.dev))
-        times.record_stream(torch.cuda.current_stream(self.dev))
-
-    def add_budget(self, t, step, max_new, max_time, seeds):
-        self.dirty = True
-        _lib.check(self.lib.hgt_sampler_add_budget_batched(self.types_c, self.T, self.triples_c, self.M, self.B, t, step, self.sn, max_new,
-                                                           0 if max_time is None else 1, 0 if max_time is None else int(max_time),
-                                                           self._seeds_c(seeds), self.hub.data_ptr(), self.n_entries, self._stream()),
-                   "hgt_sampler_add_budget_batched")
-
-    def select(self, t, step, seeds):
-        self.dirty = True
-        _lib.check(self.lib.hgt_sampler_select_batched(self.types_c, self.T, self.B, t, step, self.sn, self._seeds_c(seeds),
-                                                       self.keys.data_ptr(), self.tmp.data_ptr(), self.n_tmp, self._stream()),
-                   "hgt_sampler_select_batched")
-
-    def induce(self, mask=None):
-        """count pass, the one host read of the call (sizes [n_batch, T + M + 2]), fill pass into buffers that hold the replicas one
-        after the other -> (src, dst, edge_time, rel_ptr [B, R + 1], type_off [B, T + 1], node_time, node_id, nodes per type [B][T],
-        node offsets [B + 1], edge offsets [B + 1]); indices are local to each piece."""
-        lib, T, M, B = self.lib, self.T, self.M, self.B
-        table = _mask_table(self.g, mask)
-        if table is None:
-            count, fill, tail, what = lib.hgt_sampler_induce_count_batched, lib.hgt_sampler_induce_fill_batched, (), "hgt_sampler_induce_batched"
-        else:
-            count, fill, tail = lib.hgt_sampler_induce_count_masked_batched, lib.hgt_sampler_induce_fill_masked_batched, (_masks_c(table, M),)
-            what = "hgt_sampler_induce_masked_batched"
-        _lib.check(count(self.types_c, T, self.triples_c, M, B, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
-                         self.type_off.data_ptr(), self.rel_ptr.data_ptr(), self.sizes.data_ptr(), *tail, self._stream()), what + " (count)")
-        sizes = self.sizes.cpu().numpy()                     # the host synchronisation of the batched call
-        if sizes[:, T + M].any():
-            raise RuntimeError("pyhgt_amd: a sampler list overflowed its static capacity or a seed id was out of range")
-        n_per_type = [[int(v) for v in row[:T]] for row in sizes]
-        nodes = np.array([sum(row) for row in n_per_type], dtype=np.int64)
-        node_off = np.concatenate([[0], np.cumsum(nodes)])
-        edge_off = np.concatenate([[0], np.cumsum(nodes + sizes[:, T + M + 1].astype(np.int64))])
-        N, E = int(node_off[-1]), int(edge_off[-1])
-        i32 = dict(dtype=torch.int32, device=self.dev)
-        src, dst, etime = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
-        node_time, node_id = torch.empty(N, **i32), torch.empty(N, **i32)
-        ptr = _lib.ptr
-        _lib.check(fill(self.types_c, T, self.triples_c, M, B, self.R, self.rowoff.data_ptr(), self.hub.data_ptr(), self.n_entries,
-                        self.type_off.data_ptr(), self.sizes.data_ptr(), self.offs.data_ptr(), N, E, ptr(src), ptr(dst), ptr(etime),
-                        ptr(node_time), ptr(node_id), *tail, self._stream()), what + " (fill)")
-        return src, dst, etime, self.rel_ptr.clone(), self.type_off.clone(), node_time, node_id, n_per_type, node_off, edge_off
-
-    def gather_features(self, type_off, node_id, n_per_type, width):
-        """the feature rows of every replica's nodes in one launch: float32 [nodes of the call, width].  self.offs still holds the
-        node offsets the fill pass wrote.  A type with rows and no matrix is an error of the caller, found here before the launch."""
-        N = int(node_id.numel())
-        feats = self.g.features
-        for t in range(self.T):
-            if width and feats[t] is None and any(row[t] for row in n_per_type):
-                raise ValueError("pyhgt_amd: no feature matrix for node type %r" % self.g.types[t])
-        out = torch.empty(N, width, dtype=torch.float32, device=self.dev)
-        mats = (C.c_void_p * self.T)(*[None if f is None or f.numel() == 0 else f.data_ptr() for f in feats])
-        rows = (C.c_int32 * self.T)(*[0 if f is None else int(f.size(0)) for f in feats])
-        _lib.check(self.lib.hgt_sampler_gather_features(mats, rows, self.T, self.B, width, type_off.data_ptr(), self.offs.data_ptr(),
-                                                        node_id.data_ptr() if N else None, N, out.data_ptr() if out.numel() else None,
-                                                        self._stream()), "hgt_sampler_gather_features")
-        return out
-
-    def reset(self):
-        _lib.check(self.lib.hgt_sampler_reset_batched(self.types_c, self.T, self.B, self._stream()), "hgt_sampler_reset_batched")
-        self.dirty = False
-
-    def clear(self):
-        """full clear of the batched per-node arrays (every replica the graph holds, not only this state's) and of the counters of
-        every cached batched state"""
-        for a in self.score + self.stamp:
-            a.zero_()
-        for a in self.serial:
-            a.fill_(-1)
-        for st in [self] + list(self.g._batch_state.values()):
-            st.counts.zero_()
-        self.dirty = False
-
-    def snapshot(self):
-        """host copies of the state, one dict per replica in the form of DeviceSamplerState.snapshot()"""
-        counts = self.counts.cpu().numpy()
-        u64 = lambda a: a.cpu().numpy().view(np.uint64)
-        score, stamp = [u64(a) for a in self.score], [u64(a) for a in self.stamp]
-        serial, sampled, cand = ([a.cpu().numpy() for a in v] for v in (self.serial, self.sampled, self.cand))
-        return [dict(score=[a[b] for a in score], stamp=[a[b] for a in stamp], serial=[a[b] for a in serial],
-                     sampled=[a[b, :counts[b, t, 0]].astype(np.int64) for t, a in enumerate(sampled)],
-                     cand=[a[b, :counts[b, t, 2]].astype(np.int64) for t, a in enumerate(cand)], counts=counts[b]) for b in range(self.B)]
-
-
-def _batched_state(dgraph, n_seed, depth, sn, n_batch):
-    key = (tuple(n_seed), int(depth), int(sn), int(n_batch))
-    st = dgraph._batch_state.get(key)
-    if st is None:
-        if len(dgraph._batch_state) >= 4:
-            dgraph._batch_state.clear()
-        st = BatchedDeviceSamplerState(dgraph, n_seed, depth, sn, n_batch)
-        dgraph._batch_state[key] = st                        # after the constructor: a larger n_batch empties the cache in there
-    return st
-
-
 def _batch_args(dgraph, inps, seeds):
     """-> (per replica the seed arrays of _seed_arrays, Philox seeds); every replica has the same number of seeds per type"""
     inps, seeds = list(inps), [int(s) for s in seeds]
@@ -985,37 +942,14 @@ def sample_subgraphs_device(dgraph, max_time, sampled_depth, sampled_number, inp
     Memory: 20 bytes x nodes of the graph x B for the per-node state, kept on the graph for the largest B seen."""
     _check_args(dgraph, sampled_depth, sampled_number)
     arrays, seeds = _batch_args(dgraph, inps, seeds)
-    table = _mask_table(dgraph, mask)
-    T, sn, B = len(dgraph.types), int(sampled_number), len(arrays)
-    if dgraph.device is None or dgraph.device.type != "cuda":
-        raise RuntimeError("pyhgt_amd: sample_subgraphs_device needs a DeviceHeteroGraph on a GPU (no CPU fallback; the host sibling is "
-                           "sample_subgraphs_host)")
-    if dgraph.features is None:
-        raise ValueError("pyhgt_amd: the DeviceHeteroGraph carries no features")
+    table = _call_table(dgraph, "sample_subgraphs", mask)
+    T, B = len(dgraph.types), len(arrays)
     n_seed = [ids.size for ids, _ in arrays[0]]
-    st = _batched_state(dgraph, n_seed, sampled_depth, sn, B)
-    dev = st.dev
-    with torch.cuda.device(dev):
-        if st.dirty:
-            st.clear()
-        for t in range(T):
-            if n_seed[t]:
-                st.seed_nodes(t, np.stack([a[t][0] for a in arrays]), np.stack([a[t][1] for a in arrays]), t)
-        for t in range(T):
-            if n_seed[t]:
-                st.add_budget(t, t, n_seed[t], max_time, seeds)
-        for layer in range(sampled_depth):
-            for t in range(T):
-                if st.cap_c[t] == 0:
-                    continue
-                step = T * (1 + layer) + t
-                st.select(t, step, seeds)
-                st.add_budget(t, step, sn, max_time, seeds)
-        src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type, node_off, edge_off = st.induce(table)
-        widths = sorted({f.size(1) for f in dgraph.features if f is not None and f.size(0) > 0})
-        if len(widths) > 1:
-            raise ValueError("pyhgt_amd: feature matrices of different widths: %r" % (widths,))
-        feat = st.gather_features(type_off, node_id, n_per_type, widths[0] if widths else 0)
+    st = _batched_state(dgraph, n_seed, sampled_depth, sampled_number, B)
+    with torch.cuda.device(st.dev):
+        stacked = [tuple(np.stack([a[t][k] for a in arrays]) for k in (0, 1)) for t in range(T)]      # per type ids, times [B, n]
+        src, dst, etime, rel_ptr, type_off, node_time, node_id, n_per_type, node_off, edge_off = st.draw(stacked, max_time, seeds, table)
+        feat = st.gather_features(type_off, node_id, n_per_type, _feature_width(dgraph))
         st.reset()
         ids64, out = node_id.long(), []
         for b in range(B):

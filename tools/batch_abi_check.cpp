@@ -105,6 +105,46 @@ int main() {
     EXPECT(hgt_sampler_reset_batched(nullptr, T, B, nullptr), HGT_ERR_INVALID_ARG);
     EXPECT(hgt_sampler_reset_batched(ty, T + 1, B, nullptr), HGT_ERR_UNSUPPORTED);
 
+    // two checks fail at once: the code is that of the first -- the tables (and for the induce calls the relations), n_batch, the
+    // seeds (the masks), then what the single entry point checks in its own order
+    EXPECT(hgt_sampler_seed_batched(nullptr, T, B + 1, 0, q, q, 2, 0, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_seed_batched(ty, T + 1, 0, 0, q, q, 2, 0, nullptr), HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_seed_batched(ty, T, B + 1, T, q, q, 2, 0, nullptr), HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_seed_batched(ty, T, 0, 0, q, q, 5, 0, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_seed_batched(ty, T, B, 0, nullptr, nullptr, 5, 0, nullptr), HGT_ERR_WORKSPACE);
+    EXPECT(hgt_sampler_add_budget_batched(nullptr, T, tr, M, B + 1, 0, 0, 4, 2, 0, 0, seeds.data(), q, 64, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_add_budget_batched(ty, T, tr, M, B + 1, 0, 0, 4, 2, 0, 0, nullptr, q, 64, nullptr), HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_add_budget_batched(ty, T, tr, M, B, 0, 0, HGT_SAMPLER_MAX_NUMBER + 1, 2, 0, 0, nullptr, q, 64, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_add_budget_batched(ty, T, tr, M, B, T, 0, 4, 2, 0, 0, seeds.data(), q, 2 * into0, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_add_budget_batched(ty, T, tr, M, B, 0, 0, HGT_SAMPLER_MAX_NUMBER + 1, -1, 0, 0, seeds.data(), q, 64, nullptr),
+           HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_add_budget_batched(ty, T, tr, M, B, 0, 0, HGT_SAMPLER_MAX_NUMBER + 1, 2, 0, 0, seeds.data(), q, 2 * into0, nullptr),
+           HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_add_budget_batched(ty, T, tr, M, B, 0, 0, 4, INT_MAX, 0, 0, seeds.data(), nullptr, 0, nullptr), HGT_ERR_TOO_LARGE);
+    EXPECT(hgt_sampler_add_budget_batched(ty, T, tr, M, B, 0, 0, 4, 2, 0, 0, seeds.data(), nullptr, 2 * into0, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_add_budget_batched(ty, T, tr, M, 0, 0, 0, 4, 0, 0, 0, seeds.data(), nullptr, 0, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_select_batched(ty, T + 1, 0, 0, 0, 4, seeds.data(), k, q, 8, nullptr), HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_select_batched(ty, T, B + 1, 0, 0, 4, nullptr, k, q, 8, nullptr), HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_select_batched(ty, T, B, 0, 0, HGT_SAMPLER_MAX_NUMBER + 1, nullptr, k, q, 8, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_select_batched(ty, T, B, T, 0, 4, seeds.data(), k, q, 7, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_select_batched(ty, T, B, 0, 0, HGT_SAMPLER_MAX_NUMBER + 1, seeds.data(), nullptr, q, 7, nullptr), HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_select_batched(ty, T, B, 0, 0, 4, seeds.data(), nullptr, q, 7, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_induce_count_batched(ty, T, tr, M, B + 1, 0, q, q, slots + 1, q, q, q, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_induce_count_masked_batched(ty, T, tr, M, B + 1, R, q, q, slots + 1, q, q, q, nullptr, nullptr), HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_induce_count_masked_batched(ty, T, tr, M, B, R, nullptr, q, slots, q, q, q, nullptr, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_induce_count_batched(ty, T, tr, M, 0, R, q, q, slots, q, q, q, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_induce_count_batched(ty, T, tr, M, B, R, nullptr, q, slots, q, q, q, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_induce_fill_batched(ty, T, tr, M, B + 1, 0, q, q, slots + 1, q, q, q, 4, 6, q, q, q, q, q, nullptr), HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_induce_fill_masked_batched(ty, T, tr, M, B + 1, R, q, q, slots + 1, q, q, q, 4, 6, q, q, q, q, q, nullptr, nullptr),
+           HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_induce_fill_batched(ty, T, tr, M, B, R, q, q, slots, q, q, q, 4, (int64_t)INT_MAX + 1, q, q, q, q, q, nullptr),
+           HGT_ERR_TOO_LARGE);
+    EXPECT(hgt_sampler_induce_fill_batched(ty, T, tr, M, B, R, q, q, slots + 1, q, nullptr, q, 4, (int64_t)INT_MAX + 1, q, q, q, q, q, nullptr),
+           HGT_ERR_INVALID_ARG);
+    EXPECT(hgt_sampler_induce_fill_batched(ty, T, tr, M, B, R, q, q, slots, q, q, q, 4, 6, nullptr, q, q, q, q, nullptr), HGT_ERR_WORKSPACE);
+    EXPECT(hgt_sampler_reset_batched(ty, T + 1, 0, nullptr), HGT_ERR_UNSUPPORTED);
+    EXPECT(hgt_sampler_reset_batched(nullptr, T, B + 1, nullptr), HGT_ERR_INVALID_ARG);
+
     // features: exactly n_types pointers and row counts are read
     std::vector<const float*> feats(T, (const float*)p);
     std::vector<int32_t> rows(T, 8);
